@@ -5,12 +5,21 @@
   python bench.py --gpus N                                 # launches N ranks itself (one per GPU, RCCL), prints rank 0's line
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...     # what the driver does; same result
   python bench.py --gpus N --shard-frozen                  # fsdp.yaml-equivalent: frozen decoder weights sharded 1/N as well
+  python bench.py --full                                   # + roofline, GEMM family, CPU baseline, sharded-frozen variant (N > 1)
+  python bench.py --dump-outputs DIR                       # + the last timed step's results as DIR/*.npy
 
 A "step" = forward through CLIP tower + STC connector + splice + 32 Mistral layers (+LoRA) + brain head,
 backward through head and decoder (LoRA A/B gradients), global-norm clip, AdamW, cosine LR - all on
-libvlb HIP kernels, inputs resident in HBM.  One JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel:
-the 256x256 MFMA GEMM call of the gate/up projection, timed with HIP events on its own stream inside the
-timed region) and `cpu_baseline` (the oracle on the host cores, bounded sample, N=1 only).
+libvlb HIP kernels, inputs resident in HBM.  One JSON line on rank 0 (contract in the task statement).  A plain run sets up,
+warms up, times --steps steps and prints the line (`value` clips/s, `ms_per_step`); nothing else runs.  --full adds, as
+before: `roofline` (dominant kernel: the 256x256 MFMA GEMM call of the gate/up projection, timed with HIP events on its own
+stream inside the timed region), `gemm_family` (two extra untimed steps), `cpu_baseline` (the oracle on the host cores,
+bounded sample, N=1 only) and, at N > 1, the sharded-frozen variant.
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller: `loss.npy` (the loss
+training_step returned) and one `<name>.npy` per trainable tensor after that step's optimiser update (fp32 masters; a tensor
+larger than DUMP_SAMPLE elements is stored as a fixed, seeded sample of DUMP_SAMPLE of them).  Weights, adapters, head and
+clips are seeded, so the same arguments give the same inputs on every run.  Single-process runs only.
 """
 from __future__ import annotations
 
@@ -44,6 +53,9 @@ def gateup_traffic(shape, prefix=""):
 # algorithmic TFLOP per clip
 TFLOP_PER_CLIP = {"frozen": 36.53, "lora": 67.8, "full": 100.8}
 
+DUMP_SAMPLE = 16384            # elements kept per trainable tensor by --dump-outputs (all of a smaller one)
+DUMP_LIMIT_BYTES = 64 << 20
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -62,7 +74,30 @@ def parse():
                     help="keep the dense [B, max_len] token layout (compute the padded tail rows too)")
     ap.add_argument("--shard-frozen", action="store_true",
                     help="fsdp.yaml-equivalent: keep 1/N of every frozen decoder layer per rank, all-gather one layer ahead")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the gate/up GEMM roofline probe, the long-K GEMM family "
+                         "(2 extra steps), the CPU baseline and, at N > 1, the sharded-frozen variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and updated trainables as DIR/<name>.npy (single process only)")
     return ap.parse_args()
+
+
+def dump_outputs(d, loss, named_params):
+    """--dump-outputs: the loss and the trainables (after the step's update) as fp32 .npy files in d."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    for i, (n, t) in enumerate(named_params):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng([1234, i]).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arrays[n] = flat.float().cpu().numpy()
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    for n, v in arrays.items():
+        np.save(os.path.join(d, n + ".npy"), v)
+    print(f"bench.py: wrote {len(arrays)} arrays ({total / 2 ** 20:.1f} MiB) to {d}", file=sys.stderr)
 
 
 def cpu_baseline(num_target, lora):
@@ -157,6 +192,9 @@ def launch_ranks(a) -> int:
 
 def main():
     a = parse()
+    if a.dump_outputs and (a.gpus > 1 or os.environ.get("WORLD_SIZE", "1") != "1" or os.environ.get("VLB_FORCE_DIST") == "1"):
+        print("bench.py: --dump-outputs is for single-process runs (--gpus 1)", file=sys.stderr)
+        sys.exit(2)
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(launch_ranks(a))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -248,8 +286,8 @@ def main():
 
     for _ in range(a.warmup):
         step()
-    # ---- dominant-kernel timing: event pairs around every gate/up GEMM launch of the timed steps
-    probe = ops.enable_gemm_probe(N=2 * g.ff, K=g.dim)
+    # ---- dominant-kernel timing (--full): event pairs around every gate/up GEMM launch of the timed steps
+    probe = ops.enable_gemm_probe(N=2 * g.ff, K=g.dim) if a.full else None
     barrier()
     ops.profile_marker()                      # kernel traces are cut to [marker, marker] by tools/profile_tables.py
     barrier()
@@ -264,11 +302,13 @@ def main():
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
-    kern_ms, launches, (pM, pN, pK) = probe.result()
+    if a.dump_outputs:                        # before anything else steps the model
+        dump_outputs(a.dump_outputs, loss, m.trainable_named_parameters())
+    kern_ms, launches, (pM, pN, pK) = probe.result() if probe is not None else (0.0, 0, (0, 0, 0))
     # ---- the whole long-K GEMM family (every four-wave launch: plain, gate/up + SwiGLU, masked-pair dgrads, with their tail
     # launches), from event pairs around each call in TWO EXTRA steps after the timed region (the pairs cost ~2 us per GEMM,
     # so they stay out of `value`); vision prefetch off for these so no side-stream kernel runs under a timed call
-    fam_steps = 2 if a.geometry == "7b" and not a.fp8 else 0
+    fam_steps = 2 if a.full and a.geometry == "7b" and not a.fp8 else 0
     family = None
     if fam_steps and rank == 0 or (fam_steps and use_dist):
         fprobe = ops.enable_gemm_probe(N=2 * g.ff, K=g.dim, family=True)
@@ -288,15 +328,9 @@ def main():
                   "frac_of_bf16_peak": round(tot_tf / (tot_ms * 1e-3) / PEAK_BF16_TFLOPS, 4) if tot_ms else 0.0,
                   "by_kind": {k: {"calls_per_step": v[0] // fam_steps, "ms_per_step": round(v[1] / fam_steps, 2),
                                   "tflops": round(v[2] / (v[1] * 1e-3), 1)} for k, v in sorted(fam.items())}}
-    # the recorded collections are per call KIND: LoRA / frozen calls under the bare shape, the fp8 call under "fp8:", the plain
-    # bf16 call of the full fine-tune (no collection on record) under "full:"
-    traffic, traffic_src = gateup_traffic((pM, pN, pK), "fp8:" if a.fp8 else "full:" if full else "")
     if rank == 0:
         clips = world * B * a.steps
         value = clips / dt
-        flops_launch = 2.0 * pM * pN * pK
-        achieved = flops_launch / (kern_ms * 1e-3) / 1e12 if kern_ms else 0.0
-        peak_tf = PEAK_FP8_TFLOPS if a.fp8 else PEAK_BF16_TFLOPS
         out = {
             "metric": "clips/sec fine-tune VideoLLaMA2-7B+LoRA->2k-voxel head, 1/2/4/8 MI355X",
             "value": round(value, 4), "unit": "clips/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -327,24 +361,31 @@ def main():
                        # executed FLOPs: the per-clip figure scaled by the rows actually run (conservative: the vision tower is not reduced)
                        "step_tflops_per_gpu": round(value / world * TFLOP_PER_CLIP[a.workload] * rows_run / rows_dense, 1),
                        "step_frac_of_bf16_mfma_peak": round(value / world * TFLOP_PER_CLIP[a.workload] * rows_run / rows_dense / PEAK_BF16_TFLOPS, 4)},
-            "roofline": {"bound": "mfma", "kernel": (f"gemm_mxfp8 kernel (256x256x128 tile, 4 waves x 128x128, v_mfma_scale_f32_16x16x128_f8f6f4) + the re-cut launch of its partial "
-                                                     f"last round on the gate/up projection [{pM}x{pK}]x[{pN}x{pK}]^T, per vlb_gemm_mxfp8 call; peak = dense fp8 MFMA" if a.fp8 else
-                                                     "gemm_w4_kernel (256x256x64 tile, 4 waves x 128x128) + the split-K launches of its partial last wave "
-                         f"on the gate/up projection [{pM}x{pK}]x[{pN}x{pK}]^T, per "
-                         + ("vlb_gemm_swiglu_save call (epilogue: + LoRA pair, SwiGLU, saved pre-activations; FLOPs counted: the base GEMM only)" if lora
-                            else "vlb_gemm_bf16 call")), "achieved": round(achieved, 1), "peak": peak_tf,
-                         "unit": "TFLOP/s", "frac": round(achieved / peak_tf, 4),
-                         "traffic": traffic,
-                         "traffic_note": (f"L2->fabric bytes per call from rocprofv3 PMC passes ({traffic_src}, via profiles/gateup_traffic.json); "
-                                          if traffic is not None else "no PMC collection on record for this shape (profiles/gateup_traffic.json); ")
-                         + (f"algorithmic {2.0 * (pM * (pK + 64) + pN * (pK + 64)) + 2.0 * pM * pN + 1.0 * pM * pN:.3e} (A | t, W | B, saved [gate|up] [M,N] and silu(gate)*up [M,N/2], bf16)" if lora else
-                            f"algorithmic {(pM * pK + pN * pK) * (1 + 1 / 32) + 2.0 * pM * pN:.3e} (e4m3 A + W with their E8M0 scales, C [M,N] bf16)" if a.fp8 else
-                            f"algorithmic {2.0 * (pM * pK + pN * pK) + 2.0 * pM * pN:.3e} (A + W + C [M,N] bf16)" if full else
-                            f"algorithmic {2.0 * (pM * pK + pN * pK) + 1.0 * pM * pN:.3e} (A + W + SwiGLU-fused C [M,N/2] bf16)"),
-                         "flops_per_launch": flops_launch, "avg_launch_ms": round(kern_ms, 4), "launches_timed": launches},
-            "gemm_family": family,
         }
-        if world == 1 and not a.no_cpu_baseline and a.geometry == "7b" and not full:
+        if a.full:
+            # the recorded collections are per call KIND: LoRA / frozen calls under the bare shape, the fp8 call under "fp8:", the plain
+            # bf16 call of the full fine-tune (no collection on record) under "full:"
+            traffic, traffic_src = gateup_traffic((pM, pN, pK), "fp8:" if a.fp8 else "full:" if full else "")
+            flops_launch = 2.0 * pM * pN * pK
+            achieved = flops_launch / (kern_ms * 1e-3) / 1e12 if kern_ms else 0.0
+            peak_tf = PEAK_FP8_TFLOPS if a.fp8 else PEAK_BF16_TFLOPS
+            out["roofline"] = {"bound": "mfma", "kernel": (f"gemm_mxfp8 kernel (256x256x128 tile, 4 waves x 128x128, v_mfma_scale_f32_16x16x128_f8f6f4) + the re-cut launch of its partial "
+                                                           f"last round on the gate/up projection [{pM}x{pK}]x[{pN}x{pK}]^T, per vlb_gemm_mxfp8 call; peak = dense fp8 MFMA" if a.fp8 else
+                                                           "gemm_w4_kernel (256x256x64 tile, 4 waves x 128x128) + the split-K launches of its partial last wave "
+                               f"on the gate/up projection [{pM}x{pK}]x[{pN}x{pK}]^T, per "
+                               + ("vlb_gemm_swiglu_save call (epilogue: + LoRA pair, SwiGLU, saved pre-activations; FLOPs counted: the base GEMM only)" if lora
+                                  else "vlb_gemm_bf16 call")), "achieved": round(achieved, 1), "peak": peak_tf,
+                               "unit": "TFLOP/s", "frac": round(achieved / peak_tf, 4),
+                               "traffic": traffic,
+                               "traffic_note": (f"L2->fabric bytes per call from rocprofv3 PMC passes ({traffic_src}, via profiles/gateup_traffic.json); "
+                                                if traffic is not None else "no PMC collection on record for this shape (profiles/gateup_traffic.json); ")
+                               + (f"algorithmic {2.0 * (pM * (pK + 64) + pN * (pK + 64)) + 2.0 * pM * pN + 1.0 * pM * pN:.3e} (A | t, W | B, saved [gate|up] [M,N] and silu(gate)*up [M,N/2], bf16)" if lora else
+                                  f"algorithmic {(pM * pK + pN * pK) * (1 + 1 / 32) + 2.0 * pM * pN:.3e} (e4m3 A + W with their E8M0 scales, C [M,N] bf16)" if a.fp8 else
+                                  f"algorithmic {2.0 * (pM * pK + pN * pK) + 2.0 * pM * pN:.3e} (A + W + C [M,N] bf16)" if full else
+                                  f"algorithmic {2.0 * (pM * pK + pN * pK) + 1.0 * pM * pN:.3e} (A + W + SwiGLU-fused C [M,N/2] bf16)"),
+                               "flops_per_launch": flops_launch, "avg_launch_ms": round(kern_ms, 4), "launches_timed": launches}
+            out["gemm_family"] = family
+        if a.full and world == 1 and not a.no_cpu_baseline and a.geometry == "7b" and not full:
             out["cpu_baseline"] = cpu_baseline(cfg.num_target, lora)
     else:
         out = None
@@ -367,7 +408,7 @@ def main():
     # headline number above is already final; should the extra variant's collectives stall, a watchdog on every rank prints
     # the line with the stall recorded in it, says so on stderr and exits NON-ZERO (3): a hang is never reported as success.
     shard_variant = None
-    if world > 1 and not a.shard_frozen and not full and os.environ.get("VLB_BENCH_SHARD_VARIANT", "1") == "1":
+    if a.full and world > 1 and not a.shard_frozen and not full and os.environ.get("VLB_BENCH_SHARD_VARIANT", "1") == "1":
         limit_s = float(os.environ.get("VLB_BENCH_SHARD_VARIANT_LIMIT_S", "120"))
 
         def bail():

@@ -9,6 +9,8 @@ import re
 import numpy as np
 import torch
 
+from gen_golden import load_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 
@@ -25,7 +27,7 @@ def test_oracle_reproduces_frozen_golden():
     """Same seeds -> same weights (sha256), same inputs, same loss / prediction / head gradients."""
     import vlb_oracle as O
     g = O.geometry_mini()
-    gold = np.load(os.path.join(GOLD, "mini_frozen.npz"))
+    gold = load_golden("mini_frozen.npz")
     p = O.round_bf16(O.init_params(g, seed=1234))
     assert _digest(p) == str(gold["weights_sha256"])
     batch = O.synthetic_batch(g, 4, seed=1234)
@@ -48,7 +50,7 @@ def test_oracle_reproduces_frozen_golden():
 def test_oracle_lora_golden_loss_and_norm():
     import vlb_oracle as O
     g = O.geometry_mini()
-    gold = np.load(os.path.join(GOLD, "mini_lora.npz"))
+    gold = load_golden("mini_lora.npz")
     p = O.round_bf16(O.init_params(g, seed=1234, lora=True, lora_b_std=0.02))
     assert _digest(p) == str(gold["weights_sha256"])
     batch = O.synthetic_batch(g, 4, seed=1234)

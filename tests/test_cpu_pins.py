@@ -2,7 +2,7 @@
 in-container cross-checks for the rows no importable reference exists for (connector, splice, LoRA: "parity
 unpinned" - the upstream VideoLLaMA2 / timm / peft sources are absent).
 
-* head  == the reference's OWN src/utils.py layers   (needs /root/reference; skipped on the GPU box)
+* head  == what the reference's OWN src/utils.py layers computed   (tests/golden/ref_head.npz, written by oracle/gen_golden.py)
 * CLIP  == transformers.CLIPVisionModel, Mistral == transformers.MistralModel   (needs transformers)
 * tests/golden/*.npz == oracle/gen_golden.build_golden() today: the oracle and its fixtures cannot drift apart
 * LoRA forward / gradients == torch autograd on the explicitly merged weight W + s.B.A (and the dropout form)
@@ -22,7 +22,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
-have_reference = os.path.isfile("/root/reference/src/utils.py")
 try:
     import transformers  # noqa: F401
     have_transformers = True
@@ -30,10 +29,9 @@ except Exception:  # pragma: no cover
     have_transformers = False
 
 
-@pytest.mark.skipif(not have_reference, reason="the reference tree only exists in the build container")
 def test_pin_head_against_the_reference_layers():
     import gen_golden
-    gen_golden.pin_head()
+    gen_golden.check_head(np.load(os.path.join(GOLD, "ref_head.npz")), exact=False)
 
 
 @pytest.mark.skipif(not have_transformers, reason="transformers not importable")
@@ -48,57 +46,6 @@ def test_pin_mistral_decoder_against_transformers():
     import gen_golden
     import vlb_oracle as O
     gen_golden.pin_mistral(O.geometry_mini())
-
-
-@pytest.mark.skipif(not (have_reference and have_transformers), reason="the reference tree only exists in the build container")
-def test_committed_reference_fixtures_equal_a_fresh_run_of_the_reference():
-    """tests/golden/ref_{weight_mask.npz,linear_names.json,datamodule.json} == what the reference's own make_weight_mask /
-    find_all_linear_names / datamodule produce today (oracle/gen_ref_fixtures.generate(): the python3.10 side)."""
-    import json
-    import gen_ref_fixtures as G
-    fresh = G.generate()
-    gold = np.load(os.path.join(GOLD, "ref_weight_mask.npz"))
-    assert set(gold.files) == set(fresh["weight_mask"])
-    for k in gold.files:
-        assert np.array_equal(gold[k], np.asarray(fresh["weight_mask"][k])), k
-    for name in ("linear_names", "datamodule"):
-        with open(os.path.join(GOLD, f"ref_{name}.json")) as f:
-            assert json.load(f) == json.loads(json.dumps(fresh[name])), name
-
-
-@pytest.mark.skipif(not (have_reference and os.path.exists("/opt/conda/bin/python3.9")), reason="build container only")
-def test_committed_reference_pipeline_files_equal_a_fresh_run_of_the_reference(tmp_path):
-    """tests/golden/ref_pipeline/ == what the reference's extractfeatures / lazyloading scripts write today
-    (oracle/gen_ref_fixtures_py39.py re-run into a scratch directory; datasets compared one by one)."""
-    import json
-    import subprocess
-    from phantom_vlb_amd import h5lite
-    env = {k: v for k, v in os.environ.items() if not k.startswith("PYTHON")}
-    env["VLB_REF_PIPELINE_OUT"] = str(tmp_path / "ref_pipeline")
-    subprocess.run(["/opt/conda/bin/python3.9", "-W", "ignore", os.path.join(ROOT, "oracle", "gen_ref_fixtures_py39.py")],
-                   check=True, env=env, capture_output=True)
-    gold_dir = os.path.join(GOLD, "ref_pipeline")
-
-    def walk(g, prefix=""):
-        for k in g.keys():
-            item = g[k]
-            if hasattr(item, "keys"):
-                yield from walk(item, f"{prefix}{k}/")
-            else:
-                yield f"{prefix}{k}", np.array(item)
-
-    files = sorted(os.path.relpath(os.path.join(dp, fn), gold_dir) for dp, _, fns in os.walk(gold_dir) for fn in fns)
-    fresh_dir = env["VLB_REF_PIPELINE_OUT"]
-    assert files == sorted(os.path.relpath(os.path.join(dp, fn), fresh_dir) for dp, _, fns in os.walk(fresh_dir) for fn in fns)
-    for rel in files:
-        if rel.endswith(".json"):
-            with open(os.path.join(gold_dir, rel)) as a, open(os.path.join(fresh_dir, rel)) as b:
-                assert json.load(a) == json.load(b)
-            continue
-        a, b = dict(walk(h5lite.File(os.path.join(gold_dir, rel)))), dict(walk(h5lite.File(os.path.join(fresh_dir, rel))))
-        assert a.keys() == b.keys(), rel
-        for k in a:
-            assert a[k].dtype == b[k].dtype and np.array_equal(a[k], b[k]), (rel, k)
 
 
 @pytest.mark.skipif(not have_transformers, reason="transformers not importable")
@@ -128,7 +75,7 @@ def test_clip_preprocess_equals_the_hf_clip_image_processor():
 def test_committed_goldens_equal_a_fresh_generation(tag):
     import gen_golden
     fresh = gen_golden.build_golden(tag)
-    gold = np.load(os.path.join(GOLD, f"mini_{tag}.npz"))
+    gold = gen_golden.load_golden(f"mini_{tag}.npz")
     assert set(gold.files) == set(fresh)
     for k in gold.files:
         a, b = gold[k], np.asarray(fresh[k])

@@ -236,15 +236,16 @@ def test_two_rank_full_shard_finetune_matches_single_process(dev, fp8):
 
 
 def test_bench_gpus_2_launches_two_ranks(dev):
-    """`python bench.py --gpus 2` with no launcher: two ranks are started (time-sharing this GPU over gloo), rank 0
-    prints ONE JSON line with n_gpus 2; asking for more RCCL ranks than GPUs fails instead of running fewer."""
+    """`python bench.py --gpus 2 --full` with no launcher: two ranks are started (time-sharing this GPU over gloo), rank 0
+    prints ONE JSON line with n_gpus 2 and the sharded-frozen variant; asking for more RCCL ranks than GPUs fails instead
+    of running fewer."""
     import json
     import subprocess
     env = dict(os.environ, VLB_DIST_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--geometry", "mini", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from gen_golden import load_golden
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -29,7 +30,7 @@ def mini_frozen(dev):
     g = O.geometry_mini()
     p = O.round_bf16(O.init_params(g, seed=1234))
     batch = O.synthetic_batch(g, 4, seed=1234)
-    gold = np.load(os.path.join(GOLD, "mini_frozen.npz"))
+    gold = load_golden("mini_frozen.npz")
     # the fixture and the regenerated inputs must be the same data
     assert np.array_equal(gold["language"], batch["language"].numpy())
     assert np.allclose(gold["vision_probe"], batch["vision"][:, 0, 0, :4, :4].numpy())
@@ -156,3 +157,34 @@ def test_vision_prefetch_is_bit_identical_and_consumed_once(dev):
     l3 = float(m.training_step(batch))                      # picks the prefetched features up
     torch.cuda.synchronize()
     assert l0 == l1 == l2 == l3 and len(bb._vis_queue) == 0
+
+
+def test_bench_dump_outputs_are_reproducible(dev, tmp_path):
+    """`python bench.py --dump-outputs DIR` (mini geometry, default LoRA workload): a plain run prints ONE line with the steps
+    asked for, ms_per_step and none of the --full figures, writes the last timed step's loss and trainables as fp32 .npy
+    files, and a second run with the same arguments writes the same arrays, bit for bit (seeded inputs, fixed-order kernels)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "VLB_FORCE_DIST"):
+        env.pop(k, None)
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--geometry", "mini", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(out) == 1, r.stdout[-2000:]
+        lines.append(json.loads(out[0]))
+    for out in lines:
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert not {"roofline", "gemm_family", "cpu_baseline"} & set(out)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and "loss.npy" in files and "ridge_layer.linear.weight.npy" in files
+    assert any(".lora_A." in f for f in files) and any(".lora_B." in f for f in files)
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == np.float32 and x.size > 0 and np.array_equal(x, y), f
+    assert abs(float(np.load(tmp_path / "a" / "loss.npy")[0]) - lines[0]["config"]["loss"]) <= 1e-6

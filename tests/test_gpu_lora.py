@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from gen_golden import load_golden
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -213,7 +214,7 @@ def test_mini_lora_training_step_vs_golden(dev):
     g = O.geometry_mini()
     p = O.round_bf16(O.init_params(g, seed=1234, lora=True, lora_b_std=0.02))
     batch = O.synthetic_batch(g, 4, seed=1234)
-    gold = np.load(os.path.join(GOLD, "mini_lora.npz"))
+    gold = load_golden("mini_lora.npz")
     m = VLBLitModule(_lora_cfg())
     m.configure_model(state_dict=p, head_state=p)
     m.lora = LoraState(m.geometry, m.backbone.w, 16, 32, 0.0, m.device, sd=p)
@@ -257,7 +258,7 @@ def test_validation_step_applies_the_adapters(dev):
     g = O.geometry_mini()
     p = O.round_bf16(O.init_params(g, seed=1234, lora=True, lora_b_std=0.02))
     batch = O.synthetic_batch(g, 4, seed=1234)
-    gold = np.load(os.path.join(GOLD, "mini_lora.npz"))
+    gold = load_golden("mini_lora.npz")
     m = VLBLitModule(_lora_cfg())
     m.configure_model(state_dict=p, head_state=p)
     m.lora = LoraState(m.geometry, m.backbone.w, 16, 32, 0.1, m.device, sd=p)      # dropout configured: must be off in eval
