@@ -261,6 +261,30 @@ int vlb_head_bwd(const void* hidden, const float* wmask, const void* ln1_w, cons
                  float* ws, float* dz_ws, float* dpooled_ws, void* dhidden, int B, int S, int E, int V, float eps,
                  float l2_lambda, float loss_scale, float l2_scale, const int* cu_rows, int total_rows, void* stream);
 
+/* Frozen-backbone feature cache.  Everything of the head after the pooling reads only pooled_raw [B,E] and sumw [B]
+ * (the vlb_head_fwd outputs above); with a frozen backbone they are a fixed function of the clip, so they can be kept per
+ * clip in cache_pooled fp32 [n_rows,E] / cache_sumw fp32 [n_rows] and the head trained from there.
+ * rows: DEVICE int32 [B], cache row of batch position b; the caller checks them against [0, n_rows) before upload.
+ * vlb_feature_cache_store: cache row rows[b] <- (pooled_raw[b], sumw[b]); rows[b] = -1 stores nothing for position b.
+ *   The caller never names a row that already holds a value (first write wins: a clip's cached value never changes).
+ * vlb_head_fwd_cached: pooled_raw[b] / sumw[b] <- cache row rows[b] (kept for the backward), then the LN2 / dropout /
+ *   ridge / loss launches of vlb_head_fwd, unchanged: same (pooled_raw, sumw) in, same bits out.  ws holds
+ *   vlb_head_ws_floats(B, 1, E, V) floats or more.
+ * vlb_head_bwd_cached: vlb_head_bwd without hidden / wmask / stats / dhidden (the parameter gradients only, the same
+ *   launches). */
+int vlb_feature_cache_store(const float* pooled_raw, const float* sumw, const int32_t* rows, float* cache_pooled,
+                            float* cache_sumw, int B, int E, int n_rows, void* stream);
+int vlb_head_fwd_cached(const float* cache_pooled, const float* cache_sumw, const int32_t* rows, const void* ln1_w,
+                        const void* ln1_b, const void* ln2_w, const void* ln2_b, const void* ridge_w, const void* ridge_b,
+                        const float* y, const float* keep_scale, float* ws, float* pooled_raw, float* sumw, float* zhat,
+                        float* ln2_rstd, void* z, float* pred, float* loss_terms, int B, int E, int V, int n_rows, float eps,
+                        float l2_lambda, void* stream);
+int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
+                        const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd, const void* z,
+                        const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
+                        float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, float eps,
+                        float l2_lambda, float loss_scale, float l2_scale, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * LoRA adapters (peft LoraConfig(r, lora_alpha, lora_dropout) + get_peft_model, litmodule :113-120):
  *   y = x W^T + s * B(A(dropout_p(x))),  s = alpha/r; only A [r,in] and B [out,r] train.

@@ -55,6 +55,9 @@ SIGNATURES = {
     "vlb_head_ws_floats": [I, I, I, I],
     "vlb_head_fwd": [P] * 19 + [I, I, I, I, F, F, P, P],
     "vlb_head_bwd": [P] * 24 + [I, I, I, I, F, F, F, F, P, I, P],
+    "vlb_feature_cache_store": [P] * 5 + [I, I, I, P],
+    "vlb_head_fwd_cached": [P] * 19 + [I, I, I, I, F, F, P],
+    "vlb_head_bwd_cached": [P] * 20 + [I, I, I, F, F, F, F, P],
     "vlb_gemm_bf16_masked_pair": [P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P],
     "vlb_gemm_masked_pair_swiglu_bwd": [P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P, L, P],
     "vlb_gemm_bf16_masked_pair_ws": [P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P, L, P],

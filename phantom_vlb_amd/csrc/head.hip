@@ -185,6 +185,32 @@ __global__ __launch_bounds__(1024) void head_ln2_kernel(const float* __restrict_
   if (threadIdx.x == 0) ln2_rstd[b] = rstd;
 }
 
+// ---------------------------------------------------------------- feature cache: scatter / gather of (pooled_raw, sumw)
+// Everything downstream of head_reduce_kernel reads only pooled_raw [B,E] and sumw [B], so a frozen backbone's clip is
+// fully described by those two; they are stored per clip in cache rows [N,E] / [N] and copied back verbatim (fp32, no
+// arithmetic).  grid (ceil(E/256), B).  rows[b] < 0 skips position b; a row outside [0, n_rows) is never touched (the
+// host checks the indices before it uploads them, this is a second guard).
+__global__ __launch_bounds__(256) void feature_cache_store_kernel(const float* __restrict__ pooled_raw,
+                                                                  const float* __restrict__ sumw, const int* __restrict__ rows,
+                                                                  float* __restrict__ cache_pooled, float* __restrict__ cache_sumw,
+                                                                  int E, int n_rows) {
+  const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+  const int r = rows[b];
+  if (r < 0 || r >= n_rows) return;
+  if (e < E) cache_pooled[(int64_t)r * E + e] = pooled_raw[(int64_t)b * E + e];
+  if (blockIdx.x == 0 && threadIdx.x == 0) cache_sumw[r] = sumw[b];
+}
+__global__ __launch_bounds__(256) void feature_cache_gather_kernel(const float* __restrict__ cache_pooled,
+                                                                   const float* __restrict__ cache_sumw, const int* __restrict__ rows,
+                                                                   float* __restrict__ pooled_raw, float* __restrict__ sumw, int E,
+                                                                   int n_rows) {
+  const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+  const int r = rows[b];
+  if (r < 0 || r >= n_rows) return;
+  if (e < E) pooled_raw[(int64_t)b * E + e] = cache_pooled[(int64_t)r * E + e];
+  if (blockIdx.x == 0 && threadIdx.x == 0) sumw[b] = cache_sumw[r];
+}
+
 // ---------------------------------------------------------------- forward 3: ridge GEMV + loss partials
 // block = 4 waves x RIDGE_ROWS/4 rows of W; z (bf16 [<=BMAX, E]) is staged once per block into LDS and
 // re-read from there for every row (the W stream, 16-byte lanes, is the only HBM traffic).
@@ -622,6 +648,86 @@ int launch_pool(const bf16* hidden, const float* wmask, float* partial, float* s
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
+
+// LN1 affine + LN2 + dropout -> z, ridge GEMV, loss: everything of the forward that reads only (pooled_raw, sumw).
+// vlb_head_fwd and vlb_head_fwd_cached both end here, so the two give the same bits for the same (pooled_raw, sumw).
+int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w, const void* ln1_b, const void* ln2_w,
+                  const void* ln2_b, const void* ridge_w, const void* ridge_b, const float* y, const float* keep_scale,
+                  float* lpart, float* zhat, float* ln2_rstd, void* z, float* pred, float* loss_terms, int B, int E, int V,
+                  float eps, float l2_lambda, hipStream_t st) {
+  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
+                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
+  VLB_LAUNCH_CHECK();
+  int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+  if (B <= 16 && E % 128 == 0 && E <= 4096) {
+    const int ntiles = (V + 15) / 16;
+    rblk = ntiles < 2048 ? ntiles : 2048;          // persistent over row tiles; lpart has room for V/16 >= rblk entries
+    switch (E / 128) {
+#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL(ridge_fwd_mfma_kernel<KS>, dim3(rblk), dim3(256), 0, st, (const bf16*)ridge_w, \
+                                                       (const bf16*)ridge_b, (const bf16*)z, y, pred, lpart, B, E, V); break;
+      VLB_RIDGE_CASE(1) VLB_RIDGE_CASE(2) VLB_RIDGE_CASE(3) VLB_RIDGE_CASE(4) VLB_RIDGE_CASE(5) VLB_RIDGE_CASE(6) VLB_RIDGE_CASE(7)
+      VLB_RIDGE_CASE(8) VLB_RIDGE_CASE(9) VLB_RIDGE_CASE(10) VLB_RIDGE_CASE(11) VLB_RIDGE_CASE(12) VLB_RIDGE_CASE(13)
+      VLB_RIDGE_CASE(14) VLB_RIDGE_CASE(15) VLB_RIDGE_CASE(16) VLB_RIDGE_CASE(17) VLB_RIDGE_CASE(18) VLB_RIDGE_CASE(19)
+      VLB_RIDGE_CASE(20) VLB_RIDGE_CASE(21) VLB_RIDGE_CASE(22) VLB_RIDGE_CASE(23) VLB_RIDGE_CASE(24) VLB_RIDGE_CASE(25)
+      VLB_RIDGE_CASE(26) VLB_RIDGE_CASE(27) VLB_RIDGE_CASE(28) VLB_RIDGE_CASE(29) VLB_RIDGE_CASE(30) VLB_RIDGE_CASE(31)
+      VLB_RIDGE_CASE(32)
+#undef VLB_RIDGE_CASE
+    }
+  } else {
+    const int zlds = (B < BMAX ? B : BMAX) * E * 2;
+    if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
+    hipLaunchKernelGGL(ridge_fwd_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b,
+                       (const bf16*)z, y, pred, lpart, B, E, V);
+  }
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, rblk, 1.f / ((float)B * (float)V),
+                     l2_lambda, loss_terms);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// Ridge, dropout, LN2 and LN1-affine gradients (dpooled_ws = d loss / d pooled_raw is left for head_dhidden_kernel):
+// vlb_head_bwd and vlb_head_bwd_cached both run this, so their parameter gradients are the same bits.
+int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
+                    const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd, const void* z,
+                    const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
+                    float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, float l2_lambda,
+                    float loss_scale, float l2_scale, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const float gscale = loss_scale * 2.f / ((float)B * (float)V);
+  const int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+  const int zlds = (B < BMAX ? B : BMAX) * E * 2;
+  if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
+  hipLaunchKernelGGL(ridge_bwd_w_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
+                     d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda);
+  VLB_LAUNCH_CHECK();
+  if (B <= 16 && E % 8 == 0) {
+    // dz[b,e] = sum_v dpred[b,v] W[v,e]: contraction over the ROWS of W -> the MFMA skinny-wgrad kernel
+    // (G = dpred^T [V,16] bf16, X = W).  Result rows b < B of a [16,E] fp32 block land in dz_part[0].
+    const int splits = vlb_wgrad_splits(V);
+    float* wg_ws = ws;                                             // [splits][16][E]
+    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
+    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [V][16] bf16
+    hipLaunchKernelGGL(dpred_t_kernel, dim3((unsigned)(((int64_t)V * 16 + 255) / 256)), dim3(256), 0, st, pred, y, dpT, B, V, gscale);
+    VLB_LAUNCH_CHECK();
+    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, V, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
+    if (rc3 != VLB_OK) return rc3;
+    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
+    VLB_LAUNCH_CHECK();
+  } else {
+    hipLaunchKernelGGL(ridge_bwd_z_kernel, dim3((E + 511) / 512, DZ_SPLIT), dim3(256), 0, st, (const bf16*)ridge_w, pred,
+                       y, ws, B, E, V, gscale);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
+    VLB_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(head_ln2_bwd_kernel, dim3(B), dim3(1024), 0, st, dz_ws, (const bf16*)ln2_w, zhat, ln2_rstd, dpooled_ws, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_param_grads_kernel, dim3((E + 255) / 256), dim3(256), 0, st, dz_ws, dpooled_ws, (const bf16*)ln1_w,
+                     pooled_raw, sumw, zhat, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, B, E);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
 }  // namespace
 
 extern "C" int vlb_head_partial_rows(int S) { return (S + POOL_ROWS - 1) / POOL_ROWS; }
@@ -657,35 +763,8 @@ extern "C" int vlb_head_fwd(const void* hidden, const float* wmask, const void* 
   if (rc != VLB_OK) return rc;
   hipLaunchKernelGGL(head_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, partial, nblk, pooled_raw, sumw, E);
   VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
-                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
-  VLB_LAUNCH_CHECK();
-  int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-  if (B <= 16 && E % 128 == 0 && E <= 4096) {
-    const int ntiles = (V + 15) / 16;
-    rblk = ntiles < 2048 ? ntiles : 2048;          // persistent over row tiles; lpart has room for V/16 >= rblk entries
-    switch (E / 128) {
-#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL(ridge_fwd_mfma_kernel<KS>, dim3(rblk), dim3(256), 0, st, (const bf16*)ridge_w, \
-                                                       (const bf16*)ridge_b, (const bf16*)z, y, pred, lpart, B, E, V); break;
-      VLB_RIDGE_CASE(1) VLB_RIDGE_CASE(2) VLB_RIDGE_CASE(3) VLB_RIDGE_CASE(4) VLB_RIDGE_CASE(5) VLB_RIDGE_CASE(6) VLB_RIDGE_CASE(7)
-      VLB_RIDGE_CASE(8) VLB_RIDGE_CASE(9) VLB_RIDGE_CASE(10) VLB_RIDGE_CASE(11) VLB_RIDGE_CASE(12) VLB_RIDGE_CASE(13)
-      VLB_RIDGE_CASE(14) VLB_RIDGE_CASE(15) VLB_RIDGE_CASE(16) VLB_RIDGE_CASE(17) VLB_RIDGE_CASE(18) VLB_RIDGE_CASE(19)
-      VLB_RIDGE_CASE(20) VLB_RIDGE_CASE(21) VLB_RIDGE_CASE(22) VLB_RIDGE_CASE(23) VLB_RIDGE_CASE(24) VLB_RIDGE_CASE(25)
-      VLB_RIDGE_CASE(26) VLB_RIDGE_CASE(27) VLB_RIDGE_CASE(28) VLB_RIDGE_CASE(29) VLB_RIDGE_CASE(30) VLB_RIDGE_CASE(31)
-      VLB_RIDGE_CASE(32)
-#undef VLB_RIDGE_CASE
-    }
-  } else {
-    const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-    if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
-    hipLaunchKernelGGL(ridge_fwd_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b,
-                       (const bf16*)z, y, pred, lpart, B, E, V);
-  }
-  VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, rblk, 1.f / ((float)B * (float)V),
-                     l2_lambda, loss_terms);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, lpart, zhat, ln2_rstd,
+                       z, pred, loss_terms, B, E, V, eps, l2_lambda, st);
 }
 
 extern "C" int vlb_head_bwd(const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w,
@@ -700,39 +779,11 @@ extern "C" int vlb_head_bwd(const void* hidden, const float* wmask, const void* 
                   pred && d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
               "head_bwd: null argument");
   VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd: bad shape");
+  if (int rc = head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
+                               d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale,
+                               l2_scale, stream))
+    return rc;
   hipStream_t st = as_stream(stream);
-  const float gscale = loss_scale * 2.f / ((float)B * (float)V);
-  const int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-  const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-  if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
-  hipLaunchKernelGGL(ridge_bwd_w_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
-                     d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda);
-  VLB_LAUNCH_CHECK();
-  if (B <= 16 && E % 8 == 0) {
-    // dz[b,e] = sum_v dpred[b,v] W[v,e]: contraction over the ROWS of W -> the MFMA skinny-wgrad kernel
-    // (G = dpred^T [V,16] bf16, X = W).  Result rows b < B of a [16,E] fp32 block land in dz_part[0].
-    const int splits = vlb_wgrad_splits(V);
-    float* wg_ws = ws;                                             // [splits][16][E]
-    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
-    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [V][16] bf16
-    hipLaunchKernelGGL(dpred_t_kernel, dim3((unsigned)(((int64_t)V * 16 + 255) / 256)), dim3(256), 0, st, pred, y, dpT, B, V, gscale);
-    VLB_LAUNCH_CHECK();
-    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, V, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
-    if (rc3 != VLB_OK) return rc3;
-    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
-    VLB_LAUNCH_CHECK();
-  } else {
-    hipLaunchKernelGGL(ridge_bwd_z_kernel, dim3((E + 511) / 512, DZ_SPLIT), dim3(256), 0, st, (const bf16*)ridge_w, pred,
-                       y, ws, B, E, V, gscale);
-    VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
-    VLB_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(head_ln2_bwd_kernel, dim3(B), dim3(1024), 0, st, dz_ws, (const bf16*)ln2_w, zhat, ln2_rstd, dpooled_ws, E);
-  VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_param_grads_kernel, dim3((E + 255) / 256), dim3(256), 0, st, dz_ws, dpooled_ws, (const bf16*)ln1_w,
-                     pooled_raw, sumw, zhat, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, B, E);
-  VLB_LAUNCH_CHECK();
   if (dhidden) {
     const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
     VLB_REQUIRE(rows > 0 && rows <= (int64_t)B * S, "head_bwd: total_rows=%d out of range", total_rows);
@@ -741,6 +792,50 @@ extern "C" int vlb_head_bwd(const void* hidden, const float* wmask, const void* 
     VLB_LAUNCH_CHECK();
   }
   return VLB_OK;
+}
+
+// ---------------------------------------------------------------- frozen-backbone feature cache
+extern "C" int vlb_feature_cache_store(const float* pooled_raw, const float* sumw, const int* rows, float* cache_pooled,
+                                       float* cache_sumw, int B, int E, int n_rows, void* stream) {
+  VLB_REQUIRE(pooled_raw && sumw && rows && cache_pooled && cache_sumw, "feature_cache_store: null argument");
+  VLB_REQUIRE(B > 0 && E > 0 && n_rows > 0, "feature_cache_store: bad shape B=%d E=%d n_rows=%d", B, E, n_rows);
+  hipLaunchKernelGGL(feature_cache_store_kernel, dim3((E + 255) / 256, B), dim3(256), 0, as_stream(stream), pooled_raw, sumw,
+                     rows, cache_pooled, cache_sumw, E, n_rows);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_fwd_cached(const float* cache_pooled, const float* cache_sumw, const int* rows, const void* ln1_w,
+                                   const void* ln1_b, const void* ln2_w, const void* ln2_b, const void* ridge_w,
+                                   const void* ridge_b, const float* y, const float* keep_scale, float* ws, float* pooled_raw,
+                                   float* sumw, float* zhat, float* ln2_rstd, void* z, float* pred, float* loss_terms, int B,
+                                   int E, int V, int n_rows, float eps, float l2_lambda, void* stream) {
+  VLB_REQUIRE(cache_pooled && cache_sumw && rows && ln1_w && ln1_b && ln2_w && ln2_b && ridge_w && ridge_b && y && ws &&
+                  pooled_raw && sumw && zhat && ln2_rstd && z && pred && loss_terms, "head_fwd_cached: null argument");
+  VLB_REQUIRE(B > 0 && V > 0 && n_rows > 0 && E % 8 == 0 && E > 0 && E <= 8192,
+              "head_fwd_cached: bad shape B=%d E=%d V=%d n_rows=%d", B, E, V, n_rows);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
+                     pooled_raw, sumw, E, n_rows);
+  VLB_LAUNCH_CHECK();
+  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, ws, zhat, ln2_rstd, z,
+                       pred, loss_terms, B, E, V, eps, l2_lambda, st);
+}
+
+extern "C" int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
+                                   const float* keep_scale, const float* pooled_raw, const float* sumw, const float* zhat,
+                                   const float* ln2_rstd, const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b,
+                                   float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws,
+                                   float* dpooled_ws, int B, int E, int V, float eps, float l2_lambda, float loss_scale,
+                                   float l2_scale, void* stream) {
+  (void)eps;
+  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w && d_ridge_b &&
+                  d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
+              "head_bwd_cached: null argument");
+  VLB_REQUIRE(B > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_cached: bad shape");
+  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
+                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
+                         stream);
 }
 
 // ---------------------------------------------------------------- the exported layers on their own

@@ -104,7 +104,13 @@ class _SyntheticFile:
 
 
 class VLB_Dataset(Dataset):
+    """``with_index`` adds the dataset index (``"index"``, int64) to every item; ``features_only`` makes an item
+    ``{"index", "timeseries"}`` and reads nothing else from the file (a split whose frozen-backbone features are all
+    cached, feature_cache.py).  Both are off by default and may be switched between epochs."""
+
     def __init__(self, ds_paths, geometry="7b", num_target=1000):
+        self.ds_paths, self.geometry, self.num_target = list(ds_paths), geometry, num_target
+        self.with_index = self.features_only = False
         self.ds_files, self.length, self.ranges = {}, 0, []
         for i, p in enumerate(ds_paths):
             if isinstance(p, tuple):
@@ -124,8 +130,13 @@ class VLB_Dataset(Dataset):
         i = get_idx(self.ranges, idx)
         f = self.ds_files[i]["ds_file"]
         k = idx - self.ds_files[i]["idx_from"]
+        if self.features_only:
+            return {"index": torch.tensor(int(idx), dtype=torch.int64),
+                    "timeseries": torch.from_numpy(np.asarray(f.get(k, "timeseries"))).float()}
         item = {m: torch.from_numpy(np.asarray(f.get(k, m))).float() for m in MODS_T}
         item.update({m: np.asarray(f.get(k, m)) for m in MODS_N})
+        if self.with_index:
+            item["index"] = torch.tensor(int(idx), dtype=torch.int64)
         return item
 
 

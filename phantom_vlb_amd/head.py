@@ -108,3 +108,42 @@ class BrainHead:
                                float(loss_scale), float(l2_scale), None if cu is None else cu.data_ptr(), rows,
                                _stream()), "vlb_head_bwd")
         return dh
+
+    # ------------------------------------------------------------------ frozen-backbone feature cache (feature_cache.py)
+    def forward_cached(self, cache, indices, y, keep_scale=None):
+        """The head forward of a batch whose (pooled_raw, sumw) sit in ``cache`` rows ``indices`` (host int64 [B]):
+        -> (pred f32 [B,V], loss_terms f32[3]), the same bits vlb_head_fwd gives for the same (pooled_raw, sumw)."""
+        B = y.shape[0]
+        rows = cache.rows(indices)
+        if rows.numel() != B:
+            raise ValueError(f"head: {rows.numel()} cache rows for a batch of {B}")
+        if self._cap is None or self._cap[0] != B:
+            self._buffers(B, 1)           # no pooling workspace needed; buffers of an uncached step of this B serve as they are
+        self._saved_cached = (y, keep_scale)
+        c = self.compute
+        check(lib.vlb_head_fwd_cached(cache.pooled.data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
+                                      c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
+                                      c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
+                                      c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
+                                      y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
+                                      self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
+                                      self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
+                                      self.loss_terms.data_ptr(), B, self.E, self.V, cache.n, self.eps, self.l2_lambda,
+                                      _stream()), "vlb_head_fwd_cached")
+        return self.pred, self.loss_terms
+
+    def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
+        """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""
+        y, keep_scale = self._saved_cached
+        B = y.shape[0]
+        c, gr = self.compute, self.grads
+        check(lib.vlb_head_bwd_cached(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                                      c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(),
+                                      None if keep_scale is None else keep_scale.data_ptr(), self.pooled_raw.data_ptr(),
+                                      self.sumw.data_ptr(), self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(),
+                                      self.pred.data_ptr(), gr["ridge_layer.linear.weight"].data_ptr(),
+                                      gr["ridge_layer.linear.bias"].data_ptr(), gr["layer_norm2.weight"].data_ptr(),
+                                      gr["layer_norm2.bias"].data_ptr(), gr["layer_norm1.weight"].data_ptr(),
+                                      gr["layer_norm1.bias"].data_ptr(), self.ws.data_ptr(), self.dz.data_ptr(),
+                                      self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self.l2_lambda, float(loss_scale),
+                                      float(l2_scale), _stream()), "vlb_head_bwd_cached")

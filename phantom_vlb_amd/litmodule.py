@@ -147,10 +147,15 @@ class VLBLitModuleConfig:
     gradient_clip_val: float = 1.0  # the Trainer's gradient_clip_val, applied inside the fused AdamW
     pack_tokens: bool = True        # drop each clip's padded tail rows (flash-attn varlen equivalent)
     fp8_gemm: bool = False          # full fine-tune only: decoder forward / dgrad GEMMs on the MX-fp8 MFMA path (configs[4])
+    cache_features: bool = False    # frozen backbone only: keep each clip's pooled features, later epochs run the head alone
+    feature_cache_dir: str | None = None    # persist the feature caches there (feature_cache.py; loaded on a matching fingerprint)
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
         self.device_map = "auto"         # reference :157 (degenerate on one device)
+        if self.cache_features and (self.use_lora or not self.freeze_backbone):
+            raise ValueError("cache_features=True needs a frozen backbone without LoRA (freeze_backbone=True, use_lora=False): "
+                             "with LoRA or a full fine-tune the backbone's output changes every step")
 
 
 def resolve_geometry(cfg: VLBLitModuleConfig) -> Geometry:
@@ -341,6 +346,23 @@ class VLBLitModule(_Base):
     def _common_step(self, batch, train: bool):
         cfg, g = self.config, self.geometry
         dev = self.device
+        self._cached_step = False
+        cache = self.feature_caches.get("train" if train else "val") if cfg.cache_features and "index" in batch else None
+        if cache is not None and cache.lookup(batch["index"]):
+            # every clip's features are cached: no backbone, no weight mask; the same head kernels on the same fp32 inputs
+            y = batch["timeseries"].to(dev, torch.float32).to(torch.bfloat16).float().contiguous()
+            keep = None
+            if train and cfg.dropout_rate > 0:
+                keep = ops.dropout_keep_scale(y.shape[0], g.dim, cfg.dropout_rate, self._dropout_seed(), dev)
+            if torch.is_tensor(batch.get("vision")):
+                self.discard_prefetched_vision(batch)       # its frozen vision side is not needed
+            pred, terms = self.head.forward_cached(cache, batch["index"], y, keep)
+            self._loss_terms = terms
+            self._cached_step = True
+            return pred, y, terms
+        if cache is not None and "vision" not in batch:
+            raise RuntimeError(f"feature cache {cache.split!r}: a features-only batch missed the cache (indices "
+                               f"{batch['index'].tolist()})")
         # unpadded (packed) rows, like the reference's flash-attn path; needs the ids on the host (no sync)
         layout = self.backbone.row_layout(batch["language"], batch["padvals"]) if self.pack_tokens else None
         x_lang = batch["language"].to(dev).long()
@@ -352,7 +374,77 @@ class VLBLitModule(_Base):
             keep = ops.dropout_keep_scale(x_lang.shape[0], g.dim, cfg.dropout_rate, self._dropout_seed(), dev)
         ids_host = batch["language"] if batch["language"].device.type == "cpu" else None
         pred, _ = self.forward(batch["vision"], x_lang, wm, y=y, keep_scale=keep, layout=layout, ids_host=ids_host)
+        if cache is not None and cache.store(batch["index"], self.head) and cache.complete() and cfg.feature_cache_dir:
+            cache.save(cfg.feature_cache_dir, self._feature_cache_fp[cache.split])
         return pred, y, self._loss_terms
+
+    # ------------------------------------------------------------------ frozen-backbone feature cache (feature_cache.py)
+    @property
+    def feature_caches(self) -> dict:
+        return self.__dict__.setdefault("_feature_caches", {})
+
+    def setup_feature_cache(self, train_dataset=None, val_dataset=None) -> None:
+        """One FeatureCache per split, sized by its dataset; with ``feature_cache_dir`` each is filled from disk when the
+        fingerprint there matches.  The datasets start handing out ``"index"``.  Called once per fit, after configure_model."""
+        from .feature_cache import FeatureCache, fingerprint
+        cfg = self.config
+        if not cfg.cache_features:
+            return
+        fps = self.__dict__.setdefault("_feature_cache_fp", {})
+        for split, ds in (("train", train_dataset), ("val", val_dataset)):
+            if ds is None:
+                continue
+            ds.with_index = True
+            c = self.feature_caches.get(split)
+            if c is None or c.n != len(ds):
+                c = self.feature_caches[split] = FeatureCache(split, len(ds), self.geometry.dim, self.device)
+            fps[split] = fingerprint(cfg, ds)
+            if cfg.feature_cache_dir and not c.complete():
+                c.load(cfg.feature_cache_dir, fps[split])
+
+    def feature_cache_begin(self, split: str, dataset=None) -> None:
+        """Start of a training epoch / validation pass: a split whose cache is complete stops loading anything but the
+        targets (``features_only``; the loader's iterator - and its workers - are re-created per epoch and per pass)."""
+        c = self.feature_caches.get(split)
+        if c is None:
+            return
+        c.reset_counters()
+        if dataset is not None:
+            dataset.features_only = c.complete()
+
+    def feature_cache_end(self, split: str) -> float | None:
+        """End of a training epoch / validation pass: ``feature_cache/<split>_hit_rate`` (fraction of batches run from the
+        cache) through ``log``."""
+        c = self.feature_caches.get(split)
+        rate = None if c is None else c.hit_rate()
+        if rate is not None:
+            self.log(f"feature_cache/{split}_hit_rate", rate)
+        return rate
+
+    def _datamodule_dataset(self, split):
+        dm = getattr(getattr(self, "trainer", None), "datamodule", None)
+        return getattr(getattr(dm, "datasets", None), split, None)
+
+    def on_train_epoch_start(self):
+        """Lightning hook (the built-in runner calls feature_cache_begin itself)."""
+        if self.config.cache_features:
+            if not self.feature_caches:
+                self.setup_feature_cache(self._datamodule_dataset("train"), self._datamodule_dataset("val"))
+            self.feature_cache_begin("train", self._datamodule_dataset("train"))
+
+    def on_train_epoch_end(self):
+        if self.config.cache_features:
+            self.feature_cache_end("train")
+
+    def on_validation_epoch_start(self):
+        if self.config.cache_features:
+            if not self.feature_caches:
+                self.setup_feature_cache(self._datamodule_dataset("train"), self._datamodule_dataset("val"))
+            self.feature_cache_begin("val", self._datamodule_dataset("val"))
+
+    def on_validation_epoch_end(self):
+        if self.config.cache_features:
+            self.feature_cache_end("val")
 
     def prefetch_vision(self, batch, ready_event=None):
         """Start the frozen vision side (CLIP tower + STC connector) of a FUTURE batch on a side stream, so that it runs under
@@ -382,7 +474,11 @@ class VLBLitModule(_Base):
         self.backbone.launch_deferred_video_tokens()         # a future batch's frozen vision side: behind this forward, under this backward
         need_dh = self.lora is not None or self.full is not None
         inv_world = 1.0 / self.world_size
-        dh = self.head.backward(need_dhidden=need_dh, loss_scale=inv_world, l2_scale=inv_world)
+        if self._cached_step:
+            self.head.backward_cached(loss_scale=inv_world, l2_scale=inv_world)
+            dh = None
+        else:
+            dh = self.head.backward(need_dhidden=need_dh, loss_scale=inv_world, l2_scale=inv_world)
         if self.lora is not None:
             self.lora.backward(self.backbone, dh)
         elif self.full is not None:
@@ -416,8 +512,8 @@ class VLBLitModule(_Base):
 
     def transfer_batch_to_device(self, batch, device, dataloader_idx=0):
         """Pixels / targets / weights go to the GPU; the token ids and ``padvals`` (20 KB) stay on the host so the step can size
-        its unpadded row layout without a device sync (the step uploads them itself)."""
-        keep = ("language", "padvals")
+        its unpadded row layout without a device sync (the step uploads them itself); so does a feature-cache ``index``."""
+        keep = ("language", "padvals", "index")
         return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) and k not in keep else v) for k, v in batch.items()}
 
     def on_fit_start(self):

@@ -185,6 +185,7 @@ class Trainer:
         self.callbacks = list(callbacks or [])
         self.limit_val_batches = limit_val_batches
         self.global_step, self.current_epoch = 0, 0
+        self._feature_cache = False
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
         want = devices if isinstance(devices, int) else (len(devices) if isinstance(devices, (list, tuple)) else 1)
@@ -211,6 +212,8 @@ class Trainer:
         once at the end; with sharded frozen weights (per-layer all-gathers in every forward) all ranks keep
         running every batch so their collective sequences stay aligned."""
         self._cb("on_validation_epoch_start", model)
+        if self._feature_cache:
+            model.feature_cache_begin("val", getattr(loader, "loader", loader).dataset)
         tot, n = None, 0                     # summed on the device: one host sync per validation epoch, not per batch
         strided = self.world > 1 and getattr(model.backbone, "store", None) is None
         mine = (lambda bi: bi % self.world == self.rank) if strided else None
@@ -232,6 +235,8 @@ class Trainer:
                     c.all_reduce_sums(model)         # every rank takes part, also one that drew no batch
         self._cb("on_validation_epoch_end", model)
         metrics = {"val/brain_loss": (float(tot) if tot is not None else 0.0) / max(n, 1)}
+        if self._feature_cache and (rate := model.feature_cache_end("val")) is not None:
+            metrics["feature_cache/val_hit_rate"] = rate
         metrics.update({k: float(v) for k, v in getattr(model, "logged", {}).items() if k.startswith("val_corr_avg")})
         for c in self.callbacks:
             if hasattr(c, "on_validation_end") and isinstance(c, TrainableCheckpoint):
@@ -240,6 +245,12 @@ class Trainer:
         return metrics
 
     def fit(self, model, datamodule=None, ckpt_path=None):
+        # frozen-backbone feature cache (feature_cache.py): one process only - with sharded frozen weights a rank that skipped
+        # its forward would leave the others waiting in their per-layer all-gathers
+        self._feature_cache = bool(getattr(getattr(model, "config", None), "cache_features", False))
+        if self._feature_cache and self.world > 1:
+            raise ValueError(f"cache_features=True with WORLD_SIZE={self.world}: the feature cache is single-process only "
+                             "(data-parallel caching is not supported); run one process or set cache_features=False")
         self.model = model
         model.trainer = self
         model.configure_model()
@@ -258,13 +269,17 @@ class Trainer:
         except TypeError:
             train_loader = datamodule.train_dataloader()
         val_loader = datamodule.val_dataloader()
+        keep_on_host = ("language", "padvals")
+        if self._feature_cache:
+            model.setup_feature_cache(train_loader.dataset, val_loader.dataset)
+            keep_on_host += ("index",)        # the cache decides hit / miss on the host
         if torch.cuda.is_available():        # overlap the next batch's host->device copy with the current step
             from .datamodule import DevicePrefetcher
             # ... and start the frozen vision side of batch i+1 on a side stream under step i (VLBLitModule.prefetch_vision)
             hook = getattr(model, "prefetch_vision", None)
             drop = getattr(model, "discard_prefetched_vision", None)
-            train_loader = DevicePrefetcher(train_loader, model.device, on_staged=hook, on_discard=drop)
-            val_loader = DevicePrefetcher(val_loader, model.device, on_staged=hook, on_discard=drop)
+            train_loader = DevicePrefetcher(train_loader, model.device, keep_on_host, on_staged=hook, on_discard=drop)
+            val_loader = DevicePrefetcher(val_loader, model.device, keep_on_host, on_staged=hook, on_discard=drop)
         n_batches = len(train_loader)
         val_every = max(1, int(n_batches * self.val_check_interval)) if self.val_check_interval <= 1 else int(self.val_check_interval)
         t0 = time.time()
@@ -274,6 +289,8 @@ class Trainer:
             if hasattr(train_loader.sampler, "set_epoch"):
                 train_loader.sampler.set_epoch(epoch)
             self._cb("on_train_epoch_start", model)
+            if self._feature_cache:
+                model.feature_cache_begin("train", getattr(train_loader, "loader", train_loader).dataset)
             seen = (lambda bi: bi >= skip) if epoch == start_epoch and skip else None     # resumed mid-epoch: the batches
             batches = _iter_selected(train_loader, seen, None)                            # before the checkpoint are not staged
             try:
@@ -292,6 +309,8 @@ class Trainer:
                         return
             finally:
                 batches.close()              # a batch staged ahead but never consumed is dropped (DevicePrefetcher.on_discard)
+            if self._feature_cache and (rate := model.feature_cache_end("train")) is not None:
+                self._log({"feature_cache/train_hit_rate": rate, "epoch": epoch})
         return
 
     def save_checkpoint(self, filepath, weights_only: bool = False):
