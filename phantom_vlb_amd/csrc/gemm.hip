@@ -1,15 +1,15 @@
 // bf16 MFMA GEMMs for gfx950:  C[M,N] = act(A[M,K].W[N,K]^T + A2.W2^T + bias) + residual
 //
-// Two kernels:
-//  * gemm_tile_kernel<BM,BN,WM,WN>: 512 threads (8 waves), BK=64, LDS-DMA staging
+// Kernels:
+//  * gemm_pp_kernel<BM,BN,WM,WN,..>: 512 threads (8 waves in two ping-pong groups), BK=64, LDS-DMA staging
 //    (global_load_lds_dwordx4, swizzle applied on the SOURCE address), double-buffered LDS,
 //    v_mfma_f32_16x16x32_bf16, XCD-aware tile order.  Needs N % BN == 0, K % 64 == 0; any M.
+//  * gemm_w4_kernel<..>: the same tiles with 4 waves of 128x128 (or 96x128 / 128x64) blocks, for long K.
 //  * gemm_generic_kernel: 64x64 tile, bounds-checked register staging, any M/N, K % 8 == 0.
 //
 // MFMA operand roles are swapped on purpose (rows of the MFMA = output COLUMNS n, columns of the
 // MFMA = output rows m): each lane then owns 4 consecutive n of one row m per 16x16 tile, so the
 // epilogue packs 4 bf16 into one 8-byte store and bias/residual are 8-byte loads.
-#include <atomic>
 #include <type_traits>
 
 #include "common.hpp"
@@ -41,11 +41,8 @@ struct GemmArgs {
   // SWIGLU_PAIR only: when set, the pre-activations are ALSO stored, de-interleaved, as [gate | up] rows of N columns
   // (what a LoRA / full backward needs) - vlb_gemm_swiglu_save
   bf16* aux; int ldaux;
-  int stagger;              // tools build only (timing experiment): odd workgroups of the first round start this many 10-ns ticks late
+  int reserved;             // unused; keeps `wide` at its offset, where the kernels' scalar loads of the arguments pair up as before
   int wide;                 // C (and aux) rows 16-byte aligned: required by the four-wave kernels, which store 16 bytes per lane (store_pair16)
-  int persist_iters;        // tools build only (persistent experiment): output tiles per workgroup, grid = 256
-  // stream-K launch (gemm_w4_kernel<.., STREAMK>): 256 workgroups share sk_total = tiles x K-tiles iterations evenly; see the kernel
-  int sk_total; unsigned long long* sk_flags; unsigned long long sk_want; int* sk_err;
 };
 
 // blockIdx -> (m0, n0).  The order is defined on the full parent grid, so a GEMM can be cut into several launches (full
@@ -217,136 +214,8 @@ __device__ __forceinline__ void glds16(const void* g, void* l) {
                                    (void __attribute__((address_space(3)))*)l, 16, 0, 0);
 }
 
-template <int BM, int BN, int WM, int WN>
-__global__ __launch_bounds__(512, 2) void gemm_tile_kernel(GemmArgs p) {
-  static_assert(WM * WN == 8, "8 waves");
-  constexpr int TM = BM / WM, TN = BN / WN;   // per-wave output tile
-  constexpr int MT = TM / 16, NT = TN / 16;   // 16x16 MFMA tiles per wave
-  constexpr int A_BYTES = BM * ROW_BYTES, B_BYTES = BN * ROW_BYTES;
-  constexpr int STAGE = A_BYTES + B_BYTES;
-  constexpr int A_LD = BM / 64, B_LD = BN / 64;  // glds instructions per thread per tile
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-
-  int m0, n0;
-  map_tile(p, BM, BN, m0, n0);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-
-  // ---- staging addresses: instruction i of this wave fills LDS rows [i*64 + wave*8, +8)
-  const int srow = (lane >> 3), sslot = lane & 7;
-  const bf16* a_src[A_LD]; const bf16* b_src[B_LD];
-  const bf16* a2_src[A_LD]; const bf16* b2_src[B_LD];
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) {
-    const int r = i * 64 + wave * 8 + srow;
-    const int c = sslot ^ ((r >> 1) & 7);
-    const int gm = min(m0 + r, p.M - 1);
-    a_src[i] = p.A + (int64_t)gm * p.lda + c * 8;
-    a2_src[i] = p.A2 ? p.A2 + (int64_t)gm * p.lda2 + c * 8 : nullptr;
-  }
-#pragma unroll
-  for (int i = 0; i < B_LD; ++i) {
-    const int r = i * 64 + wave * 8 + srow;
-    const int c = sslot ^ ((r >> 1) & 7);
-    b_src[i] = p.W + (int64_t)(n0 + r) * p.ldw + c * 8;
-    b2_src[i] = p.W2 ? p.W2 + (int64_t)(n0 + r) * p.ldw2 + c * 8 : nullptr;
-  }
-  const int nk1 = p.K / BK;
-  const int nk = nk1 + p.K2 / BK;
-
-  auto stage = [&](int buf, int kt) {
-    char* base = smem + buf * STAGE + wave * 8 * ROW_BYTES;
-    if (kt < nk1) {
-      const int ko = kt * BK;
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) glds16(a_src[i] + ko, base + i * 64 * ROW_BYTES);
-#pragma unroll
-      for (int i = 0; i < B_LD; ++i) glds16(b_src[i] + ko, base + A_BYTES + i * 64 * ROW_BYTES);
-    } else {
-      const int ko = (kt - nk1) * BK;
-#pragma unroll
-      for (int i = 0; i < A_LD; ++i) glds16(a2_src[i] + ko, base + i * 64 * ROW_BYTES);
-#pragma unroll
-      for (int i = 0; i < B_LD; ++i) glds16(b2_src[i] + ko, base + A_BYTES + i * 64 * ROW_BYTES);
-    }
-  };
-
-  f32x4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fragment read offsets (within a stage): row = tile_row0 + (lane&15), chunk = ks*4 + (lane>>4)
-  const int fr = lane & 15, fq = lane >> 4;
-  int a_off[MT][2], b_off[NT][2];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) a_off[i][ks] = lds_off(wm * TM + i * 16 + fr, ks * 4 + fq);
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) b_off[j][ks] = A_BYTES + lds_off(wn * TN + j * 16 + fr, ks * 4 + fq);
-
-  stage(0, 0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
-    const char* sb = smem + cur * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 af[MT], wf[NT];
-#pragma unroll
-      for (int j = 0; j < NT; ++j) wf[j] = *reinterpret_cast<const bf16x8*>(sb + b_off[j][ks]);
-#pragma unroll
-      for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const bf16x8*>(sb + a_off[i][ks]);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j], af[i], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // ---- epilogue: lane owns n = nbase + fq*4 + {0..3} of row m = mbase + fr, per 16x16 tile
-  // C rows 16-byte aligned (p.wide): adjacent fragments paired into 16-byte stores (store_pair16); one nest per activation
-#define PP_EPILOGUE_WIDE(ACT)                                                                                            \
-  _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                       \
-    const int m = m0 + wm * TM + i * 16 + fr;                                                                            \
-    if (m >= p.M) continue;                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < NT; j += 2) {                                                                  \
-      const int n = n0 + wn * TN + j * 16 + fq * 4;                                                                      \
-      store_pair16(p.C + (int64_t)m * p.ldc, n, w4_frag_value<ACT>(p, acc[i][j], m, n), w4_frag_value<ACT>(p, acc[i][j + 1], m, n + 16), fq); \
-    }                                                                                                                    \
-  }
-#define PP_EPILOGUE_NARROW(ACT)                                                                                          \
-  _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                       \
-    const int m = m0 + wm * TM + i * 16 + fr;                                                                            \
-    if (m >= p.M) continue;                                                                                              \
-    _Pragma("unroll") for (int j = 0; j < NT; ++j) {                                                                     \
-      const int n = n0 + wn * TN + j * 16 + fq * 4;                                                                      \
-      *reinterpret_cast<bf16x4*>(p.C + (int64_t)m * p.ldc + n) = w4_frag_value<ACT>(p, acc[i][j], m, n);                 \
-    }                                                                                                                    \
-  }
-  if (p.wide) VLB_DISPATCH_ACT(p.act, PP_EPILOGUE_WIDE);
-  else VLB_DISPATCH_ACT(p.act, PP_EPILOGUE_NARROW);
-#undef PP_EPILOGUE_WIDE
-#undef PP_EPILOGUE_NARROW
-}
-
 // ------------------------------------------------------------------------------------------------
-// Ping-pong variant of the tile kernel.  The 8 waves form two groups of 4 (one wave of each group per
+// Ping-pong 8-wave tile kernel.  The 8 waves form two groups of 4 (one wave of each group per
 // SIMD).  Every K-tile is two phases (k-steps of 32); a phase is a LOAD segment (12 ds_read_b128 of
 // fragments, plus the LDS-DMA issue of the tile after next) and a COMPUTE segment (32 MFMAs), separated
 // by workgroup barriers.  Group 1 runs one barrier interval behind group 0, so on every SIMD one wave
@@ -710,25 +579,10 @@ __device__ __forceinline__ int w4_epilogue_kind(const GemmArgs& p) {
 // block 96 rows), picked by the host when they quantise the row count into fewer, fuller waves of tiles.
 // MASKED: the second operand pair (one K-tile, K2 = 64) runs FIRST, the accumulators are then multiplied by the
 // dropout keep mask / (1-p) in place, and the main K loop continues on top - dx = dy.W + keep*(u.A)/(1-p) in one GEMM.
-//
-// STREAMK (instantiated by the tools build only; measured 1.4-2x slower than the round + tail plans, see launch_w4_streamk):
-// ONE launch of 256 workgroups for an output of more than 256 tiles that is not a whole number of rounds.  The
-// launch's work is the sequence of (tile, K-tile) iterations in tile order, tiles x nk of them; workgroup r (= the r-th CU
-// slot of its XCD-contiguous run) takes iterations [bound(r), bound(r+1)) - the same number for everybody, so nobody idles
-// through a mostly empty last round and no second launch re-cuts it.  A range is at least one tile long (tiles >= 256), so a
-// tile is shared by at most two workgroups: the one that holds its FIRST K-tiles (at the END of its own range) owns it, the
-// next workgroup computes the rest of the tile at the START of its range, stores the raw fp32 accumulators as a slab
-// (layout of the split-K tail) and raises the tile's flag; the owner adds the slab to its own accumulators (fixed order:
-// bit-reproducible) and runs the epilogue.  Whole tiles inside a range end in the normal epilogue.  A contributor never
-// waits for anything, and an owner only for the first segment of the workgroup dispatched right after it in the same XCD
-// run, so the launch cannot deadlock however few CUs the dispatcher finds free; the owner's wait is bounded all the same
-// (sk_err is raised and the host fails the next call).  Cross-XCD visibility: slab and flag travel with agent-scope (sc1)
-// stores and loads - the instructions the gfx942 / gfx950 memory model uses for agent-scope atomics - ordered by vmcnt(0) +
-// a workgroup barrier on the writing side and by the flag load + barrier on the reading side; no cache-wide write-back or
-// invalidate (see the contributor branch).
+// ABL (timing-only ablations, tools build; results are WRONG when non-zero): bit0 skip the LDS-DMA of the loop, bit1 skip
+// its fragment reads, bit2 skip its barrier, bit3 skip its vmcnt(0) wait, bit4 / bit5 stage W / A from panel 0 (L2-resident).
 template <int NT = 8, int ABL = 0, int MT = 8, bool MASKED = false, bool SPLITK = false>
 __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
-  constexpr bool STREAMK = (ABL & 256) != 0;           // (an ABL bit, not a template parameter of its own: the product kernels keep their names)
   constexpr int TM = 16 * MT, TN = 16 * NT, BM = 2 * TM, BN = 2 * TN;
   constexpr int NG = MT * NT / 4;                      // groups of 4 MFMAs per block (one k-step of the wave block)
   constexpr int LAST_A = NG / 2 + 1;                   // group in which the double-slotted last A fragment is fetched
@@ -737,49 +591,13 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
   constexpr int A_LD = BM / 32, B_LD = BN / 32;       // LDS-DMA instructions per thread per tile (32 rows each)
   constexpr int ND = A_LD + B_LD;
   static_assert((NT == 8 || NT == 4) && (MT == 8 || MT == 6), "wave block 128|96 rows x 128|64 columns");
-  constexpr bool ROWSPLIT = (ABL & 64) != 0;            // the K loop that splits a K-tile's MFMAs by output rows instead of by k-step (below)
-  static_assert(ROWSPLIT || (ND <= 2 * NG && (NT - 1) < NG && (2 * (MT - 2) + 2) * NT / 8 < NG), "schedule does not fit the block");
+  static_assert(ND <= 2 * NG && (NT - 1) < NG && (2 * (MT - 2) + 2) * NT / 8 < NG, "schedule does not fit the block");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  constexpr bool PERSIST = (ABL & 128) != 0;             // tools: one workgroup per CU streams over persist_iters output tiles (below)
-  static_assert(!PERSIST || (!MASKED && !SPLITK && !ROWSPLIT), "persistent stream: plain launches only");
-  static_assert(!STREAMK || (NT == 8 && !SPLITK && !PERSIST && !ROWSPLIT), "stream-K: whole-width tiles, its own K ranges");
-  constexpr bool KRANGE = SPLITK || STREAMK;           // this workgroup walks a sub-range of a tile's K-tiles
-  constexpr int SK_MIN = 4;                             // no stream-K segment shorter than this many K-tiles
   int m0, n0;
-  int ksplit = 0;
   const int nk1 = MASKED ? p.K2 / BK : p.K / BK;       // K-tiles of the pair that runs first
   const int nk_all = p.K / BK + p.K2 / BK;
-  // stream-K: iteration range of this workgroup.  Boundaries closer than SK_MIN K-tiles to a tile boundary snap onto it
-  // (both neighbours compute the same bound).  XCD x = blockIdx & 7 takes the contiguous ranges [32x, 32x + 32).
-  [[maybe_unused]] int sk_r = 0, sk_it = 0, sk_end = 0;
-  auto sk_bound = [&](int r) {
-    int b = (int)((int64_t)r * p.sk_total / 256);
-    const int rem = b % nk_all;
-    if (rem < SK_MIN) b -= rem; else if (rem > nk_all - SK_MIN) b += nk_all - rem;
-    return b;
-  };
-  // persistent stream: work item `it` of workgroup b is tile id it*256 + (b&7)*32 + (b>>3) - the tile a launch of
-  // persist_iters*256 workgroups hands to the same CU slot in its round `it` (tile order bit 1)
-  auto persist_coords = [&](int it, int& pm0, int& pn0) {
-    tile_coords(p, p.tile0 + it * 256 + ((blockIdx.x & 7) << 5) + (blockIdx.x >> 3), 0, BM, BN, pm0, pn0);
-  };
-  if constexpr (PERSIST) persist_coords(0, m0, n0);
-  else if constexpr (STREAMK) {
-    sk_r = ((blockIdx.x & 7) << 5) + (blockIdx.x >> 3);
-    sk_it = sk_bound(sk_r); sk_end = sk_bound(sk_r + 1);
-    if (sk_it >= sk_end) return;
-    tile_coords(p, p.tile0 + sk_it / nk_all, 0, BM, BN, m0, n0);
-  }
-  else ksplit = map_tile(p, BM, BN, m0, n0);
-#ifdef VLB_TOOLS
-  // timing experiment: de-synchronise the CUs (every workgroup of a launch otherwise starts, and reaches its epilogue's
-  // burst of memory traffic, at the same moment): odd workgroups of the first round of 256 wait p.stagger x 10 ns
-  if (p.stagger > 0 && blockIdx.x < 256 && (blockIdx.x & 8)) {
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)p.stagger) __builtin_amdgcn_s_sleep(32);
-  }
-#endif
+  const int ksplit = map_tile(p, BM, BN, m0, n0);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -794,11 +612,10 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
   const int r0 = wave * 8 + srow;
   const int colb = (sslot ^ ((r0 >> 1) & 7)) * 8;
   // (tools build, timing only: ABL bit 4 / 5 make every workgroup stage W / A panel 0 - operands that always hit in L2)
-  int rowA = (ABL & 32) ? r0 : m0 + r0, rowW = (ABL & 16) ? r0 : n0 + r0;       // (re-pointed per output tile by the persistent stream / per stream-K segment)
+  const int rowA = (ABL & 32) ? r0 : m0 + r0, rowW = (ABL & 16) ? r0 : n0 + r0;
   // split-K tail: this workgroup walks K-tiles [kt_lo, kt_lo + nk) of the concatenated (pair 1 | pair 2) sequence
-  int kt_lo = SPLITK ? (int)((int64_t)ksplit * nk_all / p.k_splits) : 0;
-  int nk = SPLITK ? (int)((int64_t)(ksplit + 1) * nk_all / p.k_splits) - kt_lo : nk_all;
-  if constexpr (STREAMK) { kt_lo = sk_it % nk_all; nk = min(nk_all - kt_lo, sk_end - sk_it); }     // first segment (re-set per segment below)
+  const int kt_lo = SPLITK ? (int)((int64_t)ksplit * nk_all / p.k_splits) : 0;
+  const int nk = SPLITK ? (int)((int64_t)(ksplit + 1) * nk_all / p.k_splits) - kt_lo : nk_all;
 
   // LDS-DMA sources = uniform base (SGPR pair, advanced 128 B per K-tile) + a per-instruction 32-bit
   // byte offset held in a VGPR: the loop issues each global_load_lds with no address arithmetic at all.
@@ -815,24 +632,13 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
     curW = reinterpret_cast<const char*>(W_) + (int64_t)kt_in_pair * ROW_BYTES;
   };
   auto select = [&](int rel) {          // call with consecutive rel = 0, 1, ..: positions the bases on K-tile kt_lo + rel
-    const int kt = KRANGE ? rel + kt_lo : rel;
+    const int kt = SPLITK ? rel + kt_lo : rel;
     if (rel == 0) {
-      const bool second = KRANGE && kt >= nk1;
+      const bool second = SPLITK && kt >= nk1;
       if (MASKED != second) set_operands(p.A2, p.W2, p.lda2, p.ldw2, second ? kt - nk1 : kt);
       else set_operands(p.A, p.W, p.lda, p.ldw, second ? kt - nk1 : kt);
     }
     else if (kt == nk1) { if (MASKED) set_operands(p.A, p.W, p.lda, p.ldw, 0); else set_operands(p.A2, p.W2, p.lda2, p.ldw2, 0); }
-    else { curA += ROW_BYTES; curW += ROW_BYTES; }
-  };
-  // persistent stream: K-tile kt2 = kt + 2 of the CURRENT output tile, which for kt2 >= nk is K-tile kt2 - nk of the NEXT
-  // one (its coordinates in nm0 / nn0; the host guarantees nk >= 4 and K2 == 0 or K2 >= BK)
-  int nm0 = 0, nn0 = 0, p_it = 0, p_par = 0;
-  auto select_p = [&](int kt2) __attribute__((always_inline)) {
-    if (kt2 == nk) {
-      persist_coords(p_it + 1, nm0, nn0);
-      rowA = nm0 + r0; rowW = nn0 + r0;
-      set_operands(p.A, p.W, p.lda, p.ldw, 0);
-    } else if (kt2 == nk1 && kt2 < nk) { set_operands(p.A2, p.W2, p.lda2, p.ldw2, 0); }
     else { curA += ROW_BYTES; curW += ROW_BYTES; }
   };
   auto dma = [&](int buf, int i) {     // instruction i of the selected tile (0..A_LD-1: A, then W)
@@ -860,7 +666,6 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
 #define W4_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define W4_BARRIER() do { W4_FENCE(); __builtin_amdgcn_s_barrier(); W4_FENCE(); } while (0)
 
-sk_segment: __attribute__((unused));                  // stream-K: every further segment of this workgroup's range re-enters here
   select(0);
 #pragma unroll
   for (int i = 0; i < A_LD + B_LD; ++i) dma(0, i);
@@ -879,31 +684,18 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
   // is loaded right behind it.  Only af[7] dies too late (it would have to be read after the barrier that
   // releases its buffer), so it alone has a second slot (a7[2]).
   bf16x8 wf[2][NT], af[MT - 1], a7[2];
-  // Row-split loop (ROWSPLIT): one set of fragments for BOTH k-steps, wr[ks][j] / ar[ks][i]; see tile_r below.
-  constexpr int HM = MT / 2;
-  bf16x8 wr[2][NT], ar[2][MT];
-  if constexpr (!ROWSPLIT) {
 #pragma unroll
-    for (int j = 0; j < NT; ++j) wf[0][j] = frag(smem, b_off[0], j);
+  for (int j = 0; j < NT; ++j) wf[0][j] = frag(smem, b_off[0], j);
 #pragma unroll
-    for (int i = 0; i < MT - 1; ++i) af[i] = frag(smem, a_off[0], i);
-    a7[0] = frag(smem, a_off[0], MT - 1);
-  } else {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int j = 0; j < NT - 1; ++j) wr[ks][j] = frag(smem, b_off[ks], j);      // (fragment NT-1 is fetched at the top of every tile)
-#pragma unroll
-      for (int i = 0; i < HM; ++i) ar[ks][i] = frag(smem, a_off[ks], i);
-    }
-  }
+  for (int i = 0; i < MT - 1; ++i) af[i] = frag(smem, a_off[0], i);
+  a7[0] = frag(smem, a_off[0], MT - 1);
   __builtin_amdgcn_s_waitcnt(0xc07f);        // so that no compiler-inserted wait lands inside the loop
   W4_FENCE();
 
   // one K-tile; MORE: a tile kt+1 exists (fetch its first fragments), LOAD2: tile kt+2 exists (LDS-DMA it)
-  auto tile_k = [&](int kt, auto more_c, auto load2_c) __attribute__((always_inline)) {
+  auto tile = [&](int kt, auto more_c, auto load2_c) __attribute__((always_inline)) {
     constexpr bool MORE = decltype(more_c)::value, LOAD2 = decltype(load2_c)::value;
-    const int buf = PERSIST ? p_par : (kt & 1);            // the stream's K-tiles alternate stages across output tiles
+    const int buf = kt & 1;
     const char* sb = smem + buf * STAGE;
     const char* sn = smem + (buf ^ 1) * STAGE;
     // ---------------- block 1: MFMA(k-step 0) || reads of k-step 1
@@ -926,7 +718,7 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
     __builtin_amdgcn_s_waitcnt(0xc07f);
     if constexpr (!(ABL & 8)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if constexpr (!(ABL & 4)) { W4_BARRIER(); } else { W4_FENCE(); }
-    if constexpr (LOAD2) { if constexpr (PERSIST) select_p(kt + 2); else select(kt + 2); }
+    if constexpr (LOAD2) select(kt + 2);
     // ---------------- block 2: MFMA(k-step 1) || DMA of tile kt+2 || reads of tile kt+1, k-step 0
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
@@ -951,150 +743,14 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
     // last (asm, hence opaque) MFMAs: XDL-write -> VALU-read needs up to 18 wait states
     asm volatile("s_nop 15" ::: "memory");
     W4_FENCE();
-    if constexpr (PERSIST) p_par ^= 1;
   };
-  // Row-split K-tile (the MX-fp8 kernel's schedule, gemm_fp8.hip): the tile's MFMAs run as two blocks of NT groups, group j =
-  // W fragment j (both k-steps) against row tiles 0..HM-1 (block 1) or HM..MT-1 (block 2).  W fragments are refreshed in place
-  // one group behind their last use in block 2, the row halves alternate, so ONE set of fragments serves and - unlike the
-  // k-step split, whose stage only frees up at the middle barrier - the W image is free early in block 1 (barrier S): the
-  // LDS-DMA pieces of tile kt+2 are spread over BOTH blocks (W in block 1, A in block 2), half as dense among the MFMAs.
-#ifdef VLB_TOOLS
-  auto tile_r = [&](int kt, auto more_c, auto load2_c) __attribute__((always_inline)) {
-    constexpr bool MORE = decltype(more_c)::value, LOAD2 = decltype(load2_c)::value;
-    constexpr int S_AT = 1;
-    const char* sb = smem + (kt & 1) * STAGE;
-    const char* sn = smem + ((kt & 1) ^ 1) * STAGE;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) wr[ks][NT - 1] = frag(sb, b_off[ks], NT - 1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = HM; i < MT; ++i) ar[ks][i] = frag(sb, a_off[ks], i);
-    // ---------------- block 1: rows 0..HM-1 || DMA of W(kt+2)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      if constexpr (LOAD2) {
-        if (j == S_AT) {                      // S: every wave holds all W fragments of tile kt - this stage's W image is free
-          __builtin_amdgcn_s_waitcnt(0xc07f);
-          W4_BARRIER();
-          select(kt + 2);
-        }
-        if (j >= S_AT) {
-#pragma unroll
-          for (int pc = 0; pc < B_LD; ++pc)
-            if (pc * (NT - S_AT) / B_LD == j - S_AT) dma(kt & 1, A_LD + pc);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < HM; ++i) mfma_tied(acc[i][j], wr[ks][j], ar[ks][i]);
-      W4_FENCE();
-    }
-    if constexpr (MORE) {
-      // M: every wave holds all of tile kt (the A image is free too); tile kt+1 has landed - only W(kt+2) may still fly
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-      if constexpr (LOAD2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(B_LD) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      W4_BARRIER();
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = 0; i < HM; ++i) ar[ks][i] = frag(sn, a_off[ks], i);
-    }
-    // ---------------- block 2: rows HM..MT-1 || DMA of A(kt+2) || W fragments of tile kt+1 in place
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      if constexpr (LOAD2) {
-#pragma unroll
-        for (int pc = 0; pc < A_LD; ++pc)
-          if (pc * NT / A_LD == j) dma(kt & 1, pc);
-      }
-      if constexpr (MORE) {
-        if (j >= 1) {
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) wr[ks][j - 1] = frag(sn, b_off[ks], j - 1);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int i = HM; i < MT; ++i) mfma_tied(acc[i][j], wr[ks][j], ar[ks][i]);
-      W4_FENCE();
-    }
-    asm volatile("s_nop 15" ::: "memory");
-    W4_FENCE();
-  };
-  auto tile = [&](int kt, auto more_c, auto load2_c) __attribute__((always_inline)) {
-    if constexpr (ROWSPLIT) tile_r(kt, more_c, load2_c); else tile_k(kt, more_c, load2_c);
-  };
-#else
-  auto& tile = tile_k;                   // product build: the k-step loop, called directly (tile_r is never instantiated)
-#endif
   using T_ = std::true_type; using F_ = std::false_type;
-  if constexpr (PERSIST) {
-    // Persistent stream (tools experiment): the K loop runs on across output tiles - the last two K-tiles of a tile issue
-    // the LDS-DMA of the next tile's first two, the last one fetches its first fragments - so between two tiles only the
-    // epilogue (convert + store, no wait) and the re-zeroing of the accumulators stand in the MFMA stream: no workgroup
-    // launch, no cold prologue, no drain.
-    const int fq_ = lane >> 4;
-    auto epilogue_p = [&]() __attribute__((always_inline)) {
-      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; j += 4)
-          asm volatile("" : "+a"(acc[i][j]), "+a"(acc[i][j + 1]), "+a"(acc[i][j + 2]), "+a"(acc[i][j + 3]));
-      if (p.act == VLB_ACT_SWIGLU_PAIR) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-          const int m = m0 + wm * TM + i * 16 + fr;
-          if (m >= p.M) continue;
-#pragma unroll
-          for (int j = 0; j < NT; j += 4)
-            store_swiglu8(p, acc[i][j], acc[i][j + 1], acc[i][j + 2], acc[i][j + 3], m, (n0 + wn * TN) / 2 + (j / 2) * 16 + fq_ * 4, fq_);
-        }
-      } else {
-#define W4_EPILOGUE_P(KIND)                                                                                            \
-  _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                      \
-    const int m = m0 + wm * TM + i * 16 + fr;                                                                           \
-    if (m >= p.M) continue;                                                                                             \
-    _Pragma("unroll") for (int j = 0; j < NT; j += 2)                                                                   \
-      w4_store_frag2<KIND>(p, acc[i][j], acc[i][j + 1], m, n0 + wn * TN + j * 16 + fq_ * 4, fq_);                       \
-  }
-        const int kind = w4_epilogue_kind(p);
-        if (kind == EPI_PLAIN) { W4_EPILOGUE_P(EPI_PLAIN) }
-        else if (kind == EPI_RESIDUAL) { W4_EPILOGUE_P(EPI_RESIDUAL) }
-        else { W4_EPILOGUE_P(EPI_GENERIC + 0) }              // (bias / no activation; the tools launch admits nothing else)
-#undef W4_EPILOGUE_P
-      }
-    };
-    for (p_it = 0; p_it < p.persist_iters; ++p_it) {
-      const bool last_tile = p_it + 1 == p.persist_iters;
-      const int n_tt = last_tile ? nk - 2 : nk;
-      for (int kt = 0; kt < n_tt; ++kt) tile(kt, T_{}, T_{});
-      if (last_tile) {
-        tile(nk - 2, T_{}, F_{});
-        tile(nk - 1, F_{}, F_{});
-      }
-      epilogue_p();
-      if (p_it + 1 < p.persist_iters) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NT; ++j) { acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; asm volatile("" : "+a"(acc[i][j])); }
-        asm volatile("s_nop 7" ::: "memory");                // VALU writes of the accumulators settle before the next MFMA reads them
-        m0 = nm0; n0 = nn0;
-      }
-    }
-    return;
-  }
   int kt = 0;
   if constexpr (MASKED) {
     // K-tile 0 = the LoRA pair u.A (host guarantees K2 == 64 and nk >= 3); then keep/(1-p) on the accumulators.
     // In a split-K tail only the first K range holds the pair: the others run their first main tile here and the
     // mask degenerates to keep-all x 1.0 (same straight-line code, no branch around the pinned accumulators).
-    const bool later_range = (SPLITK && ksplit != 0) || (STREAMK && kt_lo != 0);
+    const bool later_range = SPLITK && ksplit != 0;
     const uint32_t m_thresh = later_range ? 0u : p.drop_thresh;
     const float m_scale = later_range ? 1.f : p.drop_scale;
     tile(0, T_{}, T_{});
@@ -1155,52 +811,6 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
         *reinterpret_cast<f32x4*>(wt + ((i * NT + j) * 64 + lane) * 4) = acc[i][j];
     return;
   }
-#define W4_DONE do { if constexpr (STREAMK) goto sk_next; else return; } while (0)
-  if constexpr (STREAMK) {
-    if (kt_lo != 0) {
-      // contributor: the rest of a tile whose first K-tiles belong to workgroup sk_r - 1.  Slab sk_r, then the flag.
-      float* wt = p.ws + ((int64_t)sk_r * 4 + wave) * (MT * NT * 256);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-          *reinterpret_cast<f32x4*>(wt + ((i * NT + j) * 64 + lane) * 4) = acc[i][j];
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's slab stores have reached L2
-      __builtin_amdgcn_s_barrier();                             // ... and so have the other three waves'
-      if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");      // L2 write-back (buffer_wbl2 sc1): visible to the owner's XCD
-        __hip_atomic_store(p.sk_flags + sk_r, p.sk_want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      goto sk_next;
-    }
-    if (nk < nk_all) {
-      // owner of a tile whose remaining K-tiles are the first segment of workgroup sk_r + 1: wait for its slab (bounded),
-      // add it to the accumulators, then the normal epilogue
-      if (tid == 0) {
-        int spins = 0;
-        while (__hip_atomic_load(p.sk_flags + sk_r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != p.sk_want) {
-          __builtin_amdgcn_s_sleep(16);
-          if (++spins > (1 << 20)) {                            // ~2 s: never in a healthy launch; results are then wrong and the host is told
-            __hip_atomic_store(p.sk_err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-          }
-        }
-      }
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");        // L2 / L1 invalidate (buffer_inv sc1): the slab is read from where the release put it
-      const float* ps = p.ws + ((int64_t)(sk_r + 1) * 4 + wave) * (MT * NT * 256);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const f32x4 t = *reinterpret_cast<const f32x4*>(ps + ((i * NT + j) * 64 + lane) * 4);
-          f32x4 v = acc[i][j];
-          v[0] += t[0]; v[1] += t[1]; v[2] += t[2]; v[3] += t[3];
-          acc[i][j] = v;
-          asm volatile("" : "+a"(acc[i][j]));
-        }
-    }
-  }
   // The four-wave kernels store 16 bytes per lane (store_pair16): the host only routes launches here whose C / aux rows are
   // 16-byte aligned (GemmArgs::wide).  One loop nest per epilogue kind - every loop over acc[][] must unroll completely
   // (a dynamically indexed accumulator array is moved to scratch memory, and with it the whole K loop).
@@ -1213,7 +823,7 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
       for (int j = 0; j < NT; j += 4)
         store_swiglu8(p, acc[i][j], acc[i][j + 1], acc[i][j + 2], acc[i][j + 3], m, (n0 + wn * TN) / 2 + (j / 2) * 16 + fq * 4, fq);
     }
-    W4_DONE;
+    return;
   }
 #define W4_EPILOGUE(KIND)                                                                                              \
   _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                      \
@@ -1222,250 +832,15 @@ sk_segment: __attribute__((unused));                  // stream-K: every further
     _Pragma("unroll") for (int j = 0; j < NT; j += 2)                                                                   \
       w4_store_frag2<KIND>(p, acc[i][j], acc[i][j + 1], m, n0 + wn * TN + j * 16 + fq * 4, fq);                         \
   }
-  {
-    const int kind = w4_epilogue_kind(p);
-    if (kind == EPI_PLAIN) { W4_EPILOGUE(EPI_PLAIN) W4_DONE; }
-    if (kind == EPI_RESIDUAL) { W4_EPILOGUE(EPI_RESIDUAL) W4_DONE; }
-    if (kind == EPI_SWIGLU_BWD) { W4_EPILOGUE(EPI_SWIGLU_BWD) W4_DONE; }
+  const int kind = w4_epilogue_kind(p);
+  if (kind == EPI_PLAIN) { W4_EPILOGUE(EPI_PLAIN) return; }
+  if (kind == EPI_RESIDUAL) { W4_EPILOGUE(EPI_RESIDUAL) return; }
+  if (kind == EPI_SWIGLU_BWD) { W4_EPILOGUE(EPI_SWIGLU_BWD) return; }
 #define W4_EPILOGUE_ACT(ACT) W4_EPILOGUE(EPI_GENERIC + ACT)
-    VLB_DISPATCH_ACT(p.act, W4_EPILOGUE_ACT);
+  VLB_DISPATCH_ACT(p.act, W4_EPILOGUE_ACT);
 #undef W4_EPILOGUE_ACT
 #undef W4_EPILOGUE
-  }
-sk_next: __attribute__((unused));
-  if constexpr (STREAMK) {
-    sk_it += nk;
-    if (sk_it < sk_end) {
-      // next segment of this workgroup's range: a new tile from its first K-tile (whole, or the head this workgroup owns)
-      tile_coords(p, p.tile0 + sk_it / nk_all, 0, BM, BN, m0, n0);
-      rowA = m0 + r0; rowW = n0 + r0;
-      kt_lo = sk_it % nk_all; nk = min(nk_all - kt_lo, sk_end - sk_it);
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) { acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f}; asm volatile("" : "+a"(acc[i][j])); }
-      asm volatile("s_nop 7" ::: "memory");                // VALU writes of the accumulators settle before the next MFMA reads them
-      goto sk_segment;
-    }
-  }
-#undef W4_DONE
 }
-
-#ifdef VLB_TOOLS
-// ------------------------------------------------------------------------------------------------
-// W-direct variant of the four-wave 256x256x64 tile (gemm_wd_kernel).  TOOLS BUILD ONLY: built in round 4 because the
-// ablations of gemm_w4_kernel pointed at the LDS-DMA issue, measured 4-9 % SLOWER than gemm_w4_kernel on every shape it serves
-// (interleaved same-process A/B, outputs bit-identical; DESIGN.md 5.1 has the table and the instruction-level probe that
-// explains it: a fragment-shaped global load - 16 rows x 64 B - costs the vector memory path ~4x a line-shaped one per byte).
-// Kept as the record of that experiment and as the A/B partner of tools/ab_gemm_rowsplit.py (VLB_AB=wd).
-//
-// What the ablations of gemm_w4_kernel say: with one wave per SIMD the LDS-DMA ISSUE is the largest cost
-// of the K loop (16 pieces per wave per K-tile, 60-185 issue cycles each, during which the in-order wave issues no MFMA).
-// Here only A goes through LDS: the four waves sit 1 (M) x 4 (N), wave w owns output columns [64w, 64w+64) of ALL 256
-// rows (16 x 4 accumulator tiles = the same 256 AGPRs), so
-//   * a wave's W fragments are its own (no other wave needs them): they come straight from global / L2 into REGISTERS,
-//     one K-tile ahead - 8 plain global_load_dwordx4 per wave per K-tile (16 rows x 64 B each: lane (fr, fq) fetches the
-//     16 bytes of W row fr that it feeds to the MFMA as k-group fq), no LDS write, no LDS read, no barrier dependence;
-//   * A (the operand all four waves share) is staged by LDS-DMA as before: 32 pieces of 1 KiB per K-tile = 8 per wave
-//     (half the pieces of the 2 x 2 layout), 32 KB per stage, two stages;
-//   * every wave reads all 16 A fragments of a k-step from LDS: 32 ds_read_b128 per wave per K-tile, as many as before,
-//     against an LDS image that now takes half the DMA write traffic.
-// Per K-tile and wave: 128 MFMA, 32 ds_read_b128, 8 LDS-DMA pieces, 8 global loads, 1 barrier, two COUNTED vmcnt waits
-// (never 0 in the loop: W(t+1) is waited for with A(t+2)'s pieces still in flight and vice versa).
-//
-// Registers by hand.  The W double buffer lives in v[192:255]: buffer b, k-step ks, fragment j = v[192 + 16(2b+ks)... see
-// WD_WREG.  The loads and the MFMAs that read them name those registers literally (the compiler-allocated prototype of
-// round 2 died in register allocation: asm outputs that are written asynchronously cannot be expressed as operands); every
-// asm statement that writes them lists all 64 as clobbers, so the compiler keeps nothing of its own there across any of
-// them, and tools/audit_gemm_isa.py proves on the generated ISA that no compiler-issued instruction touches v192+ between
-// the first W load and the end of the K loop.  Accumulators are tied AGPR tuples as in gemm_w4_kernel.
-// ------------------------------------------------------------------------------------------------
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-#define WD_CLOBBER "v192","v193","v194","v195","v196","v197","v198","v199","v200","v201","v202","v203","v204","v205","v206","v207","v208","v209","v210","v211","v212","v213","v214","v215","v216","v217","v218","v219","v220","v221","v222","v223","v224","v225","v226","v227","v228","v229","v230","v231","v232","v233","v234","v235","v236","v237","v238","v239","v240","v241","v242","v243","v244","v245","v246","v247","v248","v249","v250","v251","v252","v253","v254","v255"
-// W register quad of buffer b (tile parity), k-step ks, fragment j
-constexpr int WD_WREG(int b, int ks, int j) { return 192 + ((b * 2 + ks) * 4 + j) * 4; }
-template <int R, int OFF>
-__device__ __forceinline__ void wd_load_w(uint32_t voff, const char* sbase) {
-  asm volatile("global_load_dwordx4 v[%c2:%c3], %0, %1 offset:%c4" ::"v"(voff), "s"(sbase), "i"(R), "i"(R + 3), "i"(OFF) : "memory", WD_CLOBBER);
-}
-template <int R>
-__device__ __forceinline__ void wd_mfma(f32x4& c, const bf16x8& a) {
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, v[%c2:%c3], %1, %0" : "+a"(c) : "v"(__builtin_bit_cast(i32x4_t, a)), "i"(R), "i"(R + 3));
-}
-
-__global__ __launch_bounds__(256, 1) void gemm_wd_kernel(GemmArgs p) {
-  constexpr int MT = 16, NT = 4, BM = 256, BN = 256, TN = 16 * NT;
-  constexpr int STAGE = BM * ROW_BYTES;               // one A tile: 32 KB
-  constexpr int A_LD = BM / 32;                       // LDS-DMA pieces per wave per K-tile
-  constexpr int W_LD = 2 * NT;                        // W loads per wave per K-tile
-  constexpr int LAST_A = MT / 2;                      // group in which the double-slotted last A fragment is fetched
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  asm volatile("" ::: WD_CLOBBER);                    // v[192:255] are part of this kernel's register budget from here on
-
-  int m0, n0;
-  map_tile(p, BM, BN, m0, n0);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fq = lane >> 4;
-
-  // A staging as in gemm_w4_kernel: piece i of this wave fills LDS rows [i*32 + wave*8, +8), swizzle on the source address
-  const int srow = (lane >> 3), sslot = lane & 7;
-  const int r0 = wave * 8 + srow;
-  const int colb = (sslot ^ ((r0 >> 1) & 7)) * 8;
-  const int rowA = m0 + r0;
-  const int rowW = n0 + wave * TN + fr;               // W row of this lane in fragment 0 (fragment j: + 16 j)
-  const int nk1 = p.K / BK, nk = nk1 + p.K2 / BK;
-
-  // two cursors: A's LDS-DMA runs two K-tiles ahead of the MFMAs, W's register loads one
-  uint32_t offA[A_LD], offW[NT];
-  const char* curA; const char* curW;
-  auto set_a = [&](const bf16* A_, int lda_) {
-#pragma unroll
-    for (int i = 0; i < A_LD; ++i) offA[i] = ((uint32_t)min(rowA + 32 * i, p.M - 1) * (uint32_t)lda_ + (uint32_t)colb) * 2u;
-    curA = reinterpret_cast<const char*>(A_);
-  };
-  auto set_w = [&](const bf16* W_, int ldw_) {
-#pragma unroll
-    for (int j = 0; j < NT; ++j) offW[j] = ((uint32_t)(rowW + 16 * j) * (uint32_t)ldw_ + (uint32_t)(fq * 8)) * 2u;
-    curW = reinterpret_cast<const char*>(W_);
-  };
-  auto select_a = [&](int kt) { if (kt == 0) set_a(p.A, p.lda); else if (kt == nk1) set_a(p.A2, p.lda2); else curA += ROW_BYTES; };
-  auto select_w = [&](int kt) { if (kt == 0) set_w(p.W, p.ldw); else if (kt == nk1) set_w(p.W2, p.ldw2); else curW += ROW_BYTES; };
-  auto dma = [&](int buf, int i) { glds16(curA + offA[i], smem + buf * STAGE + wave * 8 * ROW_BYTES + i * 32 * ROW_BYTES); };
-
-  f32x4 acc[MT][NT];
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  int a_off[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) a_off[ks] = lds_off(fr, ks * 4 + fq);
-  auto frag = [&](const char* sb, int off, int t) { return *reinterpret_cast<const bf16x8*>(sb + off + t * 16 * ROW_BYTES); };
-
-#define WD_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define WD_BARRIER() do { WD_FENCE(); __builtin_amdgcn_s_barrier(); WD_FENCE(); } while (0)
-
-  // prologue: A(0) -> stage 0, W(0) -> register buffer 0, A(1) -> stage 1
-  select_a(0);
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) dma(0, i);
-  select_w(0);
-  static_for<0, W_LD>([&](auto qc) {
-    constexpr int q = decltype(qc)::value, j = q >> 1, ks = q & 1;
-    wd_load_w<WD_WREG(0, ks, j), ks * 64>(offW[j], curW);
-  });
-  if (nk > 1) select_a(1);                            // (a single-tile K range re-fetches tile 0: same counted waits everywhere)
-#pragma unroll
-  for (int i = 0; i < A_LD; ++i) dma(1, i);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD) : "memory");        // A(0) and W(0) are in; A(1) may still fly
-  WD_BARRIER();
-
-  // A fragments are refreshed IN PLACE: af[i] is consumed by the 4 MFMAs of group i and refetched (next k-step) at the top
-  // of group i+1; the last one would be refetched right in front of the barrier that needs it complete, so it has two slots.
-  bf16x8 af[MT - 1], al[2];
-#pragma unroll
-  for (int i = 0; i < MT - 1; ++i) af[i] = frag(smem, a_off[0], i);
-  al[0] = frag(smem, a_off[0], MT - 1);
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  WD_FENCE();
-
-  // One K-tile kt of parity PAR (= its LDS stage and its W register buffer).  ONE body serves every tile: past the end of
-  // the K range the cursors simply stop advancing, so the last tiles re-fetch the final K-tile's operands into buffers that
-  // nobody reads again (redundant loads of valid addresses instead of tail variants of a 128-MFMA body: with several
-  // variants inlined the register allocator no longer keeps the 64 accumulator tuples in place).
-  auto tile = [&](int kt, auto par_c) __attribute__((always_inline)) {
-    constexpr int PAR = decltype(par_c)::value;
-    const char* sb = smem + PAR * STAGE;
-    const char* sn = smem + (PAR ^ 1) * STAGE;
-    if (kt + 1 < nk) select_w(kt + 1);
-    // ---------------- block 1: MFMA(k-step 0) || A reads of k-step 1 || W(kt+1) -> the other register buffer
-    static_for<0, MT>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      if constexpr (i >= 1) af[i - 1] = frag(sb, a_off[1], i - 1);
-      if constexpr (i == LAST_A) al[1] = frag(sb, a_off[1], MT - 1);
-      if constexpr (i % 2 == 0) {
-        constexpr int q = i / 2, j = q >> 1, ks = q & 1;
-        wd_load_w<WD_WREG(PAR ^ 1, ks, j), ks * 64>(offW[j], curW);
-      }
-      static_for<0, NT>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        if constexpr (i == MT - 1) wd_mfma<WD_WREG(PAR, 0, j)>(acc[i][j], al[0]);
-        else wd_mfma<WD_WREG(PAR, 0, j)>(acc[i][j], af[i]);
-      });
-      WD_FENCE();
-    });
-    // this wave is done reading stage PAR (lgkmcnt); A(kt+1) has landed: only the W(kt+1) loads, issued after it, may fly
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_LD) : "memory");
-    WD_BARRIER();
-    if (kt + 2 < nk) select_a(kt + 2);
-    // ---------------- block 2: MFMA(k-step 1) || LDS-DMA of A(kt+2) into stage PAR || A reads of tile kt+1, k-step 0
-    static_for<0, MT>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      if constexpr (i >= 1) af[i - 1] = frag(sn, a_off[0], i - 1);
-      if constexpr (i == LAST_A) al[0] = frag(sn, a_off[0], MT - 1);
-      if constexpr (i % 2 == 0) dma(PAR, i / 2);
-      static_for<0, NT>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        if constexpr (i == MT - 1) wd_mfma<WD_WREG(PAR, 1, j)>(acc[i][j], al[1]);
-        else wd_mfma<WD_WREG(PAR, 1, j)>(acc[i][j], af[i]);
-      });
-      WD_FENCE();
-    });
-    // next tile's first fragments are in; W(kt+1) has landed: only A(kt+2)'s pieces, issued after it, may fly
-    __builtin_amdgcn_s_waitcnt(0xc07f);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD) : "memory");
-    asm volatile("s_nop 15" ::: "memory");      // XDL write -> (compiler-placed) VALU read of an accumulator on a loop exit edge
-    WD_FENCE();
-  };
-  using P0 = std::integral_constant<int, 0>; using P1 = std::integral_constant<int, 1>;
-  int kt = 0;
-  for (; kt + 1 < nk; kt += 2) { tile(kt, P0{}); tile(kt + 1, P1{}); }
-  if (kt < nk) tile(kt, P0{});
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the redundant tail fetches (register and LDS destinations) are retired
-  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-  for (int i = 0; i < MT; ++i) asm volatile("" : "+a"(acc[i][0]), "+a"(acc[i][1]), "+a"(acc[i][2]), "+a"(acc[i][3]));
-#undef WD_FENCE
-#undef WD_BARRIER
-
-  // epilogues of gemm_w4_kernel with this kernel's wave block (rows m0.., columns n0 + 64 wave ..)
-  if (p.act == VLB_ACT_SWIGLU_PAIR) {
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-      const int m = m0 + i * 16 + fr;
-      if (m >= p.M) continue;
-      store_swiglu8(p, acc[i][0], acc[i][1], acc[i][2], acc[i][3], m, (n0 + wave * TN) / 2 + fq * 4, fq);
-    }
-    return;
-  }
-#define WD_EPILOGUE(KIND)                                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MT; ++i) {                                                                      \
-    const int m = m0 + i * 16 + fr;                                                                                     \
-    if (m >= p.M) continue;                                                                                             \
-    _Pragma("unroll") for (int j = 0; j < NT; j += 2)                                                                   \
-      w4_store_frag2<KIND>(p, acc[i][j], acc[i][j + 1], m, n0 + wave * TN + j * 16 + fq * 4, fq);                       \
-  }
-  const int kind = w4_epilogue_kind(p);
-  if (kind == EPI_PLAIN) { WD_EPILOGUE(EPI_PLAIN) return; }
-  if (kind == EPI_RESIDUAL) { WD_EPILOGUE(EPI_RESIDUAL) return; }
-  if (kind == EPI_SWIGLU_BWD) { WD_EPILOGUE(EPI_SWIGLU_BWD) return; }
-#define WD_EPILOGUE_ACT(ACT) WD_EPILOGUE(EPI_GENERIC + ACT)
-  VLB_DISPATCH_ACT(p.act, WD_EPILOGUE_ACT);
-#undef WD_EPILOGUE_ACT
-#undef WD_EPILOGUE
-}
-
-#endif  // VLB_TOOLS (W-direct experiment)
 
 // Second half of a split-K tail: block (tile, i) sums row-tile i of every wave's accumulators over the splits in
 // a fixed order (deterministic) and applies the four-wave kernel's epilogue with the same thread <-> element map.
@@ -1504,34 +879,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmArgs p) {
 #undef W4_REDUCE_EPILOGUE
 }
 
-#ifdef VLB_TOOLS
-int g_w4_rowsplit = 0;              // tools: 1 = every four-wave launch uses the row-split K loop (ABL bit 6)
-int g_w4_persist = 0;               // tools: 1 = whole-tile 256-column launches run as a persistent stream (ABL bit 7)
-#endif
-#ifdef VLB_TOOLS
-int g_wd = 0;                       // tools: 1 = whole 256x256-tile launches run on gemm_wd_kernel (A/B of the W-direct experiment)
-// whole 256x256 tiles, both operand pairs, every epilogue kind; no masked pair, no split-K (those launches keep gemm_w4_kernel)
-inline int launch_wd(GemmArgs& a, hipStream_t s) {
-  constexpr int LDS = 2 * 256 * ROW_BYTES;
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_wd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (attr != hipSuccess) {
-    vlb_set_error("gemm: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr));
-    return VLB_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(gemm_wd_kernel, dim3(a.grid), dim3(256), LDS, s, a);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
-}
-#endif
-
 template <int NT, int ABL, int MT = 8, bool MASKED = false, bool SPLITK = false>
 int launch_w4(GemmArgs& a, hipStream_t s) {
-  constexpr bool STREAMK = (ABL & 256) != 0;
-#ifdef VLB_TOOLS
-  if constexpr (NT == 8 && ABL == 0 && MT == 8 && !MASKED && !SPLITK && !STREAMK) {
-    if (g_wd && a.split_n == 1 && a.k_splits <= 1) return launch_wd(a, s);
-  }
-#endif
   constexpr int LDS = 2 * (32 * MT + 32 * NT) * ROW_BYTES;
   // once per process and kernel; a function-local static's initialisation is thread-safe (C++11)
   static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<NT, ABL, MT, MASKED, SPLITK>),
@@ -1540,78 +889,10 @@ int launch_w4(GemmArgs& a, hipStream_t s) {
     vlb_set_error("gemm: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr));
     return VLB_ERR_LAUNCH;
   }
-#ifdef VLB_TOOLS
-  if constexpr (ABL == 0 && NT == 8 && !MASKED && !SPLITK && !STREAMK) {
-    // tools A/B: persistent stream over the full rounds of the launch (the ragged rest as a normal launch)
-    const int nk_all = a.K / 64 + a.K2 / 64;
-    const bool act_ok = a.act == VLB_ACT_NONE || a.act == VLB_ACT_SWIGLU_PAIR;
-    if (g_w4_persist && (a.order & 2) && !(a.order & 4) && a.split_n == 1 && a.k_splits <= 1 && a.grid >= 512 && nk_all >= 4 && act_ok &&
-        (a.K2 == 0 || a.K2 >= 64)) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<NT, 128, MT, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return VLB_ERR_LAUNCH;
-      GemmArgs q = a;
-      q.persist_iters = a.grid / 256;
-      hipLaunchKernelGGL((gemm_w4_kernel<NT, 128, MT, false, false>), dim3(256), dim3(256), LDS, s, q);
-      VLB_LAUNCH_CHECK();
-      const int rest = a.grid - q.persist_iters * 256;
-      if (rest == 0) return VLB_OK;
-      GemmArgs r = a;
-      r.tile0 = a.tile0 + q.persist_iters * 256; r.grid = rest;
-      hipLaunchKernelGGL((gemm_w4_kernel<NT, ABL, MT, MASKED, SPLITK>), dim3(r.grid), dim3(256), LDS, s, r);
-      VLB_LAUNCH_CHECK();
-      return VLB_OK;
-    }
-  }
-  if constexpr (ABL == 0 && NT == 8 && !MASKED && !SPLITK && !STREAMK) {
-    if (g_w4_rowsplit) {                     // tools A/B: the row-split K loop
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<NT, 64, MT, MASKED, SPLITK>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-        return VLB_ERR_LAUNCH;
-      hipLaunchKernelGGL((gemm_w4_kernel<NT, 64, MT, MASKED, SPLITK>), dim3(a.grid), dim3(256), LDS, s, a);
-      VLB_LAUNCH_CHECK();
-      return VLB_OK;
-    }
-  }
-#endif
   hipLaunchKernelGGL((gemm_w4_kernel<NT, ABL, MT, MASKED, SPLITK>), dim3(a.grid), dim3(256), LDS, s, a);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
-
-#ifdef VLB_TOOLS
-// ---- stream-K launch (see gemm_w4_kernel).  TOOLS BUILD ONLY: built and measured in round 4, 1.4-2x SLOWER than
-// the round + tail plans on every ragged shape of the LoRA step - equal-length iteration ranges put the 256 CUs at different
-// K offsets of their tiles, so the CUs that share an A or W panel no longer read the same K-slice at the same time, the per-XCD
-// L2 stops serving the re-reads, and the launch runs at the fabric's bandwidth instead of the matrix pipe's rate.
-// Workspace = 256 slabs of one 256x256 fp32 tile + 256 8-byte flags behind them.
-// A flag is "raised" when it holds (magic << 32 | call number): nothing has to be zeroed, and a stale or uninitialised flag
-// cannot match.  The timeout word lives in pinned host memory (one per process): a launch that gave up waiting sets it, and
-// every later GEMM call fails loudly instead of returning wrong numbers.
-constexpr int64_t SK_SLAB_BYTES = 256ll * 256 * 256 * 4;
-constexpr int64_t SK_FLAG_BYTES = 256 * 8;
-inline int* sk_err_word() {
-  static int* w = [] {
-    int* q = nullptr;
-    if (hipHostMalloc(reinterpret_cast<void**>(&q), 64, hipHostMallocMapped) != hipSuccess || !q) return (int*)nullptr;
-    *q = 0;
-    return q;
-  }();
-  return w;
-}
-inline unsigned long long sk_next_want() {
-  static std::atomic<unsigned int> calls{0};
-  return (0x56C4B57Bull << 32) | (unsigned long long)(++calls);
-}
-template <bool MASKED>
-int launch_w4_streamk(GemmArgs a, int tiles_m, int tiles_n, int nk_all, void* ws, hipStream_t s) {
-  a.tiles_m = tiles_m; a.tiles_n = tiles_n; a.tile0 = 0; a.split_n = 1; a.k_splits = 0; a.tail_tiles = 0; a.grid = 256;
-  a.ws = (float*)ws;
-  a.sk_total = tiles_m * tiles_n * nk_all;
-  a.sk_flags = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(ws) + SK_SLAB_BYTES);
-  a.sk_want = sk_next_want();
-  a.sk_err = sk_err_word();
-  return launch_w4<8, 256, 8, MASKED, false>(a, s);
-}
-#endif
 
 // partial last wave as a split-K pair of launches: a = the launch of the tail's parent tiles (tile0, tail_tiles,
 // k_splits, ws set by the caller)
@@ -1627,33 +908,23 @@ int launch_w4_splitk(GemmArgs& a, hipStream_t s) {
 }
 
 // Kernel selection.  The product library (libvlb.so) is built WITHOUT VLB_TOOLS: the selection below is a
-// compile-time constant, no ablation / superseded kernel is instantiated and no switch is exported.
-// `make tools` builds libvlb_tools.so with -DVLB_TOOLS for tools/bench_gemm_variants.py & co (A/B and timing-only
-// ablations whose results are wrong by construction); nothing under phantom_vlb_amd/, bench.py or tests/ loads it.
+// compile-time constant, no ablation is instantiated and no switch is exported.
+// `make tools` builds libvlb_tools.so with -DVLB_TOOLS for tools/bench_gemm_variants.py & co: timing-only ablations of
+// the product kernels (results wrong by construction) and switches that force one of the planner's or the router's
+// own choices; nothing under phantom_vlb_amd/, bench.py or tests/ loads it.
 #ifdef VLB_TOOLS
 #define VLB_TUNABLE
 #else
 #define VLB_TUNABLE constexpr
 #endif
-VLB_TUNABLE int g_variant = 3;      // 0: lock-step double buffer, 1: ping-pong wave groups, 2: four-wave 128x128 blocks,
+VLB_TUNABLE int g_variant = 3;      // 1: ping-pong wave groups, 2: four-wave 128x128 blocks,
                                     // 3 (default): four-wave kernel for long K (>= 4096), ping-pong otherwise, 192-row tiles
                                     // when the cost model prefers them; 5 (A/B): like 3 but always 192-row tiles for long K
 VLB_TUNABLE int g_force_tile = 0;   // 0: heuristic, 1: 256x256, 2: 256x128 (tuning only)
 VLB_TUNABLE int g_tail_split = 1;   // split a mostly idle last wave of tiles into 256x128 tiles
 VLB_TUNABLE int g_tile_order = 3;   // GemmArgs::order: bit 0 column bands of 8, bit 1 XCD chunks dealt per round, bit 2 16x16 rounds (A/B: variant bits 10-12 XOR 3)
 VLB_TUNABLE int g_order_auto = 1;   // pick_order's shape rule (A/B: variant bit 13 disables it)
-VLB_TUNABLE int g_stagger = 0;      // tools: start delay (10-ns ticks) of half the first-round workgroups (timing experiment)
 VLB_TUNABLE int g_tail_splitk = 1;  // ... or, when the caller passes a workspace, along K (A/B: variant bit 9 disables)
-#ifdef VLB_TOOLS
-int g_streamk = 0;                  // tools: 1 = ragged multi-round outputs as ONE stream-K launch (vlb_gemm_set_streamk; measured slower, see launch_w4_streamk)
-// true when the shape should run as ONE stream-K launch of 256-row tiles: more than one round, not a whole number of rounds,
-// few enough rounds that the ragged end matters (>= 8 full rounds: the round + tail plans lose < 2 %), every segment long enough
-inline bool sk_wanted(int tiles, int nk_all, int act, bool ws_ok) {
-  return g_streamk && ws_ok && sk_err_word() && act != VLB_ACT_SWIGLU_PAIR && tiles > 256 && tiles % 256 != 0 && tiles < 8 * 256 &&
-         nk_all >= 16;
-}
-#endif
-
 // Tile order for a shape.  The order decides which operand is swept once and which is re-read once per band, i.e. which
 // one has to come back out of the 256 MB Infinity Cache: order 3 (column bands: W once, A re-read per band) unless A is the
 // larger operand AND too large to stay cached (> 128 MB), then order 2 (row bands dealt across the XCDs: A once, W re-read).
@@ -1709,14 +980,6 @@ int launch_pp(GemmArgs& a, hipStream_t s, int lds) {
 template <int BM, int BN, int WM, int WN>
 int launch_tile(GemmArgs& a, hipStream_t s) {
   constexpr int LDS = 2 * (BM + BN) * ROW_BYTES;
-#ifdef VLB_TOOLS      // the lock-step kernel (variant 0) only exists in the tools build
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tile_kernel<BM, BN, WM, WN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-  if (attr != hipSuccess) {
-    vlb_set_error("gemm: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr));
-    return VLB_ERR_LAUNCH;
-  }
-#endif
   if (a.grid == 0) {          // plain launch: the whole GEMM with BM x BN tiles
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = a.N / BN;
@@ -1758,9 +1021,7 @@ int launch_tile(GemmArgs& a, hipStream_t s) {
     }
     if (g_variant == 2 || g_variant == 3 || g_variant == 4 || g_variant == 5 || g_variant == 6 || g_variant >= 0x20) return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
   }
-  if (g_variant == 1 || (g_variant == 0 && a.act == VLB_ACT_SWIGLU_PAIR)) {
-    return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
-  }
+  if (g_variant == 1) return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
   constexpr int T = (BM + BN) / 64;     // LDS-DMA instructions per thread per K-tile
   if constexpr (BM == 256 && BN == 256) {   // timing-only ablations of the 256x256 kernel (wrong results!)
     if (g_variant == 0x11) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 1>(a, s, LDS);
@@ -1771,13 +1032,8 @@ int launch_tile(GemmArgs& a, hipStream_t s) {
     if (g_variant == 0x16) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 6>(a, s, LDS);
   }
   if (g_variant >= 0x10) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0>(a, s, LDS);   // ablations exist for 256x256 only
-  if (g_variant != 0) {
-    vlb_set_error("gemm: unknown kernel variant %d", g_variant);
-    return VLB_ERR_INVALID;
-  }
-  hipLaunchKernelGGL((gemm_tile_kernel<BM, BN, WM, WN>), dim3(a.grid), dim3(512), LDS, s, a);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  vlb_set_error("gemm: unknown kernel variant %d", g_variant);
+  return VLB_ERR_INVALID;
 #endif
 }
 
@@ -1823,11 +1079,7 @@ extern "C" int vlb_gemm_plan(int M, int N, int K, int K2, int with_workspace) {
   return (use192 ? 192 : 256) * 1000 + t.mode * 100 + t.splits;
 }
 
-#ifdef VLB_TOOLS
-extern "C" int64_t vlb_gemm_workspace_bytes(void) { return SK_SLAB_BYTES + SK_FLAG_BYTES; }   // + the stream-K experiment's flags
-#else
 extern "C" int64_t vlb_gemm_workspace_bytes(void) { return 256ll * 256 * 256 * 4; }   // <= 256 work items x one 256x256 fp32 tile
-#endif
 
 extern "C" int vlb_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                              const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
@@ -1881,7 +1133,6 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, void* C, in
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.lda2 = lda2; a.ldw2 = ldw2;
   a.act = act; a.tiles_m = 0; a.tiles_n = 0; a.tile0 = 0; a.split_n = 1; a.grid = 0; a.drop_thresh = 0; a.drop_key = 0; a.drop_scale = 1.f;
   a.ws = nullptr; a.k_splits = 0; a.tail_tiles = 0; a.order = pick_order(M, N, K); a.aux = (bf16*)aux; a.ldaux = ldaux;
-  a.stagger = g_stagger;
   a.wide = ((uintptr_t)C % 16) == 0 && ldc % 8 == 0 && (!aux || (((uintptr_t)aux % 16) == 0 && ldaux % 8 == 0 && (N / 2) % 8 == 0));
   hipStream_t s = as_stream(stream);
   const bool vec_ok = (ldc % 4 == 0) && (!residual || ldr % 4 == 0) && (!aux || (ldaux % 4 == 0 && (N / 2) % 4 == 0)) &&
@@ -1908,11 +1159,6 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, void* C, in
       const bool w4 = (g_variant == 3 || g_variant == 5 || g_variant == 6 || (g_variant >= 0x30 && g_variant < 0x40)) && fits32 && K + K2 >= 4096;    // 6 (A/B): never 192-row tiles
 #else
       const bool w4 = (g_variant == 3 || g_variant == 5) && fits32 && K + K2 >= 4096;      // four-wave kernel shapes
-#endif
-#ifdef VLB_TOOLS
-      // tools A/B: ragged multi-round output as ONE stream-K launch of 256-row tiles instead of rounds + a re-cut / split-K tail or 192-row tiles
-      if (w4 && g_force_tile == 0 && g_variant == 3 && K % 64 == 0 && K2 % 64 == 0 && sk_wanted(tiles, (K + K2) / 64, act, ws_ok))
-        return launch_w4_streamk<false>(a, tm, tn, (K + K2) / 64, ws, s);
 #endif
       const int tm192 = (M + 191) / 192, tiles192 = tm192 * tn;
       TailPlan p256, p192;
@@ -2031,7 +1277,7 @@ static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void
   a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.lda2 = lda2; a.ldw2 = ldw2;
   a.act = act; a.tiles_m = 0; a.tiles_n = 0; a.tile0 = 0; a.split_n = 1; a.grid = 0;
   a.ws = nullptr; a.k_splits = 0; a.tail_tiles = 0; a.order = pick_order(M, N, K); a.aux = nullptr; a.ldaux = 0;
-  a.wide = 1; a.stagger = g_stagger;
+  a.wide = 1;
   uint32_t t = (uint32_t)(drop_p * 65536.f + 0.5f);
   a.drop_thresh = t > 65535u ? 65535u : t;
   a.drop_key = lowbias32_h(seed);
@@ -2042,10 +1288,6 @@ static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void
   TailPlan p256, p192;
   // (no split-K for the 256-row masked kernel: with 64 accumulator tiles + the mask temporaries the register
   // allocator starts rotating accumulator tuples behind the asm MFMAs; 192-row tiles are fine)
-#ifdef VLB_TOOLS
-  if (g_force_tile == 0 && sk_wanted(((M + 255) / 256) * tn, (K + 64) / 64, act, ws_ok))
-    return launch_w4_streamk<true>(a, (M + 255) / 256, tn, (K + 64) / 64, ws, s);
-#endif
   bool use192 = plan_rows(M, N, K + 64, ws_ok, p256, p192, false);
 #ifdef VLB_TOOLS
   if (g_force_tile == 3) use192 = false;      // A/B only: force 256- / 192-row tiles for the masked-pair kernel
@@ -2071,11 +1313,6 @@ static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void
 
 #ifdef VLB_TOOLS
 // tuning hooks, libvlb_tools.so only: kernel variant / forced tile
-extern "C" void vlb_gemm_set_stagger(int ticks) { g_stagger = ticks; }
-extern "C" void vlb_gemm_set_streamk(int on) { g_streamk = on; }
-extern "C" void vlb_gemm_set_rowsplit(int on) { g_w4_rowsplit = on; }
-extern "C" void vlb_gemm_set_persist(int on) { g_w4_persist = on; }
-extern "C" void vlb_gemm_set_wd(int on) { g_wd = on; }
 extern "C" void vlb_gemm_set_variant(int variant, int force_tile) {
   g_variant = variant & 0xff;     // 3 = default (auto)
   g_force_tile = force_tile;

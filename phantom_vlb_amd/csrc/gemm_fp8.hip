@@ -39,191 +39,10 @@ __device__ __forceinline__ void glds4f(const void* g, void* l) {
 }
 
 struct Fp8Launch { int tile0, split_n; };       // first tile id of this launch; 1 = whole tiles, 2 = column halves
-#ifdef VLB_TOOLS          // the read-phase kernel of rounds 1-2, kept in the tools build for A/B (tools/ab_fp8_variants.py)
-// 256 threads = 2(M) x 2(N) waves, one per SIMD with the full 512-register budget; wave block 128 x 128 = 64
-// accumulator tiles.  Per K-tile (128 bytes of K per row) a wave reads all its fragments (32 ds_read_b128) and scale
-// words into registers, the workgroup passes a barrier, and the stage just read is immediately refilled with tile
-// kt+2 by LDS-DMA while the 64 MFMAs of tile kt run - every DMA has one whole iteration plus an MFMA phase to land
-// (counted vmcnt, never 0 inside the loop).  Scales travel through LDS as well (global_load_lds_dword, one u32 = the
-// four block scales of a row per K-tile), so the loop holds no register-destination global load for the compiler to
-// drain the DMA queue on.
-// NT = 8: 256 x 256 tile (wave block 128 x 128).  NT = 4: 256 x 128 tile (wave block 128 x 64) - the partial last
-// wave of tiles of a GEMM is re-cut into these halves so its work spreads over twice as many CUs.
 
-template <int NT>
-__global__ __launch_bounds__(256, 1) void gemm_mxfp8_kernel(Fp8Args p, Fp8Launch L) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int A_BYTES = 256 * FROW, WROWS = 32 * NT, W_BYTES = WROWS * FROW;
-  constexpr int SA_OFF = A_BYTES + W_BYTES, SW_OFF = SA_OFF + 256 * 4;
-  constexpr int STAGE = SW_OFF + 256 * 4;                    // A image + W image + A scale words + W scale words
-  constexpr int VM = 8 + NT + 2;                             // LDS-DMA instructions per wave per K-tile
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  // ---- work item -> tile (same order as gemm.hip, tile order 3): blocks b and b+8 share an XCD; every round of 256 work
-  // items is dealt to the XCDs in chunks of 32 (a partial last round in contiguous runs), and tiles are walked in column
-  // bands of 8 with the rows inside a band - a chunk is 4 rows x 8 columns, a chip-wide round sweeps the row panels of A
-  // against the same 8 W panels, which the XCDs then share through the Infinity Cache
-  int w;
-  {
-    const int n = gridDim.x, xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const int T = n >> 8, tr = idx >> 5;
-    if (tr < T) {
-      w = (tr << 8) + (xcd << 5) + (idx & 31);
-    } else {
-      const int base = T << 8, nn = n - base, q = nn >> 3, r = nn & 7;
-      w = base + (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (idx - (T << 5));
-    }
-  }
-  const int t = L.tile0 + w / L.split_n, half = w % L.split_n;
-  const int band = t / (8 * p.tiles_m), c0 = band * 8, within = t - band * 8 * p.tiles_m;
-  const int band_cols = min(8, p.tiles_n - c0);
-  const int tm = within / band_cols, tn = c0 + within % band_cols;
-  const int m0 = tm * 256, n0 = tn * 256 + half * 128;
-  const int nk = p.K / FBK;
-
-  // ---- LDS-DMA sources.  Data: a wave instruction writes 1 KiB = 8 rows x 128 B; lane -> (row, slot); source chunk =
-  // slot ^ swz(row).  Wave w owns A rows 64w..64w+63 (8 pieces) and W rows 8*NT*w.. (NT pieces).  Scales: lane l of
-  // wave w moves the u32 of A row 64w + l and of W row (64w + l) mod WROWS (for NT = 4 the upper waves repeat rows
-  // into an unused part of the scale area: every wave issues the same number of DMA instructions).
-  const char* srcA[8]; const char* srcW[NT];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int r = wave * 64 + j * 8 + (lane >> 3), s = lane & 7;
-    srcA[j] = reinterpret_cast<const char*>(p.A) + (int64_t)min(m0 + r, p.M - 1) * p.lda + (s ^ ((r >> 1) & 7)) * 16;
-  }
-#pragma unroll
-  for (int j = 0; j < NT; ++j) {
-    const int r = wave * 8 * NT + j * 8 + (lane >> 3), s = lane & 7;
-    srcW[j] = reinterpret_cast<const char*>(p.W) + (int64_t)(n0 + r) * p.ldw + (s ^ ((r >> 1) & 7)) * 16;
-  }
-  const char* srcSA = reinterpret_cast<const char*>(p.sA) + (int64_t)min(m0 + wave * 64 + lane, p.M - 1) * p.ldsa;
-  const char* srcSW = reinterpret_cast<const char*>(p.sW) + (int64_t)(n0 + (wave * 64 + lane) % WROWS) * p.ldsw;
-  auto stage = [&](int st, int kt) {
-    char* base = smem + st * STAGE;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) glds16f(srcA[j] + (int64_t)kt * FBK, base + (wave * 8 + j) * 1024);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) glds16f(srcW[j] + (int64_t)kt * FBK, base + A_BYTES + (wave * NT + j) * 1024);
-    glds4f(srcSA + kt * 4, base + SA_OFF + wave * 256);
-    glds4f(srcSW + kt * 4, base + SW_OFF + wave * 256);
-  };
-  const int fr = lane & 15, g = lane >> 4;
-  f32x4 acc[NT][8];
-#pragma unroll
-  for (int j = 0; j < NT; ++j)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-#define VLB_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-  stage(0, 0);
-  if (nk > 1) stage(1, 1);
-  if (nk > 1) VLB_VMCNT(VM); else VLB_VMCNT(0);
-  __builtin_amdgcn_s_barrier();
-  // One K-tile.  MORE: tile kt+2 exists and is issued into the stage this tile was read from.  After the barrier the
-  // LDS-DMA pieces of tile kt+2 are issued two or three at a time in front of each row of NT MFMAs (sched_barrier fences
-  // pin that order), so their issue cost (60-100 cycles apiece) hides in the shadow of the previous row's MFMAs instead
-  // of standing as one burst in front of the whole MFMA phase.
-  auto tile = [&](int kt, auto more) {
-    constexpr bool MORE = decltype(more)::value;
-    const char* sb = smem + (kt & 1) * STAGE;
-    char* nb = smem + (kt & 1) * STAGE;                    // stage refilled with tile kt+2
-    i32x8 wf[NT], af[8];
-    int swb[NT], sab[8];
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int r = wn * 16 * NT + j * 16 + fr;
-      const i32x4 lo = *reinterpret_cast<const i32x4*>(sb + A_BYTES + f_off(r, g));
-      const i32x4 hi = *reinterpret_cast<const i32x4*>(sb + A_BYTES + f_off(r, 4 + g));
-      wf[j] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      swb[j] = *reinterpret_cast<const int*>(sb + SW_OFF + r * 4);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = wm * 128 + i * 16 + fr;
-      const i32x4 lo = *reinterpret_cast<const i32x4*>(sb + f_off(r, g));
-      const i32x4 hi = *reinterpret_cast<const i32x4*>(sb + f_off(r, 4 + g));
-      af[i] = i32x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      sab[i] = *reinterpret_cast<const int*>(sb + SA_OFF + r * 4);
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();                          // every wave holds tile kt in registers: its stage is free
-    // Both E8M0 scales travel in ONE register: byte 0 = the MFMA-A operand's (the W rows), byte 1 = the MFMA-B
-    // operand's (the activation rows), selected by op_sel 0 / 1.  Measured on gfx950 with ROCm 7.2
-    // (tools/probe_mfma_scale.py): the instruction takes both scale bytes from the register in the scale_b position
-    // and ignores the scale_a register; passing the same packed register in both positions is right under either reading.
-#pragma unroll
-    for (int j = 0; j < NT; ++j) swb[j] = (swb[j] >> (8 * g)) & 0xff;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) sab[i] = ((sab[i] >> (8 * g)) & 0xff) << 8;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if constexpr (MORE) {
-        const int64_t ko = (int64_t)(kt + 2) * FBK;
-        glds16f(srcA[i] + ko, nb + (wave * 8 + i) * 1024);
-        if (i < NT) glds16f(srcW[i] + ko, nb + A_BYTES + (wave * NT + i) * 1024);
-        if (i == 0) glds4f(srcSA + (kt + 2) * 4, nb + SA_OFF + wave * 256);
-        if (i == 1) glds4f(srcSW + (kt + 2) * 4, nb + SW_OFF + wave * 256);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int j = 0; j < NT; ++j) {
-        const int sc = swb[j] | sab[i];
-        acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j], af[i], acc[j][i], 0, 0, 0, sc, 1, sc);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    // tile kt+1 must have landed before the next iteration reads it: everything older than tile kt+2's pieces
-    if constexpr (MORE) VLB_VMCNT(VM); else VLB_VMCNT(0);
-    __builtin_amdgcn_s_barrier();
-  };
-  int kt = 0;
-  for (; kt + 2 < nk; ++kt) tile(kt, std::true_type{});
-  for (; kt < nk; ++kt) tile(kt, std::false_type{});
-#undef VLB_VMCNT
-  // ---- epilogue: lane holds, for tile (j, i): output row m = .. + fr, columns n = .. + 4g + {0,1,2,3}
-  // (C rows 16-byte aligned: adjacent fragments paired into 16-byte stores, store_pair16 in common.hpp; else 8-byte pieces)
-  auto value = [&](const f32x4& a, int m, int n) {
-    f32x4 v = a;
-    if (p.residual) {
-      const bf16x4 r = *reinterpret_cast<const bf16x4*>(p.residual + (int64_t)m * p.ldr + n);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] += (float)r[e];
-    }
-    bf16x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = (bf16)v[e];
-    return o;
-  };
-  const bool wide = ((uintptr_t)p.C % 16) == 0 && p.ldc % 8 == 0;
-  if (wide) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + wm * 128 + i * 16 + fr;
-      if (m >= p.M) continue;
-#pragma unroll
-      for (int j = 0; j < NT; j += 2) {
-        const int n = n0 + wn * 16 * NT + j * 16 + 4 * g;
-        store_pair16(p.C + (int64_t)m * p.ldc, n, value(acc[j][i], m, n), value(acc[j + 1][i], m, n + 16), g);
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int m = m0 + wm * 128 + i * 16 + fr;
-    if (m >= p.M) continue;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-      const int n = n0 + wn * 16 * NT + j * 16 + 4 * g;
-      *reinterpret_cast<bf16x4*>(p.C + (int64_t)m * p.ldc + n) = value(acc[j][i], m, n);
-    }
-  }
-}
-#endif
-
-// ---------------------------------------------------------------- pipelined variant (round 3)
-// Same tile, LDS image and operand layout as gemm_mxfp8_kernel, but no fragment-read phase in front of the MFMAs: the 64
+// ---------------------------------------------------------------- pipelined kernel (round 3)
+// 256 threads = 2(M) x 2(N) waves, one per SIMD with the full 512-register budget.  No fragment-read phase in front of the
+// MFMAs (the read-phase kernel of rounds 1-2 had one): the 64
 // MFMAs of a K-tile run as two blocks of NT groups, group j = W fragment j against activation rows 0..3 (block 1) or 4..7
 // (block 2), and every ds_read is issued under MFMAs that do not need it:
 //   block 1 of tile kt: reads activation fragments 4..7 of tile kt; after barrier S (every wave holds all of W(kt)) the W
@@ -443,46 +262,19 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_pipe_kernel(Fp8Args p, Fp8L
 
 #ifdef VLB_TOOLS
 int g_fp8_rows = 0;                 // tools: 0 = planner, 256 / 192 = forced tile height
-int g_fp8_variant = 1;              // tools: 0 = read-phase kernel (rounds 1-2), 1 = pipelined kernel
-#else
-constexpr int g_fp8_variant = 1;
 #endif
 
+// NT = 8: 256 (or 192) x 256 tiles; NT = 4: 256 (or 192) x 128 halves for the re-cut partial last round.  S_AT = 1: barrier
+// S in front of MFMA group 1 (the only value used; a template parameter so that the kernel names stay stable).
 template <int NT, int MT = 8>
 int launch_fp8(const Fp8Args& a, Fp8Launch L, int grid, hipStream_t st) {
   constexpr int LDS = 2 * (32 * MT * FROW + 32 * NT * FROW + 2 * 256 * 4);
-  if constexpr (MT != 8) {
-    static const hipError_t attr6 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_pipe_kernel<NT, 1, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (attr6 != hipSuccess) { vlb_set_error("gemm_mxfp8: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr6)); return VLB_ERR_LAUNCH; }
-    hipLaunchKernelGGL((gemm_mxfp8_pipe_kernel<NT, 1, MT>), dim3(grid), dim3(256), LDS, st, a, L);
-    VLB_LAUNCH_CHECK();
-    return VLB_OK;
-  }
-#ifdef VLB_TOOLS
-  if (g_fp8_variant == 2 || g_fp8_variant == 3) {            // tools: barrier S in front of MFMA group 2 / 0 instead of 1
-    auto k = g_fp8_variant == 2 ? &gemm_mxfp8_pipe_kernel<NT, 2> : &gemm_mxfp8_pipe_kernel<NT, 0>;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return VLB_ERR_LAUNCH;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(256), LDS, st, a, L);
-    VLB_LAUNCH_CHECK();
-    return VLB_OK;
-  }
-#endif
-  if (g_fp8_variant == 1) {
-    static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_pipe_kernel<NT, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (attr1 != hipSuccess) { vlb_set_error("gemm_mxfp8: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr1)); return VLB_ERR_LAUNCH; }
-    hipLaunchKernelGGL((gemm_mxfp8_pipe_kernel<NT, 1>), dim3(grid), dim3(256), LDS, st, a, L);
-    VLB_LAUNCH_CHECK();
-    return VLB_OK;
-  }
-#ifdef VLB_TOOLS
-  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+  // once per process and kernel; a function-local static's initialisation is thread-safe (C++11)
+  static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_pipe_kernel<NT, 1, MT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
   if (attr != hipSuccess) { vlb_set_error("gemm_mxfp8: cannot reserve %d bytes of LDS: %s", LDS, hipGetErrorString(attr)); return VLB_ERR_LAUNCH; }
-  hipLaunchKernelGGL((gemm_mxfp8_kernel<NT>), dim3(grid), dim3(256), LDS, st, a, L);
+  hipLaunchKernelGGL((gemm_mxfp8_pipe_kernel<NT, 1, MT>), dim3(grid), dim3(256), LDS, st, a, L);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
-#else
-  return VLB_ERR_LAUNCH;
-#endif
 }
 
 // ---------------------------------------------------------------- bf16 -> MX fp8 (e4m3 + E8M0 block scales)
@@ -675,7 +467,7 @@ __global__ __launch_bounds__(256) void quantize_dual_mxfp8_kernel(const bf16* __
 }  // namespace
 
 #ifdef VLB_TOOLS
-extern "C" void vlb_gemm_mxfp8_set_variant(int v) { g_fp8_variant = v & 0xff; g_fp8_rows = v >> 8; }     // rows in bits 8.. (0: planner)
+extern "C" void vlb_gemm_mxfp8_set_variant(int v) { g_fp8_rows = v >> 8; }     // forced tile height in bits 8.. (0: planner)
 // tools build only: ONE v_mfma_scale_f32_16x16x128_f8f6f4 on caller-given per-lane registers (layout experiments)
 namespace {
 template <int OA, int OB>
@@ -764,7 +556,6 @@ extern "C" int vlb_gemm_mxfp8(const void* Aq, int lda, const void* sA, int ldsa,
 #ifdef VLB_TOOLS
   if (g_fp8_rows == 256) use192 = false;
   if (g_fp8_rows == 192) use192 = true;
-  if (g_fp8_variant != 1) use192 = false;
 #endif
   const int rows = use192 ? 192 : 256, tiles = use192 ? t192 : t256, rem = use192 ? r192 : r256;
   const bool halves = use192 ? h192 : h256;

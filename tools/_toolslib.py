@@ -1,5 +1,6 @@
-"""Import FIRST in a tuning script: points phantom_vlb_amd at libvlb_tools.so (the -DVLB_TOOLS build: kernel-variant
-switches, timing-only ablations with WRONG results, superseded kernels kept for A/B), building it if needed."""
+"""Import FIRST in a tuning script: points phantom_vlb_amd at libvlb_tools.so (the -DVLB_TOOLS build: timing-only ablations
+of the product kernels, with WRONG results, and switches that force the product's own planner / routing choices), building
+it if needed."""
 import os
 import subprocess
 
