@@ -764,6 +764,9 @@ extern "C" int vlb_attention_bwd(const void* q, int ldq, const void* k, int ldk,
   VLB_REQUIRE(B > 0 && S > 0 && Hq > 0 && Hkv > 0 && Hq % Hkv == 0, "attention_bwd: bad shape");
   VLB_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && lddo % 8 == 0 && lddq % 8 == 0 &&
                   lddk % 4 == 0 && lddv % 4 == 0, "attention_bwd: strides must keep vector alignment");
+  // every kernel below reads q / k / v / out / dout rows in 16-byte vectors and writes dq in 8-byte ones
+  VLB_REQUIRE(((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)dout) % 16) == 0) &&
+                  ((uintptr_t)dq % 8 == 0), "attention_bwd: misaligned pointer");
   hipStream_t st = as_stream(stream);
   const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;     // packed: sum of clip lengths
   VLB_REQUIRE(rows > 0 && rows <= (int64_t)B * S, "attention_bwd: total_rows=%d out of range", total_rows);

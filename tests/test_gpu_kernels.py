@@ -231,7 +231,9 @@ def test_attention_fwd(dev, B, S, Hq, Hkv, D, causal, masked):
     if mask is not None:
         allow = allow & mask.bool()[:, None, None, :]
     lse_ref = torch.logsumexp(s.masked_fill(~allow, float("-inf")), -1)
-    assert (lse.cpu() - lse_ref).abs().max() < 2e-2
+    # lse = m.scale + log(l) in fp32 on both sides: a few fp32 ulps of |lse| plus the log of an fp32 sum (derived, not
+    # measured; an lse off by e moves every P by a factor exp(e))
+    assert ((lse.cpu() - lse_ref).abs() <= 1e-4 * (1 + lse_ref.abs())).all(), float((lse.cpu() - lse_ref).abs().max())
 
 
 def test_attention_softmax_rescale_branch(dev):
