@@ -345,6 +345,12 @@ int vlb_grad_sumsq(const float* g, int64_t n, float* sumsq, float* ws, void* str
 int vlb_adamw_step(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
                    float max_norm, void* stream);
+/* gradient accumulation over a flat store: acc[i] = first ? g[i] : acc[i] + g[i]  (fp32 accumulator; `first` replaces a
+ * memset).  Any n > 0; acc and g 16-byte aligned (the bf16 g: 8-byte).  With sumsq != NULL the same pass also adds
+ * sum(acc^2) of the RESULT to sumsq[0] through ws (vlb_sumsq_ws_floats() floats): bit-identical to vlb_grad_sumsq on the
+ * finished accumulator, so the last micro-batch of a window needs no separate norm pass. */
+int vlb_grad_accum(float* acc, const float* g, int64_t n, int first, float* sumsq, float* ws, void* stream);
+int vlb_grad_accum_bf16(float* acc, const void* g_bf16, int64_t n, int first, float* sumsq, float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Full-parameter fine-tuning (BASELINE configs[4]; litmodule :86-99 with freeze_backbone=False, use_lora=False:

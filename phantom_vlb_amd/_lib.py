@@ -72,6 +72,8 @@ SIGNATURES = {
     "vlb_sumsq_ws_floats": [],
     "vlb_grad_sumsq": [P, L, P, P, P],
     "vlb_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, F, P],
+    "vlb_grad_accum": [P, P, L, I, P, P, P],
+    "vlb_grad_accum_bf16": [P, P, L, I, P, P, P],
     "vlb_dropout_keep_scale": [P, L, F, ctypes.c_uint32, P],
     "vlb_transpose_pad": [P, I, P, I, I, I, I, P],
     "vlb_norm_bwd_ws_floats": [I, I],

@@ -600,9 +600,98 @@ __global__ void adamw_kernel(float* __restrict__ p, bf16* __restrict__ pb, const
   }
 }
 
+// ---- gradient accumulation (accumulate_grad_batches > 1): acc = first ? g : acc + g over a flat store, fp32 or bf16 g.
+// One 16-byte lane access per fp32 array and trip (8 bytes for a bf16 g), kAccumUnroll independent trips issued before the
+// first use so that a thread keeps up to 8 loads in flight.  n is arbitrary: the last n % 4 elements are done one by one
+// by the lane whose turn they are.
+// SUMSQ: the same pass also leaves the clip norm's partial sums of the RESULT in `part`, laid out so that the total is
+// bit-identical to vlb_grad_sumsq on the finished accumulator.  sumsq_kernel's thread t of S = 256 * nb sums the squares
+// of elements t, t + S, t + 2S ... in that order; here lane u of S / 4 lanes owns the four chains 4u .. 4u + 3 (one
+// f32x4 per trip, same order), so a 64-lane wave holds exactly the 256 chains of one sumsq_kernel block and folds them
+// in block_sum's order: the xor butterfly 32, 16, .. 1 inside each group of 64 chains (here: lanes 8, 4, 2, 1, then
+// components 2, 1), then the four groups in sequence.  Launched with 64-thread blocks, one per sumsq_kernel block.
+constexpr int kAccumUnroll = 4;
+__device__ __forceinline__ f32x4 ld_grad4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 ld_grad4(const bf16* p) {
+  const bf16x4 v = *reinterpret_cast<const bf16x4*>(p);
+  return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
+template <typename G, bool SUMSQ>
+__global__ __launch_bounds__(256) void grad_accum_kernel(float* __restrict__ acc, const G* __restrict__ g, int64_t n, int first,
+                                                         float* __restrict__ part) {
+  const int64_t nv = n >> 2;                                  // whole 4-element vectors
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int64_t q = tid; q < nv; q += kAccumUnroll * stride) {
+    f32x4 a[kAccumUnroll], b[kAccumUnroll];
+#pragma unroll
+    for (int u = 0; u < kAccumUnroll; ++u) {
+      const int64_t j = q + u * stride;
+      if (j < nv) {
+        b[u] = ld_grad4(g + j * 4);
+        if (!first) a[u] = *reinterpret_cast<const f32x4*>(acc + j * 4);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kAccumUnroll; ++u) {
+      const int64_t j = q + u * stride;
+      if (j < nv) {
+        f32x4 r = b[u];
+        if (!first) r = a[u] + b[u];
+        *reinterpret_cast<f32x4*>(acc + j * 4) = r;
+        if (SUMSQ) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) s[c] += r[c] * r[c];
+        }
+      }
+    }
+  }
+  const int rem = (int)(n & 3);
+  if (rem && tid == nv % stride) {                            // the vector after the last whole one is this lane's next trip
+    for (int c = 0; c < rem; ++c) {
+      const int64_t e = nv * 4 + c;
+      float r = (float)g[e];
+      if (!first) r = acc[e] + r;
+      acc[e] = r;
+      if (SUMSQ) s[c] += r * r;
+    }
+  }
+  if (SUMSQ) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) s[c] += __shfl_xor(s[c], o, 64);
+    }
+    const float grp = (s[0] + s[2]) + (s[1] + s[3]);          // lanes 16w .. 16w + 15 hold group w's sum
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) t += __shfl(grp, 16 * w, 64);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+  }
+}
+
 inline int grid_for(int64_t n, int block) {
   int64_t b = (n + block - 1) / block;
   return (int)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
+}
+
+template <typename G>
+int grad_accum_launch(float* acc, const G* g, int64_t n, int first, float* sumsq, float* ws, void* stream) {
+  hipStream_t st = as_stream(stream);
+  if (!sumsq) {
+    hipLaunchKernelGGL((grad_accum_kernel<G, false>), dim3(grid_for((n + 3) / 4, 256 * kAccumUnroll)), dim3(256), 0, st, acc, g, n, first,
+                       (float*)nullptr);
+    VLB_LAUNCH_CHECK();
+    return VLB_OK;
+  }
+  int64_t nb64 = (n + 1023) / 1024;                            // vlb_grad_sumsq's block count: one wave here per block there
+  const int nb = (int)(nb64 > kSumsqBlocks ? kSumsqBlocks : nb64);
+  hipLaunchKernelGGL((grad_accum_kernel<G, true>), dim3(nb), dim3(64), 0, st, acc, g, n, first, ws);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, ws, nb, sumsq);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
 }
 }  // namespace
 
@@ -844,4 +933,14 @@ extern "C" int vlb_adamw_step(float* master, void* param_bf16, const float* grad
                      grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, sumsq, max_norm);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
+}
+extern "C" int vlb_grad_accum(float* acc, const float* g, int64_t n, int first, float* sumsq, float* ws, void* stream) {
+  VLB_REQUIRE(n > 0 && acc && g && (sumsq == nullptr || ws) && ((uintptr_t)acc % 16) == 0 && ((uintptr_t)g % 16) == 0,
+              "grad_accum: n > 0, acc and g 16-byte aligned, ws with sumsq");
+  return grad_accum_launch<float>(acc, g, n, first, sumsq, ws, stream);
+}
+extern "C" int vlb_grad_accum_bf16(float* acc, const void* g_bf16, int64_t n, int first, float* sumsq, float* ws, void* stream) {
+  VLB_REQUIRE(n > 0 && acc && g_bf16 && (sumsq == nullptr || ws) && ((uintptr_t)acc % 16) == 0 && ((uintptr_t)g_bf16 % 8) == 0,
+              "grad_accum_bf16: n > 0, acc 16-byte and g 8-byte aligned, ws with sumsq");
+  return grad_accum_launch<bf16>(acc, (const bf16*)g_bf16, n, first, sumsq, ws, stream);
 }

@@ -83,19 +83,36 @@ class _ExplicitLoss(torch.autograd.Function):
     Lightning's automatic optimisation can call ``loss.backward()``.  The backward pass ran explicitly inside
     ``training_step`` (hand-written kernels, no autograd tape); ``backward`` here only (re-)attaches those gradient buffers as
     the Parameters' ``.grad`` - Lightning zeroes the gradients between ``training_step`` and ``backward`` - and returns no
-    autograd gradients, so nothing is accumulated twice.  The upstream gradient must be 1 (no gradient accumulation /
-    loss scaling: the reference uses neither; ``on_fit_start`` checks)."""
+    autograd gradients, so nothing is accumulated twice.  Under ``accumulate_grad_batches = k > 1`` Lightning calls
+    ``(loss / k).backward()``: the module has already applied the 1/k (``training_step`` scales the head backward, the
+    gradients never flow through autograd), so the upstream gradient must be exactly that 1/k - anything else (a loss
+    scaler, a different divisor) would silently give a differently scaled step and raises instead.  The check reads one
+    scalar back and runs for k > 1 only; at k = 1 the upstream gradient is taken to be 1, as before."""
 
     @staticmethod
     def forward(ctx, loss, module, *params):
         ctx.module = module
         ctx.n = len(params)
+        ctx.k = module.accumulate_grad_batches
         return loss.detach().clone()
 
     @staticmethod
     def backward(ctx, gout):
+        if ctx.k > 1:
+            got, want = float(gout), 1.0 / ctx.k
+            if abs(got - want) > 1e-6 * want:
+                raise ValueError(f"loss.backward() arrived with an upstream gradient of {got!r}, expected 1/accumulate_grad_batches = "
+                                 f"{want!r}: the module scales its explicit backward by 1/k itself, so the loss must be divided by "
+                                 f"k = {ctx.k} and by nothing else (no loss scaling)")
         ctx.module._attach_gradients()
         return (None, None) + (None,) * ctx.n
+
+
+def check_accumulate_grad_batches(k) -> int:
+    """``accumulate_grad_batches`` as both runners accept it: an int >= 1."""
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"accumulate_grad_batches={k!r}: an integer >= 1 is needed (1 = one optimiser step per batch)")
+    return k
 
 
 class _LinearInfo:
@@ -181,10 +198,41 @@ class VLBLitModule(_Base):
         self.world_size = 1
         self.rank = 0
         self.pack_tokens = bool(getattr(config, "pack_tokens", True))
+        self._accumulate = None         # accumulate_grad_batches when set by hand; None: the attached runner's value
+        self._micro = 0                 # position inside the current accumulation window
+        self._window_opt_step = 0       # optimiser step count the position belongs to (a step() starts a new window)
+        self.last_micro_batch = None    # runner's notice for the next training_step: it closes its window (True / False)
 
     @property
     def device(self):
         return self._device
+
+    # ------------------------------------------------------------------ gradient accumulation
+    @property
+    def accumulate_grad_batches(self) -> int:
+        """k: ``training_step`` calls per optimiser step.  Not a config field (the 16 are the reference's): it is the
+        ``accumulate_grad_batches`` of the runner that drives the module (``lightning.pytorch.Trainer`` or the built-in
+        ``trainer.Trainer``), or a value set here by a hand-written loop."""
+        if self._accumulate is not None:
+            return self._accumulate
+        tr = self.__dict__.get("_trainer") or self.__dict__.get("trainer")
+        k = getattr(tr, "accumulate_grad_batches", 1)
+        return 1 if k is None else check_accumulate_grad_batches(k)
+
+    @accumulate_grad_batches.setter
+    def accumulate_grad_batches(self, k):
+        self._accumulate = None if k is None else check_accumulate_grad_batches(k)
+
+    def check_accumulation_supported(self, k: int | None = None):
+        """k > 1 is refused where there is nowhere to accumulate: the full fine-tune under data parallelism."""
+        k = self.accumulate_grad_batches if k is None else k
+        sb = getattr(self, "sharded_backbone", None)
+        if k > 1 and sb is not None and sb.active:
+            raise ValueError(f"accumulate_grad_batches={k} with the full fine-tune under data parallelism is not supported "
+                             f"({'FULL_SHARD' if sb.full_shard else 'SHARD_GRAD_OP'}: the layers' bf16 gradient "
+                             f"{'buffers rotate' if sb.full_shard else 'shards are reduce-scattered'} every step and have nowhere to "
+                             "accumulate).  Use accumulate_grad_batches=1 and more ranks for the batch size, or train LoRA / the "
+                             "frozen-backbone head, which accumulate under data parallelism")
 
     # ------------------------------------------------------------------ model
     def configure_model(self, state_dict: dict | None = None, head_state: dict | None = None) -> None:
@@ -268,12 +316,22 @@ class VLBLitModule(_Base):
     def _attach_gradients(self):
         """``.grad`` of every trainable Parameter <- the gradient buffer the explicit backward filled (aliases, no copies)."""
         masters = dict(self._named_masters())
+        opt = getattr(self, "optimizer", None)
+        acc = opt.window_gradient(0) if opt is not None and self._window_complete() else None
         for n, p in self.trainable_named_parameters():
             if n.startswith("backbone."):
                 continue        # bf16 gradients (like the reference's bf16 parameters'): read them with self.full.flat.g_(name)
-            g = self.head.grads[n] if n in self.head.grads else self.lora.grads[n]
+            if acc is not None:             # a complete accumulation window: what the optimiser will consume is the accumulator
+                o, cnt, shp = self.flat.offsets[n]
+                g = acc[o:o + cnt].view(shp)
+            else:
+                g = self.head.grads[n] if n in self.head.grads else self.lora.grads[n]
             p.grad = g
             masters[n].grad = g             # the plain master views (head.master[n], lora.master[n]) carry it too
+
+    def _window_complete(self) -> bool:
+        k = self.accumulate_grad_batches
+        return k > 1 and (self._micro >= k or bool(self.__dict__.get("_window_closed")))
 
     def trainable_state_dict(self) -> dict:
         """Trainables on the host under their upstream / peft names and layouts (LoRA B as [out, r], rank padding
@@ -470,19 +528,40 @@ class VLBLitModule(_Base):
         self._step += 1
         if self.lora is not None:
             self.lora.rank = self.rank
+        # accumulate_grad_batches = k: micro-batch j of a window contributes (1/k) d(mse_j + l2)/dtheta - the ridge penalty counts
+        # once per optimiser step, as k backward passes of loss/k give.  Everything behind the head is linear in dhidden, so the
+        # head backward's two scales are the only place the 1/k enters.  (k = 1: scale 1/world, no accumulator, as ever.)
+        k = self.accumulate_grad_batches
+        opt = getattr(self, "optimizer", None)
+        j = last = None
+        if k > 1:
+            if opt is None:
+                raise RuntimeError("accumulate_grad_batches > 1 needs configure_optimizers() first: the optimiser owns the accumulator")
+            self.check_accumulation_supported(k)
+            if opt.step_count != self._window_opt_step:           # an optimiser step closed the previous window
+                self._micro, self._window_opt_step = 0, opt.step_count
+            j = self._micro
+            if j >= k:
+                raise RuntimeError(f"training_step #{j + 1} of a window of accumulate_grad_batches={k}: optimizer.step() is due")
+            last = (j + 1 == k) if self.last_micro_batch is None else bool(self.last_micro_batch)
+            opt.begin_micro_batch(j, last)
+        self.last_micro_batch = None
         pred, y, terms = self._common_step(batch, train=True)
         self.backbone.launch_deferred_video_tokens()         # a future batch's frozen vision side: behind this forward, under this backward
         need_dh = self.lora is not None or self.full is not None
-        inv_world = 1.0 / self.world_size
+        scale = 1.0 / (self.world_size * k)
         if self._cached_step:
-            self.head.backward_cached(loss_scale=inv_world, l2_scale=inv_world)
+            self.head.backward_cached(loss_scale=scale, l2_scale=scale)
             dh = None
         else:
-            dh = self.head.backward(need_dhidden=need_dh, loss_scale=inv_world, l2_scale=inv_world)
+            dh = self.head.backward(need_dhidden=need_dh, loss_scale=scale, l2_scale=scale)
         if self.lora is not None:
             self.lora.backward(self.backbone, dh)
         elif self.full is not None:
             self.full.backward(dh)
+        if k > 1:
+            opt.accumulate(j, last)
+            self._micro, self._window_closed = j + 1, last
         self._attach_gradients()
         self.log("train/brain_loss", terms[2])
         if _LP is None:
@@ -518,14 +597,15 @@ class VLBLitModule(_Base):
 
     def on_fit_start(self):
         """Called by a Lightning ``Trainer.fit`` (never by the built-in runner).  What the bridge does not support is
-        refused here instead of producing wrong gradients: accumulation (every step overwrites the gradient buffers) and
-        anything but ONE device - Lightning's DDP / FSDP wrappers reduce autograd gradients, and the kernels' gradients
-        never flow through autograd (``_ExplicitLoss.backward`` returns None); multi-GPU runs use the built-in runner's
-        clip-sharded data parallelism (``torchrun ... train.py``, parallel.attach_data_parallel)."""
+        refused here instead of producing wrong gradients: anything but ONE device - Lightning's DDP / FSDP wrappers reduce
+        autograd gradients, and the kernels' gradients never flow through autograd (``_ExplicitLoss.backward`` returns
+        None); multi-GPU runs use the built-in runner's clip-sharded data parallelism (``torchrun ... train.py``,
+        parallel.attach_data_parallel).  ``accumulate_grad_batches = k`` is supported: the module reads k from the Trainer,
+        scales and accumulates inside ``training_step``, and ``_ExplicitLoss.backward`` insists on Lightning's ``loss / k``.
+        (An epoch's short last window is stepped correctly too; without a notice that it closes, the optimiser runs its
+        norm pass separately instead of fused into the last accumulation.)"""
         tr = self.__dict__.get("_trainer") or self.__dict__.get("trainer")
-        if getattr(tr, "accumulate_grad_batches", 1) not in (None, 1):
-            raise ValueError("accumulate_grad_batches > 1 is not supported: every training_step overwrites the gradient buffers "
-                             "(the reference's configs do not accumulate)")
+        check_accumulate_grad_batches(getattr(tr, "accumulate_grad_batches", 1) or 1)
         world = getattr(tr, "world_size", 1) or 1
         strategy = type(getattr(tr, "strategy", None)).__name__
         if world > 1 or strategy not in ("NoneType", "SingleDeviceStrategy"):

@@ -11,6 +11,12 @@ All state lives in the flat buffers of ``flat.FlatTrainables``: one sum-of-squar
 clip+AdamW launch per step.  Under data parallelism ``parallel.ShardedFlatState`` is attached and
 the same two launches run on this rank's 1/world slice between a gradient reduce-scatter and an
 all-gather of the refreshed bf16 copies.
+
+Gradient accumulation (``accumulate_grad_batches = k > 1``): every ``training_step`` still overwrites the stores' gradient
+buffers, and ``accumulate(index_in_window, is_last)`` adds them into one fp32 accumulator per store (``vlb_grad_accum`` /
+``vlb_grad_accum_bf16``; allocated on first use, never at k = 1).  The ``step()`` that closes the window reads the
+accumulators instead of the gradient buffers; the accumulators are not part of ``state_dict()`` (a checkpoint is taken on a
+window boundary).
 """
 from __future__ import annotations
 
@@ -44,6 +50,10 @@ class VlbAdamW(torch.optim.Optimizer):
         self.sumsq_ws = torch.zeros(max(lib.vlb_sumsq_ws_floats(), 1024), dtype=torch.float32, device=dev)
         self.step_count = 0
         self.post_step = []           # callables run after every update (e.g. LoRA derived layouts, W^T refresh)
+        self.accum = [None] * len(self.flats)         # fp32 accumulator per store: allocated by the first accumulate() only
+        self._acc_live = False        # accumulate() ran since the last step(): step() consumes the accumulators
+        self._acc_sumsq = False       # ... and the last accumulate() left the clip norm's sum of squares in self.sumsq
+        self._acc_pos = None          # (index_in_window, is_last) announced by begin_micro_batch (data parallelism)
 
     @property
     def sharded(self):
@@ -119,6 +129,72 @@ class VlbAdamW(torch.optim.Optimizer):
         for fn in self.post_step:
             fn()                      # derived layouts (LoRA A^T / B pads, W^T copies) from the restored weights
 
+    # ------------------------------------------------------------------ gradient accumulation (accumulate_grad_batches > 1)
+    def _active(self, i: int):
+        """Store i's ShardedFlatState when it runs collectives (at world 1 its buffers ARE the flat buffers), else None."""
+        sh = self.shardeds[i]
+        return sh if sh is not None and sh.active else None
+
+    def _accumulator(self, i: int):
+        if self.accum[i] is None:
+            f = self.flats[i]
+            if self._active(i) is not None and getattr(f, "grad_bf16", False):
+                raise ValueError("accumulate_grad_batches > 1 with the full fine-tune under data parallelism is not supported (FULL_SHARD's "
+                                 "two rotating layer gradient buffers, and SHARD_GRAD_OP's bf16 shards, have nowhere to accumulate): "
+                                 "use accumulate_grad_batches=1 with more ranks, or LoRA / the frozen head, which do accumulate")
+            self.accum[i] = torch.empty(f.numel, dtype=torch.float32, device=f.compute.device)
+        return self.accum[i]
+
+    def accumulate_range(self, i: int, start: int, end: int, first: bool, sumsq: bool = False):
+        """accumulator[start:end] (+)= store i's gradient buffer [start:end]; ``sumsq``: also self.sumsq += sum(result^2)."""
+        f, acc = self.flats[i], self._accumulator(i)
+        bf = getattr(f, "grad_bf16", False)
+        fn = lib.vlb_grad_accum_bf16 if bf else lib.vlb_grad_accum
+        check(fn(acc.data_ptr() + 4 * start, f.grad.data_ptr() + (2 if bf else 4) * start, end - start, int(first),
+                 self.sumsq.data_ptr() if sumsq else None, self.sumsq_ws.data_ptr() if sumsq else None, _stream()), "vlb_grad_accum")
+
+    def begin_micro_batch(self, index_in_window: int, is_last: bool):
+        """Before the backward pass of a micro-batch of an accumulation window.  Only data parallelism needs it: micro-batches
+        that do not close the window start no collective (Lightning's ``no_sync``); on the closing one every segment is
+        accumulated and reduce-scattered FROM THE ACCUMULATOR the moment its layers are differentiated."""
+        self._acc_pos = (int(index_in_window), bool(is_last))
+        for i in range(len(self.flats)):
+            sh = self._active(i)
+            if sh is not None:
+                acc = self._accumulator(i)
+                first = index_in_window == 0
+                sh.defer = not is_last
+                sh.accum_src = acc
+                sh.accum_add = (lambda s, e, i=i, first=first: self.accumulate_range(i, s, e, first)) if is_last else None
+
+    def accumulate(self, index_in_window: int, is_last: bool):
+        """After the backward pass of micro-batch ``index_in_window`` (0-based): add the gradient buffers into the
+        accumulators (``index_in_window == 0`` overwrites them: no memset).  ``is_last`` says that the next ``step()`` follows
+        directly: the same pass then also computes the clip norm's sum of squares of the accumulated gradient - bit-identical
+        to ``vlb_grad_sumsq`` on it - and ``step()`` runs no separate norm pass.  A window that is closed without
+        ``is_last`` is still stepped correctly (``step()`` then runs that pass itself)."""
+        first = index_in_window == 0
+        any_active = any(self._active(i) is not None for i in range(len(self.flats)))
+        if any_active and self._acc_pos != (int(index_in_window), bool(is_last)):
+            raise RuntimeError("accumulate() under data parallelism needs begin_micro_batch() with the same position before the backward pass")
+        fuse = bool(is_last) and self.max_norm > 0 and not any_active
+        if fuse:
+            self.sumsq.zero_()
+        for i, f in enumerate(self.flats):
+            sh = self._active(i)
+            if sh is None:
+                self.accumulate_range(i, 0, f.numel, first, sumsq=fuse)
+            elif not is_last:
+                self.accumulate_range(i, 0, f.numel, first)
+            else:
+                for si in range(len(sh.segments)):          # the segments backward has not handed over yet (the head's at least)
+                    sh.reduce_segment(si)
+        self._acc_live, self._acc_sumsq, self._acc_pos = True, fuse, None
+
+    def window_gradient(self, index: int = 0):
+        """The accumulated fp32 gradient of store ``index`` while a window is waiting for its ``step()``, else None."""
+        return self.accum[index] if self._acc_live else None
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -128,22 +204,33 @@ class VlbAdamW(torch.optim.Optimizer):
         group = self.param_groups[0]
         self.step_count += 1
         st = _stream()
+        acc_live, acc_sumsq = self._acc_live, self._acc_sumsq
+        self._acc_live = self._acc_sumsq = False
         for sh in self.shardeds:
             if sh is not None:
+                sh.defer = False             # (a window closed without notice: its segments are reduced from the accumulator now)
                 sh.finish_reduce()           # reduce-scatters started under backward + the rest
+                sh.accum_src = sh.accum_add = None
         bufs = [sh if sh is not None else f for f, sh in zip(self.flats, self.shardeds)]
-        self.sumsq.zero_()
+        # gradient the update reads: the store's buffer (a rank's reduce-scattered slice under data parallelism), or after an
+        # accumulation window the fp32 accumulator - also for the full fine-tune's bf16 store
+        grads = [(self.accum[i], False) if acc_live and self._active(i) is None else (b.grad, getattr(f, "grad_bf16", False))
+                 for i, (f, b) in enumerate(zip(self.flats, bufs))]
+        if not acc_sumsq:
+            self.sumsq.zero_()
         b1, b2 = group["betas"]
         if self.max_norm > 0:
-            for f, b in zip(self.flats, bufs):
-                fn = lib.vlb_grad_sumsq_bf16 if getattr(f, "grad_bf16", False) else lib.vlb_grad_sumsq
-                check(fn(b.grad.data_ptr(), b.numel, self.sumsq.data_ptr(), self.sumsq_ws.data_ptr(), st), "vlb_grad_sumsq")
+            for b, (g, bf) in zip(bufs, grads):
+                if acc_sumsq:
+                    break                    # the window's last accumulate() computed it in the same pass
+                fn = lib.vlb_grad_sumsq_bf16 if bf else lib.vlb_grad_sumsq
+                check(fn(g.data_ptr(), b.numel, self.sumsq.data_ptr(), self.sumsq_ws.data_ptr(), st), "vlb_grad_sumsq")
             active = [sh for sh in self.shardeds if sh is not None]
             if active:
                 active[0].all_reduce_scalar(self.sumsq)      # the clip norm covers every rank's slices
-        for f, b in zip(self.flats, bufs):
-            fn = lib.vlb_adamw_step_g16 if getattr(f, "grad_bf16", False) else lib.vlb_adamw_step
-            check(fn(b.master.data_ptr(), b.compute.data_ptr(), b.grad.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
+        for b, (g, bf) in zip(bufs, grads):
+            fn = lib.vlb_adamw_step_g16 if bf else lib.vlb_adamw_step
+            check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
                      float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.step_count,
                      self.sumsq.data_ptr(), self.max_norm, st), "vlb_adamw_step")
         for sh in self.shardeds:

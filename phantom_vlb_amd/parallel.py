@@ -16,6 +16,10 @@ the MI355X-native equivalent of that config, not a translation of torch FSDP:
   fine-tune's backbone store is FULL_SHARD for its trained bf16 WEIGHTS as well (``full_shard=True``, the default:
   1/world of every decoder layer per rank, a layer gathered for its forward and again for its backward into two
   rotating buffers; ``VLB_FSDP_STRATEGY=SHARD_GRAD_OP`` keeps them replicated), and so are the frozen ones when opted into:
+  Under gradient accumulation (``accumulate_grad_batches = k``) the micro-batches that do not close a window start NO
+  collective (Lightning's ``no_sync``): each rank adds its gradients into a local fp32 accumulator, and on the closing
+  micro-batch every segment is accumulated and reduce-scattered from that accumulator as soon as its layers are
+  differentiated - the overlap with the backward pass is kept and the traffic per optimiser step does not grow with k.
 * ``ShardedLayerStore`` - the fsdp.yaml-equivalent parameter sharding for the frozen decoder layers:
   each rank keeps 1/world of every layer's flat bf16 weights (436 MB/layer -> 54.5 MB at 8 ranks);
   the full layer is all-gathered into one of two buffers on a side stream, one layer ahead of
@@ -145,6 +149,10 @@ class ShardedFlatState:
             self.load_masters()
             flat.m = flat.v = None                # the full-size moments are released: sharded state only
         self._pending = {}
+        # gradient accumulation (VlbAdamW.begin_micro_batch sets these per micro-batch; all off at accumulate_grad_batches = 1)
+        self.defer = False            # a micro-batch that does not close its window: backward starts no collective
+        self.accum_src = None         # the optimiser's fp32 accumulator: what the reduce-scatters read instead of flat.grad
+        self.accum_add = None         # callable(start, end): add this micro-batch's gradients of that range into it first
         self.full_shard = bool(full_shard and self.active)
         if self.full_shard:
             self._enter_full_shard()
@@ -223,13 +231,18 @@ class ShardedFlatState:
             return
         s, e = self.segments[si]
         _, mine = self._own(si)
-        src = self.gpool[(si - 1) % 2][:e - s] if (self.full_shard and si > 0) else self.flat.grad[s:e]
+        if self.accum_src is not None:        # an accumulation window closes: this segment's sum over the window's micro-batches
+            if self.accum_add is not None:
+                self.accum_add(s, e)
+            src = self.accum_src[s:e]
+        else:
+            src = self.gpool[(si - 1) % 2][:e - s] if (self.full_shard and si > 0) else self.flat.grad[s:e]
         self._pending[si] = self.comm.reduce_scatter(self.grad[mine], src)
 
     def on_layer_done(self, li: int):
         """LoRA / full backward hook: layer li (walking L-1 .. 0) has its final gradients."""
         si = self.layer_seg.get(li)
-        if si is not None:
+        if si is not None and not self.defer:
             self.reduce_segment(si)
 
     def finish_reduce(self):

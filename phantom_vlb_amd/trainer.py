@@ -3,8 +3,13 @@
 Honours the keys the reference's YAML passes (config/experiment/*.yaml:42-51): ``precision``
 (must be a bf16 mode - the kernels are bf16), ``gradient_clip_val`` (fused into the AdamW kernel),
 ``devices``/``num_nodes`` (one process per GPU via torchrun), ``max_epochs``, ``max_steps``,
-``val_check_interval`` (fraction of an epoch), ``log_every_n_steps``; callbacks with the Lightning
-hook names used by the reference (train.py:20-30); a CSV metrics file like CSVLogger's.
+``val_check_interval`` (fraction of an epoch), ``log_every_n_steps``, ``accumulate_grad_batches``; callbacks with the
+Lightning hook names used by the reference (train.py:20-30); a CSV metrics file like CSVLogger's.
+
+``accumulate_grad_batches = k`` follows Lightning: a window is k consecutive batches of one epoch followed by one optimiser
+step (an epoch's last window may be short); ``global_step``, the LR scheduler, ``log_every_n_steps`` and ``max_steps`` count
+optimiser steps.  With k > 1 validation (and with it every checkpoint) waits for the first window boundary at or after the
+batch where ``val_check_interval`` falls due, so no checkpoint carries a half-filled accumulator.
 """
 from __future__ import annotations
 
@@ -172,12 +177,21 @@ def _iter_selected(loader, select=None, limit=None):
     return gen()
 
 
+def accumulation_window(batch_idx: int, n_batches: int, k: int) -> tuple[bool, bool]:
+    """(opens, closes): whether batch ``batch_idx`` of an epoch of ``n_batches`` is the first / the last micro-batch of its
+    accumulation window.  Lightning's rule: windows are runs of k batches counted from the start of the epoch, and the
+    epoch's last batch closes its window whatever its length - a window never crosses an epoch."""
+    return batch_idx % k == 0, (batch_idx + 1) % k == 0 or batch_idx + 1 == n_batches
+
+
 class Trainer:
     def __init__(self, precision="bf16-mixed", accelerator="gpu", gradient_clip_val=1.0, devices=1, num_nodes=1,
                  max_epochs=1, max_steps=-1, val_check_interval=1.0, log_every_n_steps=50, logger=None, callbacks=None,
-                 limit_val_batches=None, **kw):
+                 limit_val_batches=None, accumulate_grad_batches=1, **kw):
         if "bf16" not in str(precision):
             raise ValueError(f"precision={precision!r}: the libvlb kernels compute in bf16 (reference: bf16-mixed)")
+        from .litmodule import check_accumulate_grad_batches
+        self.accumulate_grad_batches = check_accumulate_grad_batches(accumulate_grad_batches)
         self.gradient_clip_val = float(gradient_clip_val or 0.0)
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.val_check_interval, self.log_every_n_steps = val_check_interval, log_every_n_steps
@@ -262,6 +276,9 @@ class Trainer:
             init_distributed()
             attach_data_parallel(model, opt)
             sync_module_states(model)
+        k = self.accumulate_grad_batches
+        if hasattr(model, "check_accumulation_supported"):
+            model.check_accumulation_supported(k)
         if ckpt_path:
             self.global_step = load_trainable_checkpoint(model, ckpt_path)
         try:
@@ -283,7 +300,9 @@ class Trainer:
         n_batches = len(train_loader)
         val_every = max(1, int(n_batches * self.val_check_interval)) if self.val_check_interval <= 1 else int(self.val_check_interval)
         t0 = time.time()
-        start_epoch, skip = divmod(self.global_step, max(n_batches, 1)) if ckpt_path else (0, 0)
+        steps_per_epoch = -(-n_batches // k)          # optimiser steps: the epoch's last window may be short
+        start_epoch, skip = divmod(self.global_step, max(steps_per_epoch, 1)) if ckpt_path else (0, 0)
+        skip *= k                                     # checkpoints are taken on window boundaries: whole windows are skipped
         for epoch in range(start_epoch, self.max_epochs):
             self.current_epoch = epoch
             if hasattr(train_loader.sampler, "set_epoch"):
@@ -294,16 +313,29 @@ class Trainer:
             seen = (lambda bi: bi >= skip) if epoch == start_epoch and skip else None     # resumed mid-epoch: the batches
             batches = _iter_selected(train_loader, seen, None)                            # before the checkpoint are not staged
             try:
+                window, val_due = [], False
                 for bi, batch in batches:
                     self._cb("on_train_batch_start", model, batch, bi)
+                    closes = True
+                    if k > 1:
+                        closes = accumulation_window(bi, n_batches, k)[1]
+                        model.last_micro_batch = closes
                     loss = model.training_step(batch)
+                    val_due = val_due or (bi + 1) % val_every == 0
+                    if k > 1:
+                        window.append(loss.detach().clone())      # the unscaled micro-batch losses; logged as their mean
+                        if not closes:
+                            continue
                     opt.step()
                     sched.step()
                     self.global_step += 1
                     if self.global_step % self.log_every_n_steps == 0:
-                        self._log({"train/brain_loss": float(loss), "lr": opt.param_groups[0]["lr"], "epoch": epoch,
+                        shown = float(loss) if k == 1 else sum(float(x) for x in window) / len(window)
+                        self._log({"train/brain_loss": shown, "lr": opt.param_groups[0]["lr"], "epoch": epoch,
                                    "elapsed_s": time.time() - t0})
-                    if (bi + 1) % val_every == 0:
+                    window = []
+                    if val_due:
+                        val_due = False
                         self.validate(model, val_loader)
                     if 0 < self.max_steps <= self.global_step:
                         return

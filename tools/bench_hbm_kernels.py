@@ -91,6 +91,27 @@ def main():
                                                     1e-4, 0.9, 0.999, 1e-8, 1e-2, 1, ss.data_ptr(), 1.0, st), "adamw"), reps=5))
         del head, mst, grd, m1, v1, cp
         torch.cuda.empty_cache()
+    # ---- gradient accumulation (accumulate_grad_batches > 1) next to AdamW at the same n: the 7B LoRA r=16 flat store
+    # (head V=2048 + 32 layers of adapters, flat.FlatTrainables' padding included) and 268 M elements.  12 B (fp32 g) / 10 B (bf16 g) per element; "+sumsq" = the window's last call.
+    st = torch.cuda.current_stream().cuda_stream
+    ws = torch.zeros(max(lib.vlb_sumsq_ws_floats(), 1024), device=dev)
+    ss = torch.zeros(1, device=dev)
+    for label, n in (("LoRA store", 50_561_280), ("268 M", 65536 * E)):
+        mst, grd, m1, v1, acc = (torch.zeros(n, device=dev) for _ in range(5))
+        cp = torch.zeros(n, device=dev, dtype=BF)
+        grd.normal_(generator=g)
+        g16 = grd.to(BF)
+        row(f"adamw_step {label} ({n / 1e6:.0f} M)", n * 30,
+            timeit(lambda: check(lib.vlb_adamw_step(mst.data_ptr(), cp.data_ptr(), grd.data_ptr(), m1.data_ptr(), v1.data_ptr(), n,
+                                                    1e-4, 0.9, 0.999, 1e-8, 1e-2, 1, ss.data_ptr(), 1.0, st), "adamw"), reps=5))
+        for name, fn, src, nb in (("grad_accum", lib.vlb_grad_accum, grd, 12), ("grad_accum_bf16", lib.vlb_grad_accum_bf16, g16, 10)):
+            for fused in (False, True):
+                a = (ss.data_ptr(), ws.data_ptr()) if fused else (None, None)
+                row(f"{name}{' +sumsq' if fused else ''} {label}", n * nb,
+                    timeit(lambda: check(fn(acc.data_ptr(), src.data_ptr(), n, 0, a[0], a[1], st), name), reps=5))
+                acc.zero_()
+        del mst, grd, m1, v1, acc, cp, g16
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
