@@ -296,6 +296,17 @@ int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const void* ridge_
  * seeds_host: R/16 host uint32 (may be NULL when drop_p == 0). */
 int vlb_lora_down(const void* x, int ldx, const void* A, void* t, int ldt, int M, int K, int R, float scale,
                   float drop_p, const uint32_t* seeds_host, void* stream);
+/* Merge one projection's adapter into a COPY of its base weight (peft LoraLayer.merge / get_delta_weight:
+ * W + scale * B @ A), out of place - W is never modified and there is no unmerge:
+ *   Wm[row(n), k] = bf16_rne( float(W[row(n), k]) + scale * sum_{r<R} float(Bt[r, n]) * float(A[r, k]) ),  n < N, k < K.
+ * W / Wm: bf16 [*, K] with row strides ldw / ldwm (multiples of 8), Wm must not overlap W; Bt: bf16 [R, N] (lora_B stored
+ * transposed), A: bf16 [R, K]; R = the padded rank, 16 / 32 / 48 / 64 (padded rows zero); scale = alpha / r in fp32.
+ * Products accumulate in fp32, the scale and the addition of W are fp32, ONE rounding to bf16.
+ * row_map 0: row(n) = n (pass the base of a q / k / v band inside a stacked weight); 1 (gate): row(n) = 32 (n/16) + n%16;
+ * 2 (up): row(n) = 32 (n/16) + 16 + n%16 - the 16-row interleave of VLB_ACT_SWIGLU_PAIR, for W and Wm alike (N % 16 == 0).
+ * N % 8 == 0, K % 8 == 0, all four operands 16-byte aligned. */
+int vlb_lora_merge(const void* W, int ldw, void* Wm, int ldwm, const void* Bt, const void* A, int N, int K, int R, float scale,
+                   int row_map, void* stream);
 /* dx[M,K] += sum_g keep_g/(1-p) * (u[:, 16g:16g+16] . A_g) ; At: [K, >=R] bf16 (transposed adapters, row stride ldat).
  * K % 64 == 0, dx 16-byte aligned with lddx % 8 == 0. */
 int vlb_lora_dx_masked(const void* u, int ldu, const void* At, int ldat, void* dx, int lddx, int M, int K, int R, float drop_p,

@@ -68,6 +68,7 @@ SIGNATURES = {
     "vlb_wgrad_splits": [I],
     "vlb_wgrad_skinny": [P, I, P, I, P, P, I, I, I, F, F, F, P, P],
     "vlb_lora_down": [P, I, P, P, I, I, I, I, F, F, P, P],
+    "vlb_lora_merge": [P, I, P, I, P, P, I, I, I, F, I, P],
     "vlb_lora_dx_masked": [P, I, P, I, P, I, I, I, I, F, P, P],
     "vlb_sumsq_ws_floats": [],
     "vlb_grad_sumsq": [P, L, P, P, P],

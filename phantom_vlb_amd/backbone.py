@@ -351,9 +351,12 @@ class Backbone:
         store.prefetch(i + direction)
         return {**lw, **full}
 
-    def decoder(self, x, key_mask, B, S, layer_outputs=None, layout=None):
+    def decoder(self, x, key_mask, B, S, layer_outputs=None, layout=None, layers=None):
+        """``layers``: per-layer weight dicts to run instead of ``self.w.layers`` (``LoraState.merge()``'s list); they are
+        used as they are, never gathered from the sharded store."""
         for i in range(len(self.w.layers)):
-            x = self.decoder_layer(x, self.layer_weights(i), key_mask, B, S, layout=layout)
+            lw = self.layer_weights(i) if layers is None else layers[i]
+            x = self.decoder_layer(x, lw, key_mask, B, S, layout=layout)
             if layer_outputs is not None:
                 layer_outputs.append(x)
         return ops.rmsnorm(x, self.w.final_norm, self.g.rms_eps)

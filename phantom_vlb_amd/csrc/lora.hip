@@ -462,6 +462,102 @@ __global__ void wgrad_u_reduce_kernel(const float* __restrict__ ws, int splits, 
   u[(int64_t)m * ldu + jr] = (bf16)(v * scale);
 }
 
+// ---------------------------------------------------------------- Wm = bf16(W + scale * Bt^T . A)   (peft merge)
+// HBM-bound: W is read once and Wm written once, 16 bytes per lane; the rank-R delta is formed on the matrix pipe.
+// Block = 4 waves = MG_ROWS output rows x MG_COLS columns.  The block's A panel [R, 256] and Bt panel [R, 128] are staged
+// row-major in LDS (ranks >= R zero: R = 16 / 48 are zero-extended to the MFMA's K = 32); both MFMA operands contract
+// over the panels' ROW index, so the fragments are gathered from LDS element by element - A's once per block (kept in
+// registers), Bt's once per 16-row tile.  A wave owns 64 columns and walks the block's 16-row tiles; per tile four
+// MFMAs (x KS k-steps) whose A-operand rows are permuted as in lora_dx_kernel, so that a lane ends up with 16
+// CONSECUTIVE columns of its row: two 16-byte loads of W, two 16-byte stores of Wm, the four lanes of a row cover
+// one 128-byte line.  The next tile's W is in flight during this tile's math.
+constexpr int MG_COLS = 256;
+constexpr int MG_ROWS = 128;
+
+// row of W / Wm that holds output feature n: plain, or the gate (1) / up (2) half of the 16-row interleave
+__device__ __forceinline__ int64_t merge_row(int n, int row_map) {
+  return row_map == 0 ? (int64_t)n : (int64_t)32 * (n >> 4) + (row_map == 2 ? 16 : 0) + (n & 15);
+}
+
+template <int KS>   // MFMA k-steps of 32 ranks: R <= 32 * KS
+__global__ __launch_bounds__(256) void lora_merge_kernel(const bf16* __restrict__ W, int ldw, bf16* __restrict__ Wm, int ldwm,
+                                                         const bf16* __restrict__ Bt, const bf16* __restrict__ A, int N, int K,
+                                                         int R, float scale, int row_map) {
+  constexpr int RR = 32 * KS;
+  __shared__ __attribute__((aligned(16))) bf16 As[RR][MG_COLS + 8];
+  __shared__ __attribute__((aligned(16))) bf16 Bs[RR][MG_ROWS + 8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int k0 = blockIdx.x * MG_COLS, nb0 = blockIdx.y * MG_ROWS;
+  for (int c = tid; c < RR * (MG_COLS / 8); c += 256) {
+    const int r = c / (MG_COLS / 8), kc = (c % (MG_COLS / 8)) * 8;
+    bf16x8 v = bf16x8{};
+    if (r < R && k0 + kc + 8 <= K) v = *reinterpret_cast<const bf16x8*>(A + (int64_t)r * K + k0 + kc);
+    *reinterpret_cast<bf16x8*>(&As[r][kc]) = v;
+  }
+  for (int c = tid; c < RR * (MG_ROWS / 8); c += 256) {
+    const int r = c / (MG_ROWS / 8), nc = (c % (MG_ROWS / 8)) * 8;
+    bf16x8 v = bf16x8{};
+    if (r < R && nb0 + nc + 8 <= N) v = *reinterpret_cast<const bf16x8*>(Bt + (int64_t)r * N + nb0 + nc);
+    *reinterpret_cast<bf16x8*>(&Bs[r][nc]) = v;
+  }
+  __syncthreads();
+  // A operand of MFMA t: row fr <-> column 16*(fr/4) + 4t + fr%4 of the wave's 64, contraction index = rank 32ks + 8fq + j
+  const int arow = wave * 64 + 16 * (fr >> 2) + (fr & 3);
+  bf16x8 af[4][KS];
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) af[t][ks][j] = As[32 * ks + 8 * fq + j][arow + 4 * t];
+  // the lane's 16 columns; K % 8 == 0, so each 8-column half is wholly inside or wholly outside
+  const int kcol = k0 + wave * 64 + 16 * fq;
+  const bool ok0 = kcol + 8 <= K, ok1 = kcol + 16 <= K;
+  const int tiles = min(MG_ROWS / 16, (N - nb0 + 15) / 16);
+  auto load_w = [&](int nt, bf16x8& w0, bf16x8& w1) {
+    const int n = min(nb0 + 16 * nt + fr, N - 1);
+    const bf16* p = W + merge_row(n, row_map) * ldw + kcol;
+    w0 = bf16x8{}; w1 = bf16x8{};
+    if (ok0) w0 = *reinterpret_cast<const bf16x8*>(p);
+    if (ok1) w1 = *reinterpret_cast<const bf16x8*>(p + 8);
+  };
+  bf16x8 w0, w1;
+  load_w(0, w0, w1);
+  for (int nt = 0; nt < tiles; ++nt) {
+    bf16x8 nx0 = w0, nx1 = w1;
+    if (nt + 1 < tiles) load_w(nt + 1, nx0, nx1);
+    bf16x8 bfr[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) bfr[ks][j] = Bs[32 * ks + 8 * fq + j][16 * nt + fr];
+    float sum[16];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[t][ks], bfr[ks], d, 0, 0, 0);
+      // lane holds columns kcol + 4t + {0..3} of row nb0 + 16nt + fr
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sum[4 * t + e] = d[e];
+    }
+    const int n = nb0 + 16 * nt + fr;
+    if (n < N) {
+      bf16x8 o0, o1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        o0[e] = (bf16)((float)w0[e] + scale * sum[e]);
+        o1[e] = (bf16)((float)w1[e] + scale * sum[8 + e]);
+      }
+      bf16* q = Wm + merge_row(n, row_map) * ldwm + kcol;
+      if (ok0) *reinterpret_cast<bf16x8*>(q) = o0;
+      if (ok1) *reinterpret_cast<bf16x8*>(q + 8) = o1;
+    }
+    w0 = nx0; w1 = nx1;
+  }
+}
+
 inline uint32_t lowbias32_host(uint32_t x) {
   x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
   return x;
@@ -564,6 +660,30 @@ extern "C" int vlb_lora_dx_masked(const void* u, int ldu, const void* At, int ld
 extern "C" int vlb_transpose16_scatter(const void* jobs, int n_jobs, void* stream) {
   VLB_REQUIRE(jobs && n_jobs > 0, "transpose16_scatter: empty job table");
   hipLaunchKernelGGL(transpose16_scatter_kernel, dim3(n_jobs), dim3(256), 0, as_stream(stream), (const ScatterJob*)jobs);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_lora_merge(const void* W, int ldw, void* Wm, int ldwm, const void* Bt, const void* A, int N, int K, int R,
+                              float scale, int row_map, void* stream) {
+  VLB_REQUIRE(W && Wm && Bt && A, "lora_merge: null operand");
+  VLB_REQUIRE(R == 16 || R == 32 || R == 48 || R == 64, "lora_merge: R=%d (the padded rank must be 16, 32, 48 or 64)", R);
+  VLB_REQUIRE(row_map >= 0 && row_map <= 2, "lora_merge: row_map=%d (0 plain, 1 gate, 2 up)", row_map);
+  VLB_REQUIRE(N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && (row_map == 0 || N % 16 == 0),
+              "lora_merge: bad shape N=%d K=%d (multiples of 8; N a multiple of 16 for the gate / up row maps)", N, K);
+  VLB_REQUIRE(ldw >= K && ldwm >= K && ldw % 8 == 0 && ldwm % 8 == 0, "lora_merge: bad row strides ldw=%d ldwm=%d (K=%d)", ldw, ldwm, K);
+  VLB_REQUIRE((((uintptr_t)W | (uintptr_t)Wm | (uintptr_t)Bt | (uintptr_t)A) % 16) == 0, "lora_merge: operands must be 16-byte aligned");
+  // the base weights are never modified (no in-place merge, no unmerge): the two images may not share a byte
+  const int64_t rows = row_map == 0 ? N : 2 * (int64_t)N - (row_map == 1 ? 16 : 0);
+  const uintptr_t w0 = (uintptr_t)W, w1 = w0 + (uintptr_t)(((rows - 1) * ldw + K) * 2);
+  const uintptr_t m0 = (uintptr_t)Wm, m1 = m0 + (uintptr_t)(((rows - 1) * ldwm + K) * 2);
+  VLB_REQUIRE(W != Wm && (w1 <= m0 || m1 <= w0), "lora_merge: Wm must not alias W (the merge is out of place)");
+  dim3 grid((K + MG_COLS - 1) / MG_COLS, (N + MG_ROWS - 1) / MG_ROWS);
+  hipStream_t st = as_stream(stream);
+  if (R <= 32)
+    hipLaunchKernelGGL(lora_merge_kernel<1>, grid, dim3(256), 0, st, (const bf16*)W, ldw, (bf16*)Wm, ldwm, (const bf16*)Bt, (const bf16*)A, N, K, R, scale, row_map);
+  else
+    hipLaunchKernelGGL(lora_merge_kernel<2>, grid, dim3(256), 0, st, (const bf16*)W, ldw, (bf16*)Wm, ldwm, (const bf16*)Bt, (const bf16*)A, N, K, R, scale, row_map);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }

@@ -166,6 +166,7 @@ class VLBLitModuleConfig:
     fp8_gemm: bool = False          # full fine-tune only: decoder forward / dgrad GEMMs on the MX-fp8 MFMA path (configs[4])
     cache_features: bool = False    # frozen backbone only: keep each clip's pooled features, later epochs run the head alone
     feature_cache_dir: str | None = None    # persist the feature caches there (feature_cache.py; loaded on a matching fingerprint)
+    merge_lora_for_eval: bool = False   # LoRA only: eval-mode forwards run the frozen-path decoder on merged weights (LoraState.merge)
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -173,6 +174,8 @@ class VLBLitModuleConfig:
         if self.cache_features and (self.use_lora or not self.freeze_backbone):
             raise ValueError("cache_features=True needs a frozen backbone without LoRA (freeze_backbone=True, use_lora=False): "
                              "with LoRA or a full fine-tune the backbone's output changes every step")
+        if self.merge_lora_for_eval and not self.use_lora:
+            raise ValueError("merge_lora_for_eval=True needs use_lora=True: without adapters there is nothing to merge")
 
 
 def resolve_geometry(cfg: VLBLitModuleConfig) -> Geometry:
@@ -389,7 +392,9 @@ class VLBLitModule(_Base):
         vis = self._vision_tensor(x_video)
         ids = x_lang.to(self.device, torch.int64).contiguous()
         B = ids.shape[0]
-        if self.lora is not None:        # eval mode keeps the adapters (peft eval: dropout off), like the reference's validation
+        if self.lora is not None and not self.training and getattr(self.config, "merge_lora_for_eval", False):
+            hidden, key_mask = self._merged_forward(vis, ids, layout)      # the same adapters, folded into the weights
+        elif self.lora is not None:      # eval mode keeps the adapters (peft eval: dropout off), like the reference's validation
             hidden, key_mask = self.lora.forward(self.backbone, vis, ids, layout, train=self.training)
         elif self.full is not None and self.training:      # full fine-tune: forward that keeps what backward needs
             hidden, key_mask = self.full.forward(vis, ids, layout, ids_host=ids_host)
@@ -400,6 +405,53 @@ class VLBLitModule(_Base):
         pred, terms = self.head.forward(hidden, weight_mask, y, keep_scale, layout)
         self._loss_terms = terms
         return pred, terms[1]
+
+    # ------------------------------------------------------------------ merged adapters (peft merge_adapter / merge_and_unload)
+    def _merged_layers(self):
+        """``LoraState.merge()``'s per-layer weights (re-merged only when the adapters changed since the last merge)."""
+        if self.lora is None:
+            raise ValueError("merged weights need a LoRA run (use_lora=True): there are no adapters to merge")
+        if getattr(self.backbone, "store", None) is not None:
+            raise ValueError("merged LoRA weights with a sharded frozen layer store (Backbone.enable_sharding) are not supported: "
+                             "every rank holds 1/world of each layer, and merging gathered shards is out of scope")
+        return self.lora.merge()
+
+    def _merged_forward(self, vis, ids, layout):
+        """Eval-mode forward of a LoRA module on merged weights: the frozen path (``Backbone.decoder_layer``: one GEMM per
+        projection, SwiGLU in the epilogue) instead of ``LoraState._decoder_eval``."""
+        bb, g = self.backbone, self.geometry
+        layers = self._merged_layers()
+        emb, key_mask = bb.splice(ids, bb.video_tokens(vis), layout)
+        return bb.decoder(emb, key_mask, vis.shape[0], g.max_len, layout=layout, layers=layers), key_mask
+
+    def merged_state_dict(self) -> dict:
+        """The decoder linears with the adapters merged in (``W + (alpha/r) B A``, bf16, host) under their upstream names,
+        de-stacked and de-interleaved, plus the head tensors: with the untouched rest of the base checkpoint it loads as a
+        plain decoder, ``configure_model(state_dict={**base, **merged})`` under ``use_lora=False, freeze_backbone=True``."""
+        g = self.geometry
+        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
+        sd = {}
+        for i, mw in enumerate(self._merged_layers()):
+            p = f"model.layers.{i}"
+            if "wgu_il" in mw:
+                gu = mw["wgu_il"].view(g.ff // 16, 2, 16, g.dim)
+                gate, up = gu[:, 0].reshape(g.ff, g.dim), gu[:, 1].reshape(g.ff, g.dim)
+            else:
+                gate, up = mw["wgu"][:g.ff], mw["wgu"][g.ff:]
+            for n, t in (("self_attn.q_proj", mw["wqkv"][:qd]), ("self_attn.k_proj", mw["wqkv"][qd:qd + kd]),
+                         ("self_attn.v_proj", mw["wqkv"][qd + kd:]), ("self_attn.o_proj", mw["wo"]),
+                         ("mlp.gate_proj", gate), ("mlp.up_proj", up), ("mlp.down_proj", mw["wdown"])):
+                sd[f"{p}.{n}.weight"] = t.detach().cpu().contiguous().clone()
+        sd.update({n: self.head.master[n].detach().cpu().clone() for n in HEAD_PARAMS})
+        return sd
+
+    def save_merged(self, path: str) -> str:
+        """``merged_state_dict()`` as one safetensors file (the format ``load_safetensors_dir`` reads)."""
+        from safetensors.torch import save_file
+        d = os.path.dirname(os.path.abspath(path))
+        os.makedirs(d, exist_ok=True)
+        save_file(self.merged_state_dict(), path)
+        return path
 
     def _common_step(self, batch, train: bool):
         cfg, g = self.config, self.geometry

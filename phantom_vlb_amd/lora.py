@@ -163,6 +163,9 @@ class LoraState:
             self.grad_A.append(ga)
         # bf16 compute copies the optimiser refreshes in place: A rows inside the stacked matrix, B^T separate
         self.bt = {n: torch.zeros(t.shape, dtype=BF16, device=device) for n, t in self.master.items() if "lora_B" in n}
+        self.version = 0               # bumped whenever the bf16 compute copies may have changed (refresh / load_state_dict)
+        self._merged = None            # merge(): per-layer dicts of merged weights, allocated on first use
+        self._merged_version = -1
         self.refresh(from_master=True)
         self._ws = None
 
@@ -219,6 +222,47 @@ class LoraState:
                 t.copy_(self.master[n])
         jobs = self._scatter_jobs()
         check(lib.vlb_transpose16_scatter(jobs.data_ptr(), self._n_jobs, _stream()), "vlb_transpose16_scatter")
+        self.version += 1
+
+    # ------------------------------------------------------------------ merged weights (peft merge_adapter, out of place)
+    def merge(self):
+        """Per-layer weight dicts ``Backbone.decoder_layer`` runs as they are: ``W + (alpha/r) B A`` for the seven adapted
+        projections in the frozen forward layouts (``wqkv``, ``wo``, ``wgu_il`` or ``wgu``, ``wdown``), the norms by
+        reference.  The adapters are the bf16 compute copies the forward multiplies by, so the merged decoder represents
+        what ``_decoder_eval`` applies; one rounding per weight (vlb_lora_merge).  The base weights are not touched and
+        the ``_t`` (dgrad) layouts are not merged: nothing differentiates through the result.  Buffers are allocated on
+        the first call and reused; while ``version`` is unchanged (no refresh() / load_state_dict() since the last merge)
+        the cached list is returned and nothing is launched."""
+        layers = self.w.layers
+        if any(lw.get(k) is None for lw in layers for k in ("wqkv", "wo", "wdown", "wgu_il" if self.gu_il else "wgu")):
+            raise ValueError("LoraState.merge(): the frozen decoder weights are sharded (Backbone.enable_sharding): a rank holds "
+                             "1/world of every layer, and merging gathered shards is not supported")
+        if self._merged is not None and self._merged_version == self.version:
+            return self._merged
+        if self._merged is None:
+            keys = ("wqkv", "wo", "wdown", "wgu_il" if self.gu_il else "wgu")
+            self._merged = [{"in_norm": lw["in_norm"], "post_norm": lw["post_norm"], **{k: torch.empty_like(lw[k]) for k in keys}}
+                            for lw in layers]
+        g, rp = self.g, self.rp
+        for li, (lw, mw, lay) in enumerate(zip(layers, self._merged, self.layers)):
+            def one(gname, j, w, wm, row_map=ops.MERGE_PLAIN):
+                pre = f"model.layers.{li}.{lay[gname]['targets'][j]}"
+                ops.lora_merge(w, wm, self.bt[f"{pre}.lora_B.weight"], lay[gname]["A"][rp * j:rp * j + rp], self.scale, row_map)
+            row = 0
+            for j, t in enumerate(lay["qkv"]["targets"]):       # q / k / v bands of the stacked weight
+                n = self.out_dims[t]
+                one("qkv", j, lw["wqkv"][row:row + n], mw["wqkv"][row:row + n])
+                row += n
+            one("o", 0, lw["wo"], mw["wo"])
+            if self.gu_il:
+                one("gu", 0, lw["wgu_il"], mw["wgu_il"], ops.MERGE_GATE)
+                one("gu", 1, lw["wgu_il"], mw["wgu_il"], ops.MERGE_UP)
+            else:
+                one("gu", 0, lw["wgu"][:g.ff], mw["wgu"][:g.ff])
+                one("gu", 1, lw["wgu"][g.ff:], mw["wgu"][g.ff:])
+            one("down", 0, lw["wdown"], mw["wdown"])
+        self._merged_version = self.version
+        return self._merged
 
     def state_dict(self):
         """peft layout: lora_A [r,in], lora_B [out,r] (rank padding removed)."""

@@ -208,6 +208,29 @@ def interleave_gate_up(w_gate, w_up):
     return torch.stack([w_gate.view(ff // 16, 16, k), w_up.view(ff // 16, 16, k)], 1).reshape(2 * ff, k).contiguous()
 
 
+MERGE_PLAIN, MERGE_GATE, MERGE_UP = 0, 1, 2
+merge_launches = 0          # vlb_lora_merge calls so far (LoraState.merge's cache is checked against it)
+
+
+def lora_merge(w, wm, bt, a, scale, row_map=MERGE_PLAIN):
+    """wm[row(n)] = bf16(w[row(n)] + scale * bt[:, n] . a) for the n < N outputs of one adapted projection (peft
+    ``merge``): fp32 accumulate, fp32 scale, one rounding; ``w`` is left alone.  bt [R, N] (lora_B transposed), a [R, K],
+    R the padded rank (16..64).  ``MERGE_PLAIN``: w / wm are the projection's [N, K] rows (a band view of a stacked weight
+    is fine); ``MERGE_GATE`` / ``MERGE_UP``: w / wm are whole [2N, K] ``interleave_gate_up`` images."""
+    global merge_launches
+    _dev(w)
+    R, K = a.shape
+    N = bt.shape[1]
+    rows = N if row_map == MERGE_PLAIN else 2 * N
+    assert bt.shape[0] == R and w.shape == (rows, K) and wm.shape == (rows, K)
+    assert w.stride(1) == 1 and wm.stride(1) == 1 and a.is_contiguous() and bt.is_contiguous()
+    assert w.dtype == wm.dtype == bt.dtype == a.dtype == BF16
+    check(lib.vlb_lora_merge(w.data_ptr(), w.stride(0), wm.data_ptr(), wm.stride(0), bt.data_ptr(), a.data_ptr(), N, K, R,
+                             float(scale), int(row_map), _stream()), "vlb_lora_merge")
+    merge_launches += 1
+    return wm
+
+
 def transpose(x):
     R, C = x.shape
     out = torch.empty(C, R, dtype=BF16, device=x.device)

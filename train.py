@@ -18,7 +18,21 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
+def export_merged(litmodule, path: str) -> str:
+    """Root key ``export_merged=<file>``: after the fit a LoRA run also writes its decoder linears with the adapters merged in
+    (plus the head) as one safetensors file - with the untouched rest of the base checkpoint, a plain VideoLLaMA2 decoder
+    (VLBLitModule.save_merged).  The counterpart of storing only the adapters (reference train.py:60 TODO)."""
+    if not getattr(litmodule.config, "use_lora", False):
+        raise ValueError(f"export_merged={path!r} needs a LoRA run (litmodule.config.use_lora=true): without adapters there is "
+                         "nothing to merge")
+    out = litmodule.save_merged(str(path))
+    print(f"[train] merged LoRA weights written to {out}")
+    return out
+
+
 def train(config: dict) -> None:
+    if config.get("export_merged") and not config["litmodule"]["config"].get("use_lora"):       # before the fit, not after it
+        raise ValueError(f"export_merged={config['export_merged']!r} needs a LoRA run (litmodule.config.use_lora=true)")
     import torch
     from phantom_vlb_amd.config import instantiate, use_builtin_trainer
     from src import LogValAccuracyCallback
@@ -55,6 +69,8 @@ def train(config: dict) -> None:
     litmodule = instantiate(config["litmodule"])
     trainer.fit(model=litmodule, datamodule=datamodule)
     trainer.save_checkpoint(config["output_dir"])          # reference train.py:58 -> <output_dir>/final.ckpt
+    if config.get("export_merged"):
+        export_merged(litmodule, config["export_merged"])
 
 
 if __name__ == "__main__":
