@@ -8,32 +8,12 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from exact_ints import _lowbias32, keep_mask          # numpy restatement of the kernels' counter-based dropout mask
 from gen_golden import load_golden
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-
-
-# ---- numpy restatement of the kernels' counter-based dropout mask (phantom_vlb_amd/csrc/lora.hip)
-def _lowbias32(x):
-    x = x.astype(np.uint64)
-    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & np.uint64(0xffffffff)
-    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & np.uint64(0xffffffff)
-    x ^= x >> np.uint64(16)
-    return x
-
-
-def keep_mask(seed, M, K, p):
-    thresh = min(65535, int(p * 65536 + 0.5))
-    m = np.arange(M, dtype=np.uint64)[:, None]
-    kp = np.arange(K // 2, dtype=np.uint64)[None, :]
-    c = m * np.uint64(K // 2) + kp
-    h = _lowbias32((c & np.uint64(0xffffffff)) ^ _lowbias32(((c >> np.uint64(32)) + np.uint64(seed)) & np.uint64(0xffffffff)))
-    keep = np.empty((M, K), dtype=bool)
-    keep[:, 0::2] = (h & np.uint64(0xffff)) >= thresh
-    keep[:, 1::2] = (h >> np.uint64(16)) >= thresh
-    return torch.from_numpy(keep)
 
 
 def _r(*shape, dev, scale=1.0, seed=0):
