@@ -19,7 +19,7 @@ import math
 import torch
 
 from . import ops
-from .geometry import Geometry, VIDEO_TOKEN_ID
+from .geometry import Geometry, VIDEO_TOKEN_ID, decoder_linears
 
 BF16 = torch.bfloat16
 V_PRE = "model.vision_tower.vision_tower.vision_model"
@@ -175,17 +175,23 @@ class Weights:
         sd["model.embed_tokens.weight"] = rn(g.vocab, g.dim)
         for i in range(g.layers):
             p = f"model.layers.{i}"
-            sd[f"{p}.self_attn.q_proj.weight"] = rn(g.heads * g.head_dim, g.dim)
-            sd[f"{p}.self_attn.k_proj.weight"] = rn(g.kv_heads * g.head_dim, g.dim)
-            sd[f"{p}.self_attn.v_proj.weight"] = rn(g.kv_heads * g.head_dim, g.dim)
-            sd[f"{p}.self_attn.o_proj.weight"] = rn(g.dim, g.heads * g.head_dim)
-            sd[f"{p}.mlp.gate_proj.weight"] = rn(g.ff, g.dim)
-            sd[f"{p}.mlp.up_proj.weight"] = rn(g.ff, g.dim)
-            sd[f"{p}.mlp.down_proj.weight"] = rn(g.dim, g.ff)
+            for lin in decoder_linears(g):
+                sd[f"{p}.{lin.suffix}.weight"] = rn(lin.out, lin.inp)
             sd[f"{p}.input_layernorm.weight"] = ones(g.dim)
             sd[f"{p}.post_attention_layernorm.weight"] = ones(g.dim)
         sd["model.norm.weight"] = ones(g.dim)
         return sd
+
+
+def destack_decoder_layer(g: Geometry, wqkv, wo, wdown, wgu=None, wgu_il=None) -> dict:
+    """Inverse of the stacking in ``Weights.__init__``: a decoder layer's kernel weights -> its seven linears keyed by
+    upstream suffix (``self_attn.q_proj`` ... ``mlp.down_proj``), as row bands of what was passed in.  Gate / up come from
+    the plain ``wgu`` or, when only the ``ops.interleave_gate_up`` image ``wgu_il`` is given, from its 16-row blocks put
+    back in [gate; up] order (one copy)."""
+    if wgu is None:
+        wgu = wgu_il.view(g.ff // 16, 2, 16, -1).transpose(0, 1).reshape(2 * g.ff, -1)
+    stacked = dict(wqkv=wqkv, wo=wo, wgu=wgu, wdown=wdown)
+    return {lin.suffix: stacked[lin.stacked][lin.row:lin.row + lin.out] for lin in decoder_linears(g)}
 
 
 class Backbone:
@@ -250,16 +256,34 @@ class Backbone:
         x = ops.gemm(x, w.ro0[0], bias=w.ro0[1], act=ops.ACT_GELU)
         return ops.gemm(x, w.ro2[0], bias=w.ro2[1])
 
+    # ---------------- the decoder's attention block, shared by the frozen, LoRA and full fine-tune paths
+    def attention(self, qkv, key_mask, B, layout=None, need_lse=False):
+        """RoPE on the q | k columns of the stacked projection output ``qkv`` [rows, q_dim + 2 kv_dim], in place, then causal
+        attention: returns ``a`` [rows, q_dim], or ``(a, lse)`` with ``need_lse`` (what ``attention_bwd`` takes)."""
+        g, w = self.g, self.w
+        qd, kd = g.q_dim, g.kv_dim
+        ops.rope_(qkv, w.rope_cos, w.rope_sin, B, g.max_len, g.heads + g.kv_heads, g.head_dim,
+                  pos=None if layout is None else layout.pos)
+        return ops.attention_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, g.max_len, g.heads, g.kv_heads,
+                                 g.head_dim, True, g.head_dim ** -0.5, key_mask=key_mask, need_lse=need_lse, layout=layout)
+
+    def attention_bwd(self, qkv, a, d_a, lse, key_mask, B, layout, delta):
+        """Backward of ``attention``: d_a -> dqkv, the inverse rotation applied.  ``qkv`` is the rotated buffer the forward
+        left behind; ``delta`` fp32 [B, heads, max_len] is scratch the caller allocates once per backward pass."""
+        g, w = self.g, self.w
+        dqkv = ops.attention_bwd(qkv, g.q_dim, g.kv_dim, a, d_a, lse, key_mask, B, g.max_len, g.heads, g.kv_heads,
+                                 g.head_dim, True, g.head_dim ** -0.5, layout=layout, delta=delta)
+        ops.rope_(dqkv, w.rope_cos, w.rope_sin, B, g.max_len, g.heads + g.kv_heads, g.head_dim, sign=-1,
+                  pos=None if layout is None else layout.pos)
+        return dqkv
+
     # ---------------- a7: one Mistral decoder layer (modeling_mistral.py:202-240)
     def decoder_layer(self, x, lw, key_mask, B, S, save=None, layout=None):
         g = self.g
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
+        assert S == g.max_len, "the decoder runs at the geometry's sequence length (rope tables, attention)"
         h = ops.rmsnorm(x, lw["in_norm"], g.rms_eps)
         qkv = ops.gemm(h, lw["wqkv"])
-        ops.rope_(qkv, self.w.rope_cos, self.w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim,
-                  pos=None if layout is None else layout.pos)
-        a = ops.attention_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, S, g.heads, g.kv_heads, g.head_dim,
-                              True, g.head_dim ** -0.5, key_mask=key_mask, layout=layout)
+        a = self.attention(qkv, key_mask, B, layout)
         x = ops.gemm(a, lw["wo"], residual=x)
         h = ops.rmsnorm(x, lw["post_norm"], g.rms_eps)
         if lw.get("wgu_il") is not None:
@@ -276,7 +300,6 @@ class Backbone:
         explicit removal of it is exercised."""
         from .litmodule import _LinearInfo
         g = self.g
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
         for i in range(g.vit_layers):
             p = f"{V_PRE}.encoder.layers.{i}"
             for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
@@ -287,13 +310,8 @@ class Backbone:
             yield f"{M_PRE}.{n}", _LinearInfo(g.dim, g.dim)
         for i in range(g.layers):
             p = f"model.layers.{i}"
-            yield f"{p}.self_attn.q_proj", _LinearInfo(qd, g.dim)
-            yield f"{p}.self_attn.k_proj", _LinearInfo(kd, g.dim)
-            yield f"{p}.self_attn.v_proj", _LinearInfo(kd, g.dim)
-            yield f"{p}.self_attn.o_proj", _LinearInfo(g.dim, qd)
-            yield f"{p}.mlp.gate_proj", _LinearInfo(g.ff, g.dim)
-            yield f"{p}.mlp.up_proj", _LinearInfo(g.ff, g.dim)
-            yield f"{p}.mlp.down_proj", _LinearInfo(g.dim, g.ff)
+            for lin in decoder_linears(g):
+                yield f"{p}.{lin.suffix}", _LinearInfo(lin.out, lin.inp)
         yield "lm_head", _LinearInfo(g.vocab, g.dim)
 
     def splice(self, ids, video_tokens, layout=None):

@@ -22,15 +22,12 @@ import numpy as np
 import torch
 
 from ._lib import LIB_PATH, check, lib
+from .ops import _stream
 
 FORMAT_VERSION = 1
 # Geometry fields that shape the frozen forward; the head's own (num_target, l2_lambda) and the adapters' are left out, so
 # a persisted cache serves head hyper-parameter sweeps.
 _HEAD_ONLY_FIELDS = ("num_target", "l2_lambda", "lora_r", "lora_alpha")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _file_id(path: str) -> list:

@@ -23,16 +23,14 @@ import torch
 
 from . import ops
 from ._lib import check, lib
+from .backbone import destack_decoder_layer
 from .flat import SEG_ALIGN
 from .geometry import Geometry, VIDEO_TOKEN_ID
+from .ops import _stream
 
 BF16 = torch.bfloat16
 CONN_W = ("conv1", "dw", "se1", "se1b", "se2", "se2b", "conv3", "ds")        # single-tensor entries of a bottleneck block
 CONN_LN = ("bn1", "bn2", "bn3", "dsbn")                                      # (weight, bias) pairs
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # fp8 path: quantisations produced by the kernel that writes the bf16 tensor (rmsnorm / SwiGLU) or from one read for both layouts
@@ -459,17 +457,12 @@ class FullFineTune:
         vid = self.connector_forward(bb.video_tokens(vision_f32, tower_only=True), B)     # tower frozen: nothing kept; may have run one step ahead
         x, key_mask = bb.splice(ids, vid, layout)
         self._ids_host = ids_host if ids_host is not None else ids.cpu()
-        S = g.max_len
-        pos = None if layout is None else layout.pos
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
         self.saved = []
         for li in range(g.layers):
             lw = self._enter(li, backward=False)
             h1, h1q = self._norm(x, lw["in_norm"])
             qkv = self._lin(h1, li, "wqkv", xq=h1q)
-            ops.rope_(qkv, w.rope_cos, w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim, pos=pos)
-            a, lse = ops.attention_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, S, g.heads, g.kv_heads, g.head_dim,
-                                       True, g.head_dim ** -0.5, key_mask=key_mask, need_lse=True, layout=layout)
+            a, lse = bb.attention(qkv, key_mask, B, layout, need_lse=True)
             x2 = self._lin(a, li, "wo", residual=x)
             h2, h2q = self._norm(x2, lw["post_norm"])
             gu = self._lin(h2, li, "wgu", xq=h2q)
@@ -488,12 +481,9 @@ class FullFineTune:
     def backward(self, dhidden):
         """dhidden: d loss / d (post-final-norm hidden) bf16 [rows, dim].  Fills every backbone gradient."""
         g, w, G = self.g, self.w, self.flat.g_
-        B, S = self.B, g.max_len
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
-        layout = self.layout
-        pos = None if layout is None else layout.pos
+        B, layout = self.B, self.layout
         dx = ops.rmsnorm_bwd_full(self.x_last, w.final_norm, dhidden, g.rms_eps, G("norm"))
-        delta = torch.empty(B, g.heads, S, dtype=torch.float32, device=self.dev)
+        delta = torch.empty(B, g.heads, g.max_len, dtype=torch.float32, device=self.dev)
         for li in range(g.layers - 1, -1, -1):
             lw, sv = self._enter(li, backward=True), self.saved[li]
             pre = f"layers.{li}"
@@ -510,9 +500,7 @@ class FullFineTune:
             dq_ = self._dual(dx2) or (None, None)
             self.wgrad(dx2, sv["a"], G(f"{pre}.wo"), fp8=self.fp8, dyTq=dq_[1])
             d_a = self._lin(dx2, li, "wo_t", xq=dq_[0])
-            dqkv = ops.attention_bwd(sv["qkv"], qd, kd, sv["a"], d_a, sv["lse"], self.key_mask, B, S, g.heads, g.kv_heads,
-                                     g.head_dim, True, g.head_dim ** -0.5, layout=layout, delta=delta)
-            ops.rope_(dqkv, w.rope_cos, w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim, sign=-1, pos=pos)
+            dqkv = self.bb.attention_bwd(sv["qkv"], sv["a"], d_a, sv["lse"], self.key_mask, B, layout, delta)
             dq_ = self._dual(dqkv) or (None, None)
             self.wgrad(dqkv, sv["h1"], G(f"{pre}.wqkv"), fp8=self.fp8, dyTq=dq_[1])
             d_h1 = self._lin(dqkv, li, "wqkv_t", xq=dq_[0])
@@ -568,18 +556,11 @@ class FullFineTune:
             # "grad" is then the REDUCED gradient of the last step)
             buf = self.shards.gather_full(which)
         M = lambda n: f.view(buf, n).detach().float().cpu()
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
         sd = {"model.embed_tokens.weight": M("embed_tokens"), "model.norm.weight": M("norm")}
         for li in range(g.layers):
             p, q = f"model.layers.{li}", f"layers.{li}"
-            wqkv, wgu = M(f"{q}.wqkv"), M(f"{q}.wgu")
-            sd[f"{p}.self_attn.q_proj.weight"] = wqkv[:qd].clone()
-            sd[f"{p}.self_attn.k_proj.weight"] = wqkv[qd:qd + kd].clone()
-            sd[f"{p}.self_attn.v_proj.weight"] = wqkv[qd + kd:].clone()
-            sd[f"{p}.self_attn.o_proj.weight"] = M(f"{q}.wo")
-            sd[f"{p}.mlp.gate_proj.weight"] = wgu[:g.ff].clone()
-            sd[f"{p}.mlp.up_proj.weight"] = wgu[g.ff:].clone()
-            sd[f"{p}.mlp.down_proj.weight"] = M(f"{q}.wdown")
+            for n, t in destack_decoder_layer(g, M(f"{q}.wqkv"), M(f"{q}.wo"), M(f"{q}.wdown"), wgu=M(f"{q}.wgu")).items():
+                sd[f"{p}.{n}.weight"] = t.clone()         # a band must not pin (or alias) the stacked tensor it was cut from
             sd[f"{p}.input_layernorm.weight"] = M(f"{q}.in_norm")
             sd[f"{p}.post_attention_layernorm.weight"] = M(f"{q}.post_norm")
         P = "model.mm_projector"

@@ -7,8 +7,32 @@ BASELINE.json configs[0] runs through the same kernels.
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import NamedTuple
 
 VIDEO_TOKEN_ID = -201  # src/preprocessing/videollama2_vlb_extractfeatures.py:235-236
+
+
+class DecoderLinear(NamedTuple):
+    """One of the seven ``nn.Linear`` of a Mistral decoder layer and where its rows live in the kernel weights."""
+    suffix: str         # upstream module name below ``model.layers.{i}``
+    out: int
+    inp: int
+    stacked: str        # kernel tensor holding it: wqkv | wo | wgu | wdown
+    row: int            # first row of its band there (wgu: in the plain [gate; up] order)
+
+
+def decoder_linears(g) -> tuple[DecoderLinear, ...]:
+    """The decoder layer's linears in upstream module order: shapes, and the stacking ``backbone.Weights`` applies
+    (q | k | v share their input and are one weight, so are gate | up).  ``g``: a ``Geometry``, or any object with its
+    fields (the oracle keeps a dataclass of its own)."""
+    qd, kd, d, ff = g.heads * g.head_dim, g.kv_heads * g.head_dim, g.dim, g.ff
+    return (DecoderLinear("self_attn.q_proj", qd, d, "wqkv", 0),
+            DecoderLinear("self_attn.k_proj", kd, d, "wqkv", qd),
+            DecoderLinear("self_attn.v_proj", kd, d, "wqkv", qd + kd),
+            DecoderLinear("self_attn.o_proj", d, qd, "wo", 0),
+            DecoderLinear("mlp.gate_proj", ff, d, "wgu", 0),
+            DecoderLinear("mlp.up_proj", ff, d, "wgu", ff),
+            DecoderLinear("mlp.down_proj", d, ff, "wdown", 0))
 
 
 @dataclass
@@ -40,6 +64,14 @@ class Geometry:
     l2_lambda: float = 1e-3
     lora_r: int = 16
     lora_alpha: int = 32
+
+    @property
+    def q_dim(self) -> int:
+        return self.heads * self.head_dim
+
+    @property
+    def kv_dim(self) -> int:
+        return self.kv_heads * self.head_dim
 
     @property
     def grid(self) -> int:
@@ -87,6 +119,3 @@ def geometry_mini(**kw) -> Geometry:
     g.update(kw)
     return Geometry(**g)
 
-
-LORA_TARGETS = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj", "self_attn.o_proj",
-                "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")

@@ -13,14 +13,11 @@ import math
 import torch
 
 from ._lib import check, lib
+from .ops import _stream
 
 BF16 = torch.bfloat16
 HEAD_PARAMS = ("layer_norm1.weight", "layer_norm1.bias", "layer_norm2.weight", "layer_norm2.bias",
                "ridge_layer.linear.weight", "ridge_layer.linear.bias")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class BrainHead:

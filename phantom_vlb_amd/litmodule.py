@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import torch
 
 from . import ops
-from .backbone import Backbone, Weights
+from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
 from .head import HEAD_PARAMS, BrainHead
 from .optim import VlbAdamW
@@ -418,7 +418,7 @@ class VLBLitModule(_Base):
 
     def _merged_forward(self, vis, ids, layout):
         """Eval-mode forward of a LoRA module on merged weights: the frozen path (``Backbone.decoder_layer``: one GEMM per
-        projection, SwiGLU in the epilogue) instead of ``LoraState._decoder_eval``."""
+        projection, SwiGLU in the epilogue) instead of ``LoraState.decoder_forward(train=False)``."""
         bb, g = self.backbone, self.geometry
         layers = self._merged_layers()
         emb, key_mask = bb.splice(ids, bb.video_tokens(vis), layout)
@@ -428,20 +428,11 @@ class VLBLitModule(_Base):
         """The decoder linears with the adapters merged in (``W + (alpha/r) B A``, bf16, host) under their upstream names,
         de-stacked and de-interleaved, plus the head tensors: with the untouched rest of the base checkpoint it loads as a
         plain decoder, ``configure_model(state_dict={**base, **merged})`` under ``use_lora=False, freeze_backbone=True``."""
-        g = self.geometry
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
         sd = {}
         for i, mw in enumerate(self._merged_layers()):
-            p = f"model.layers.{i}"
-            if "wgu_il" in mw:
-                gu = mw["wgu_il"].view(g.ff // 16, 2, 16, g.dim)
-                gate, up = gu[:, 0].reshape(g.ff, g.dim), gu[:, 1].reshape(g.ff, g.dim)
-            else:
-                gate, up = mw["wgu"][:g.ff], mw["wgu"][g.ff:]
-            for n, t in (("self_attn.q_proj", mw["wqkv"][:qd]), ("self_attn.k_proj", mw["wqkv"][qd:qd + kd]),
-                         ("self_attn.v_proj", mw["wqkv"][qd + kd:]), ("self_attn.o_proj", mw["wo"]),
-                         ("mlp.gate_proj", gate), ("mlp.up_proj", up), ("mlp.down_proj", mw["wdown"])):
-                sd[f"{p}.{n}.weight"] = t.detach().cpu().contiguous().clone()
+            lins = destack_decoder_layer(self.geometry, mw["wqkv"], mw["wo"], mw["wdown"], mw.get("wgu"), mw.get("wgu_il"))
+            for n, t in lins.items():
+                sd[f"model.layers.{i}.{n}.weight"] = t.detach().cpu().contiguous().clone()
         sd.update({n: self.head.master[n].detach().cpu().clone() for n in HEAD_PARAMS})
         return sd
 

@@ -23,16 +23,13 @@ import torch
 
 from . import ops
 from ._lib import check, lib
-from .geometry import Geometry
+from .geometry import Geometry, decoder_linears
+from .ops import _stream
 
 BF16 = torch.bfloat16
 PAD = 64  # adapter rank columns padded to one GEMM K-tile
 FUSE_SWIGLU_BWD = True      # SwiGLU backward in the epilogue of the down projection's dgrad GEMM (A/B switch)
 MERGE_DB_U = True           # one dB^T / u sweep for the projections sharing a dy (q|k|v, gate|up) instead of one each (A/B switch)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _seeds(vals):
@@ -115,11 +112,8 @@ class LoraState:
         self.rank = 0                  # data-parallel rank, mixed into the dropout seeds (ranks draw distinct masks)
         self.grad_hook = None          # callable(layer index) fired by backward when a layer's gradients are final
         self.base_seed = seed
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
-        self.out_dims = {"self_attn.q_proj": qd, "self_attn.k_proj": kd, "self_attn.v_proj": kd, "self_attn.o_proj": g.dim,
-                         "mlp.gate_proj": g.ff, "mlp.up_proj": g.ff, "mlp.down_proj": g.dim}
-        self.in_dims = {"self_attn.q_proj": g.dim, "self_attn.k_proj": g.dim, "self_attn.v_proj": g.dim,
-                        "self_attn.o_proj": qd, "mlp.gate_proj": g.dim, "mlp.up_proj": g.dim, "mlp.down_proj": g.ff}
+        self.out_dims = {lin.suffix: lin.out for lin in decoder_linears(g)}
+        self.in_dims = {lin.suffix: lin.inp for lin in decoder_linears(g)}
         gen = torch.Generator(device="cpu").manual_seed(seed + 17)
         self.master: dict[str, torch.Tensor] = {}
         self.grads: dict[str, torch.Tensor] = {}
@@ -229,10 +223,10 @@ class LoraState:
         """Per-layer weight dicts ``Backbone.decoder_layer`` runs as they are: ``W + (alpha/r) B A`` for the seven adapted
         projections in the frozen forward layouts (``wqkv``, ``wo``, ``wgu_il`` or ``wgu``, ``wdown``), the norms by
         reference.  The adapters are the bf16 compute copies the forward multiplies by, so the merged decoder represents
-        what ``_decoder_eval`` applies; one rounding per weight (vlb_lora_merge).  The base weights are not touched and
-        the ``_t`` (dgrad) layouts are not merged: nothing differentiates through the result.  Buffers are allocated on
-        the first call and reused; while ``version`` is unchanged (no refresh() / load_state_dict() since the last merge)
-        the cached list is returned and nothing is launched."""
+        what ``decoder_forward(train=False)`` applies; one rounding per weight (vlb_lora_merge).  The base weights are not
+        touched and the ``_t`` (dgrad) layouts are not merged: nothing differentiates through the result.  Buffers are
+        allocated on the first call and reused; while ``version`` is unchanged (no refresh() / load_state_dict() since the
+        last merge) the cached list is returned and nothing is launched."""
         layers = self.w.layers
         if any(lw.get(k) is None for lw in layers for k in ("wqkv", "wo", "wdown", "wgu_il" if self.gu_il else "wgu")):
             raise ValueError("LoraState.merge(): the frozen decoder weights are sharded (Backbone.enable_sharding): a rank holds "
@@ -285,8 +279,8 @@ class LoraState:
     def _workspace(self, M):
         if self._ws is None or self._ws["cap"] < M:          # grow-only: packed batches change M every step
             g, d = self.g, self.dev
-            kmax = max(g.ff, g.dim, g.heads * g.head_dim)
-            kgrp = max(2 * g.ff, (g.heads + 2 * g.kv_heads) * g.head_dim)      # widest dy a group's projections share
+            kmax = max(g.ff, g.dim, g.q_dim)
+            kgrp = max(2 * g.ff, g.q_dim + 2 * g.kv_dim)      # widest dy a group's projections share
             self._ws = dict(cap=M, wg=torch.empty(lib.vlb_wgrad_splits(M) * 48 * kmax, dtype=torch.float32, device=d),
                             uws=torch.empty(lib.vlb_wgrad_u_ws_floats(M, kgrp), dtype=torch.float32, device=d),
                             u_full=torch.zeros(M, self._rpad_max(), dtype=BF16, device=d))
@@ -345,51 +339,32 @@ class LoraState:
         return self.decoder_forward(backbone, x, key_mask, B, layout, train=train)
 
     def decoder_forward(self, backbone, x, key_mask, B, layout=None, train=True):
-        """The adapted decoder on spliced embeddings x [rows, dim] (the part of forward() that keeps activations)."""
+        """The adapted decoder on spliced embeddings x [rows, dim].  train=True draws this step's dropout masks and keeps
+        every layer's activations for backward().  train=False (validation / inference) runs the same layers with dropout
+        off and keeps nothing: it touches neither ``step`` (the dropout seed sequence) nor what a pending backward() reads
+        (``saved``, ``x_last``, ``key_mask``, ``B``, ``layout``), and no activation outlives the layer after its own."""
         g, w = self.g, self.w
-        S = g.max_len
-        pos = None if layout is None else layout.pos
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
-        if not train:
-            return self._decoder_eval(backbone, x, key_mask, B, layout)
-        self.saved = []
-        self.step += 1
+        p = None if train else 0.0                  # None: the configured dropout (_lora_t)
+        if train:
+            self.saved = []
+            self.step += 1
         for li, lay in enumerate(self.layers):
             lw = backbone.layer_weights(li)
-            sd = [self._seed(li, k) for k in range(7)]
+            sd = [self._seed(li, k) for k in range(7)] if train else [None] * 7     # no dropout: no seeds
             h1 = ops.rmsnorm(x, lw["in_norm"], g.rms_eps)
-            qkv, t_qkv = self._adapted(h1, lw["wqkv"], lay["qkv"], sd[0:3], slot=(li, 0))
-            ops.rope_(qkv, w.rope_cos, w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim, pos=pos)
-            a, lse = ops.attention_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, S, g.heads, g.kv_heads,
-                                       g.head_dim, True, g.head_dim ** -0.5, key_mask=key_mask, need_lse=True,
-                                       layout=layout)
-            x2, t_o = self._adapted(a, lw["wo"], lay["o"], sd[3:4], residual=x, slot=(li, 1))
+            qkv, t_qkv = self._adapted(h1, lw["wqkv"], lay["qkv"], sd[0:3], slot=(li, 0), p=p)
+            att = backbone.attention(qkv, key_mask, B, layout, need_lse=train)
+            a, lse = att if train else (att, None)
+            x2, t_o = self._adapted(a, lw["wo"], lay["o"], sd[3:4], residual=x, slot=(li, 1), p=p)
             h2 = ops.rmsnorm(x2, lw["post_norm"], g.rms_eps)
-            hh, gu, t_gu = self._adapted_mlp_in(h2, lw, lay["gu"], sd[4:6], (li, 2))
-            x3, t_d = self._adapted(hh, lw["wdown"], lay["down"], sd[6:7], residual=x2, slot=(li, 3))
-            self.saved.append(dict(x=x, h1=h1, qkv=qkv, a=a, lse=lse, x2=x2, h2=h2, gu=gu, hh=hh, t_qkv=t_qkv, t_o=t_o,
-                                   t_gu=t_gu, t_d=t_d, seeds=sd))
+            hh, gu, t_gu = self._adapted_mlp_in(h2, lw, lay["gu"], sd[4:6], (li, 2), p=p, save=train)
+            x3, t_d = self._adapted(hh, lw["wdown"], lay["down"], sd[6:7], residual=x2, slot=(li, 3), p=p)
+            if train:
+                self.saved.append(dict(x=x, h1=h1, qkv=qkv, a=a, lse=lse, x2=x2, h2=h2, gu=gu, hh=hh, t_qkv=t_qkv, t_o=t_o,
+                                       t_gu=t_gu, t_d=t_d, seeds=sd))
             x = x3
-        self.x_last, self.key_mask, self.B, self.layout = x, key_mask, B, layout
-        return ops.rmsnorm(x, w.final_norm, g.rms_eps), key_mask
-
-    def _decoder_eval(self, backbone, x, key_mask, B, layout):
-        """Adapted decoder without dropout and without saved activations (validation / inference)."""
-        g, w = self.g, self.w
-        S = g.max_len
-        pos = None if layout is None else layout.pos
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
-        for li, lay in enumerate(self.layers):
-            lw = backbone.layer_weights(li)
-            h = ops.rmsnorm(x, lw["in_norm"], g.rms_eps)
-            qkv, _ = self._adapted(h, lw["wqkv"], lay["qkv"], None, slot=(li, 0), p=0.0)
-            ops.rope_(qkv, w.rope_cos, w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim, pos=pos)
-            a = ops.attention_fwd(qkv[:, :qd], qkv[:, qd:qd + kd], qkv[:, qd + kd:], B, S, g.heads, g.kv_heads, g.head_dim,
-                                  True, g.head_dim ** -0.5, key_mask=key_mask, layout=layout)
-            x, _ = self._adapted(a, lw["wo"], lay["o"], None, residual=x, slot=(li, 1), p=0.0)
-            h = ops.rmsnorm(x, lw["post_norm"], g.rms_eps)
-            hh, _, _ = self._adapted_mlp_in(h, lw, lay["gu"], None, (li, 2), p=0.0, save=False)
-            x, _ = self._adapted(hh, lw["wdown"], lay["down"], None, residual=x, slot=(li, 3), p=0.0)
+        if train:
+            self.x_last, self.key_mask, self.B, self.layout = x, key_mask, B, layout
         return ops.rmsnorm(x, w.final_norm, g.rms_eps), key_mask
 
     # ------------------------------------------------------------------ backward
@@ -445,13 +420,9 @@ class LoraState:
     def backward(self, backbone, dhidden):
         """dhidden: d loss / d (post-final-norm hidden) bf16 [B*S, dim].  Fills self.grads."""
         g, w = self.g, self.w
-        B, S = self.B, g.max_len
-        qd, kd = g.heads * g.head_dim, g.kv_heads * g.head_dim
-        layout = self.layout
-        pos = None if layout is None else layout.pos
-        M = self.x_last.shape[0]
+        B, layout = self.B, self.layout
         dx = ops.rmsnorm_bwd(self.x_last, w.final_norm, dhidden, g.rms_eps)
-        delta = torch.empty(B, g.heads, S, dtype=torch.float32, device=self.dev)
+        delta = torch.empty(B, g.heads, g.max_len, dtype=torch.float32, device=self.dev)
         for li in range(g.layers - 1, -1, -1):
             lw, sv = backbone.layer_weights(li, transposed=True, direction=-1), self.saved[li]
             sd = sv["seeds"]
@@ -459,10 +430,7 @@ class LoraState:
             d_h2 = self._group_backward(li, "gu", d_gu, sv["h2"], sv["t_gu"], sd[4:6], lw["wgu_t"], True)
             dx2 = ops.rmsnorm_bwd(sv["x2"], lw["post_norm"], d_h2, g.rms_eps, dx_in=dx)
             d_a = self._group_backward(li, "o", dx2, sv["a"], sv["t_o"], sd[3:4], lw["wo_t"], True)
-            qkv = sv["qkv"]
-            dqkv = ops.attention_bwd(qkv, qd, kd, sv["a"], d_a, sv["lse"], self.key_mask, B, S, g.heads, g.kv_heads,
-                                     g.head_dim, True, g.head_dim ** -0.5, layout=layout, delta=delta)
-            ops.rope_(dqkv, w.rope_cos, w.rope_sin, B, S, g.heads + g.kv_heads, g.head_dim, sign=-1, pos=pos)
+            dqkv = backbone.attention_bwd(sv["qkv"], sv["a"], d_a, sv["lse"], self.key_mask, B, layout, delta)
             need_dx = li > 0                # embeddings / connector are frozen: nothing upstream of layer 0 trains
             d_h1 = self._group_backward(li, "qkv", dqkv, sv["h1"], sv["t_qkv"], sd[0:3], lw["wqkv_t"], need_dx)
             if need_dx:

@@ -116,6 +116,11 @@ def _gemm_workspace(device):
     return ws
 
 
+def _split_k_workspace(device, M, N, K):
+    """The workspace for a long-K GEMM (K: both operand pairs together) with more than one wave of tiles; None otherwise."""
+    return _gemm_workspace(device) if K >= 4096 and M * N > 256 * 192 * 256 else None
+
+
 def gemm(a, w, bias=None, residual=None, act=ACT_NONE, a2=None, w2=None, out=None):
     """out[M,N] = act(a[M,K] @ w[N,K]^T + a2 @ w2^T + bias) + residual   (all bf16, fp32 accumulate)."""
     _dev(a)
@@ -128,7 +133,7 @@ def gemm(a, w, bias=None, residual=None, act=ACT_NONE, a2=None, w2=None, out=Non
     if a2 is not None:
         K2 = a2.shape[1]
         assert w2.shape == (N, K2) and a2.shape[0] == M
-    ws = _gemm_workspace(a.device) if K + K2 >= 4096 and M * N > 256 * 192 * 256 else None    # more than one wave of tiles
+    ws = _split_k_workspace(a.device, M, N, K + K2)
     with _Timed("plain", M, N, K, K2):
         check(lib.vlb_gemm_bf16_ws(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
                                    M, N, K, _p(bias), _p(residual), residual.stride(0) if residual is not None else 0, act,
@@ -152,7 +157,7 @@ def gemm_swiglu_save(a, w_il, a2=None, w2_il=None):
     if a2 is not None:
         K2 = a2.shape[1]
         assert w2_il.shape == (N, K2) and a2.shape[0] == M
-    ws = _gemm_workspace(a.device) if K + K2 >= 4096 and M * N > 256 * 192 * 256 else None
+    ws = _split_k_workspace(a.device, M, N, K + K2)
     with _Timed("gate_up+swiglu", M, N, K, K2):
         check(lib.vlb_gemm_swiglu_save(a.data_ptr(), a.stride(0), w_il.data_ptr(), w_il.stride(0), h.data_ptr(), h.stride(0),
                                        gu.data_ptr(), gu.stride(0), M, N, K, _p(a2), a2.stride(0) if a2 is not None else 0, _p(w2_il),
@@ -174,7 +179,7 @@ def gemm_masked_pair(a, w, a2, w2, p, seed, out=None):
     assert w.shape[1] == K and a2.shape[0] == M and w2.shape[0] == N and a2.shape[1] >= 64 and w2.shape[1] >= 64
     if out is None:
         out = torch.empty(M, N, dtype=BF16, device=a.device)
-    ws = _gemm_workspace(a.device) if K + 64 >= 4096 and M * N > 256 * 192 * 256 else None
+    ws = _split_k_workspace(a.device, M, N, K + 64)
     with _Timed("masked", M, N, K, 64):
         check(lib.vlb_gemm_bf16_masked_pair_ws(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), out.data_ptr(), out.stride(0),
                                                M, N, K, a2.data_ptr(), a2.stride(0), w2.data_ptr(), w2.stride(0), float(p),
@@ -192,7 +197,7 @@ def gemm_masked_pair_swiglu_bwd(dy, w_t, gu, a2, w2, p, seed, out=None):
     assert w_t.shape[1] == K and gu.shape == (M, 2 * ff) and a2.shape[0] == M and w2.shape[0] == ff
     if out is None:
         out = torch.empty(M, 2 * ff, dtype=BF16, device=dy.device)
-    ws = _gemm_workspace(dy.device) if K + 64 >= 4096 and M * ff > 256 * 192 * 256 else None
+    ws = _split_k_workspace(dy.device, M, ff, K + 64)
     with _Timed("masked", M, ff, K, 64):
         check(lib.vlb_gemm_masked_pair_swiglu_bwd(dy.data_ptr(), dy.stride(0), w_t.data_ptr(), w_t.stride(0), gu.data_ptr(), gu.stride(0),
                                                   out.data_ptr(), out.stride(0), M, ff, K, a2.data_ptr(), a2.stride(0), w2.data_ptr(),

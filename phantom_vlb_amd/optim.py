@@ -23,10 +23,7 @@ from __future__ import annotations
 import torch
 
 from ._lib import check, lib
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+from .ops import _stream
 
 
 class VlbAdamW(torch.optim.Optimizer):

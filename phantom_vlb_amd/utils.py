@@ -9,8 +9,8 @@ from __future__ import annotations
 
 import torch
 
-from . import ops  # noqa: F401
 from ._lib import check, lib
+from .ops import _stream
 
 
 try:                                   # a real Callback when Lightning is installed: its Trainer calls every hook by name
@@ -26,10 +26,6 @@ def get_hrf_weight(time_diff: float) -> float:
     restatement of its algorithm in phantom_vlb_amd/episodes.py (unpinned)."""
     from .episodes import get_hrf_weight as _impl
     return _impl(time_diff)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class HRFConvolveLayer:

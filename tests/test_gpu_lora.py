@@ -414,3 +414,36 @@ def test_mini_lora_other_ranks_match_oracle(dev, r, p):
     sd = m.trainable_state_dict()
     assert sd["model.layers.0.self_attn.k_proj.lora_A.weight"].shape == (r, g.dim)
     assert sd["model.layers.0.self_attn.k_proj.lora_B.weight"].shape == (g.kv_heads * g.head_dim, r)
+
+
+def test_validation_between_training_steps_changes_nothing(dev):
+    """A validation_step between two training steps leaves the run where it was: the dropout seed sequence (LoRA step counter,
+    head dropout) and the trained values are those of the run without it, bit for bit, and the validation forward itself is
+    deterministic.  LoRA dropout 0.1 and head dropout 0.2, so a counter the eval forward advanced would draw other masks."""
+    import dataclasses
+    import vlb_oracle as O
+    from phantom_vlb_amd.litmodule import VLBLitModule
+    g = O.geometry_mini()
+    p = O.round_bf16(O.init_params(g, seed=5, lora=True, lora_b_std=0.05))
+    b1, b2, bval = (O.synthetic_batch(g, 2, seed=s) for s in (6, 7, 8))
+
+    def run(validate):
+        m = VLBLitModule(dataclasses.replace(_lora_cfg(0.1), dropout_rate=0.2))
+        m.configure_model(state_dict=p, head_state=p)
+        opt = m.configure_optimizers()[0][0]
+        losses, val = [], None
+        for i, batch in enumerate((b1, b2)):
+            if validate and i == 1:
+                val = m.validation_step(bval), m.validation_step(bval)
+            losses.append(m.training_step(batch).clone())
+            opt.step()
+        return {n: t.clone() for n, t in m.trainable_state_dict().items()}, losses, val
+
+    sd_a, loss_a, _ = run(False)
+    sd_b, loss_b, (v1, v2) = run(True)
+    assert torch.equal(v1["brain_preds"], v2["brain_preds"]) and torch.equal(v1["loss"], v2["loss"])
+    assert all(torch.equal(x, y) for x, y in zip(loss_a, loss_b)), (loss_a, loss_b)
+    assert len(sd_a) == len(sd_b) >= 6 + 28 and any(".lora_B." in n for n in sd_a)
+    bad = [n for n in sd_a if not torch.equal(sd_a[n], sd_b[n])]
+    assert not bad, bad
+    assert not torch.equal(sd_a["model.layers.0.self_attn.q_proj.lora_A.weight"].cpu(), p["model.layers.0.self_attn.q_proj.lora_A.weight"])

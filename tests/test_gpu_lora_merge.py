@@ -295,7 +295,7 @@ def test_export_round_trip_is_bit_exact(dev, tmp_path):
 
 
 def test_default_validation_is_untouched(dev):
-    """Flag off: validation_step is the _decoder_eval forward, bit for bit, and no merged buffer exists."""
+    """Flag off: validation_step is the adapted decoder's train=False forward, bit for bit, and no merged buffer exists."""
     import vlb_oracle as O
     from phantom_vlb_amd import ops
     g = O.geometry_mini()
@@ -303,15 +303,21 @@ def test_default_validation_is_untouched(dev):
     batch = O.synthetic_batch(g, 4, seed=1234)
     m = _module(p)
     assert m.config.merge_lora_for_eval is False
-    calls = []
-    inner = m.lora._decoder_eval
-    m.lora._decoder_eval = lambda *a, **k: (calls.append(1), inner(*a, **k))[1]
+    calls, trains = [], []
+    inner = m.lora.decoder_forward
+
+    def spy(backbone, x, key_mask, B, layout=None, train=True):
+        calls.append(1)
+        trains.append(train)
+        return inner(backbone, x, key_mask, B, layout, train=train)
+    m.lora.decoder_forward = spy
     launches = ops.merge_launches
     out = m.validation_step(batch)
     assert calls == [1] and ops.merge_launches == launches
+    assert trains == [False]
     assert getattr(m.lora, "_merged", None) is None
     # the same forward by hand: adapted eval decoder, then the head
-    m.lora._decoder_eval = inner
+    del m.lora.decoder_forward
     layout = m.backbone.row_layout(batch["language"], batch["padvals"])
     ids = batch["language"].to(m.device).long()
     wm = m.make_weight_mask(batch["padvals"], batch["vis_weights"], batch["lang_weights"], ids.shape[1], g.max_len)

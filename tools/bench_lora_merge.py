@@ -138,7 +138,7 @@ def model():
         for merged in (True, False):
             ts[merged].append(median_ms([lambda: val(merged)] * 3, warmup=0))
     tm, tu = statistics.median(ts[True]), statistics.median(ts[False])
-    say(f"validation step, unmerged (_decoder_eval)        {tu:9.2f} ms   rounds: " + " ".join(f"{t:.2f}" for t in ts[False]))
+    say(f"validation step, unmerged (adapted decoder)      {tu:9.2f} ms   rounds: " + " ".join(f"{t:.2f}" for t in ts[False]))
     say(f"validation step, merged (frozen path)            {tm:9.2f} ms   rounds: " + " ".join(f"{t:.2f}" for t in ts[True]))
     say(f"saving per validation batch                      {tu - tm:9.2f} ms   ({(tu - tm) / tu * 100:.1f}%)")
     if tu > tm:
