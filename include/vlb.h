@@ -285,6 +285,49 @@ int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const void* ridge_
                         float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, float eps,
                         float l2_lambda, float loss_scale, float l2_scale, void* stream);
 
+/* Correlation training objectives of the brain head (opt-in; the four entry points above are the MSE path and keep
+ * their bits).  Per clip b over the V targets, with p = pred[b,:] and y = y[b,:]:
+ *   cosine :  u = p,           t = y            (mu_p = mu_y = 0)
+ *   pearson:  u = p - mean(p), t = y - mean(y)  (needs V >= 2)
+ *   nu = max(||u||, 1e-8), nt = max(||t||, 1e-8)  (the clamp of torch.nn.functional.cosine_similarity)
+ *   c_b = <u,t> / (nu nt);   data term = 1 - mean_b c_b;   loss_terms = {data term, lambda*||W||_F^2, their sum}
+ *   d pred[b,v] = a_b (p_v - mu_p) + b_b (y_v - mu_y),  b_b = -s/(B nu nt),  a_b = s c_b/(B nu ||u||), 0 where ||u|| = 0
+ *   (s = loss_scale).  a_b is s c_b/(B nu^2) wherever the norm is not clamped; under the clamp it is what autograd gives
+ *   for F.cosine_similarity (the clamp acts on the norm's value only).  An all-zero target row gives c_b = 0 and a zero
+ *   gradient; nothing is ever NaN.
+ * loss_kind: VLB_LOSS_COSINE or VLB_LOSS_PEARSON; VLB_LOSS_MSE is refused here (VLB_ERR_INVALID), as are pearson with
+ * V < 2 and null pointers.
+ * rowstat: fp32 [B,8] = {mu_p, mu_y, sum u^2, sum t^2, sum u t, c_b, 0, 0};  loss_aux: fp32 [2] = {mean((pred-y)^2), mean_b c_b}. */
+#define VLB_LOSS_MSE 0
+#define VLB_LOSS_COSINE 1
+#define VLB_LOSS_PEARSON 2
+/* The cosine alternative the reference's training_step docstring names first,
+ * `1 - F.cosine_similarity(brain_encoding, y, dim=-1).mean() + l2_reg` (src/litmodule/videollama2_vlb_litmodule.py:290-301),
+ * and its row-centred form (the correlation a run is scored on, val_corr_avg).  Runs after vlb_head_fwd or
+ * vlb_head_fwd_cached on their outputs `pred` and `ws`, before anything else touches ws: fills rowstat and loss_aux and
+ * rewrites loss_terms[0] and [2]; loss_terms[1] comes out with the bits the forward wrote.  The l2 term and the MSE are
+ * summed again from the ridge forward's per-block partials inside ws (so a repeated call gives the same result); S says
+ * where they are: the S handed to vlb_head_fwd, or 0 after vlb_head_fwd_cached. */
+int vlb_head_loss_fwd(const float* pred, const float* y, const float* ws, float* rowstat, float* loss_terms, float* loss_aux,
+                      int B, int S, int E, int V, int loss_kind, float l2_lambda, void* stream);
+/* vlb_head_bwd for the objective of vlb_head_loss_fwd (reference docstring :290-301 as above): the same launches with
+ * d pred taken from rowstat instead of gscale*(pred - y); l2_scale and everything behind dz are unchanged.  ws holds
+ * vlb_head_ws_floats(B,S,E,V) floats (4 per clip are used for the coefficients a_b, b_b, mu_p, mu_y). */
+int vlb_head_bwd_loss(const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w, const void* ridge_w,
+                      const float* y, const float* keep_scale, const float* stats, const float* pooled_raw,
+                      const float* sumw, const float* zhat, const float* ln2_rstd, const void* z, const float* pred,
+                      float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b,
+                      float* ws, float* dz_ws, float* dpooled_ws, void* dhidden, int B, int S, int E, int V, float eps,
+                      float l2_lambda, float loss_scale, float l2_scale, const int* cu_rows, int total_rows, void* stream,
+                      int loss_kind, const float* rowstat);
+/* vlb_head_bwd_cached for the objective of vlb_head_loss_fwd (reference docstring :290-301 as above). */
+int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
+                             const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd,
+                             const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w,
+                             float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B,
+                             int E, int V, float eps, float l2_lambda, float loss_scale, float l2_scale, void* stream,
+                             int loss_kind, const float* rowstat);
+
 /* ---------------------------------------------------------------------------------------------
  * LoRA adapters (peft LoraConfig(r, lora_alpha, lora_dropout) + get_peft_model, litmodule :113-120):
  *   y = x W^T + s * B(A(dropout_p(x))),  s = alpha/r; only A [r,in] and B [out,r] train.

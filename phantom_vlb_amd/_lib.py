@@ -58,6 +58,9 @@ SIGNATURES = {
     "vlb_feature_cache_store": [P] * 5 + [I, I, I, P],
     "vlb_head_fwd_cached": [P] * 19 + [I, I, I, I, F, F, P],
     "vlb_head_bwd_cached": [P] * 20 + [I, I, I, F, F, F, F, P],
+    "vlb_head_loss_fwd": [P] * 6 + [I, I, I, I, I, F, P],
+    "vlb_head_bwd_loss": [P] * 24 + [I, I, I, I, F, F, F, F, P, I, P, I, P],
+    "vlb_head_bwd_cached_loss": [P] * 20 + [I, I, I, F, F, F, F, P, I, P],
     "vlb_gemm_bf16_masked_pair": [P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P],
     "vlb_gemm_masked_pair_swiglu_bwd": [P, I, P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P, L, P],
     "vlb_gemm_bf16_masked_pair_ws": [P, I, P, I, P, I, I, I, I, P, I, P, I, F, ctypes.c_uint32, P, L, P],

@@ -1,6 +1,7 @@
 // Fused brain head (the arithmetic the reference itself owns):
 //   hidden --LN1--> sum_s w[b,s]*(.) --LN2--> dropout --Linear(E->V)--> pred ; loss = MSE + lambda*||W||^2
 // reference: src/litmodule/videollama2_vlb_litmodule.py:245-254,302 ; src/utils.py:56,66-71.
+// Opt-in objectives in place of the MSE (its docstring :290-301): 1 - mean_b cos(pred_b, y_b), plain or row-centred (Pearson).
 //
 // HBM-bound.  The LN1-normalised [B,S,E] tensor is never materialised: because LN1's affine is
 // per-column,   pooled[e] = g1[e] * sum_s w_s*rstd_s*(x_se - mu_s) + b1[e] * sum_s w_s,
@@ -361,20 +362,142 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restr
   }
 }
 
+// ---------------------------------------------------------------- correlation objectives (cosine / pearson), forward
+// Reference: the training_step docstring of src/litmodule/videollama2_vlb_litmodule.py:290-301 names
+//   1 - F.cosine_similarity(brain_encoding, y, dim=-1).mean() + l2_reg ;  pearson is the same on row-centred inputs.
+// Row statistics, one block of 1024 per clip: rowstat[b] = {mu_p, mu_y, sum u^2, sum t^2, sum u t, c_b, 0, 0} with
+// u = p - mu_p, t = y - mu_y (mu = 0 for cosine: the mean pass is skipped).  Two passes (means, then centred sums), so a
+// common offset of the rows costs nothing.  A row of [B,V] fp32 starts at element b*V, 16-byte aligned only when that is a
+// multiple of 4: up to 3 head elements one per thread, f32x4 body, up to 3 tail elements; when pred and y rows differ in
+// alignment everything goes the scalar way.  A thread adds head, body, tail in that order into one accumulator per
+// quantity; block_sum is wave_sum + the 16 wave partials in order: fixed order, no atomics.
+__device__ __forceinline__ void row_split(const float* p, const float* q, int V, int& head, int& nvec) {
+  const uintptr_t ap = reinterpret_cast<uintptr_t>(p), aq = reinterpret_cast<uintptr_t>(q);
+  if ((ap & 15) != (aq & 15)) { head = V; nvec = 0; return; }        // scalar throughout
+  head = (int)(((16 - (ap & 15)) & 15) >> 2);
+  if (head > V) head = V;
+  nvec = (V - head) >> 2;
+}
+
+template <bool CENTRE>
+__global__ __launch_bounds__(1024) void head_rowstat_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                            float* __restrict__ rowstat, int V) {
+  __shared__ float red[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* pr = pred + (int64_t)b * V;
+  const float* yr = y + (int64_t)b * V;
+  int head, nvec;
+  row_split(pr, yr, V, head, nvec);
+  const int tail0 = head + 4 * nvec;             // first tail element
+  float mp = 0.f, my = 0.f;
+  if constexpr (CENTRE) {
+    float sp = 0.f, sy = 0.f;
+    for (int i = tid; i < head; i += 1024) { sp += pr[i]; sy += yr[i]; }
+    for (int k = tid; k < nvec; k += 1024) {
+      const f32x4 a = *reinterpret_cast<const f32x4*>(pr + head + 4 * k), c = *reinterpret_cast<const f32x4*>(yr + head + 4 * k);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { sp += a[j]; sy += c[j]; }
+    }
+    for (int i = tail0 + tid; i < V; i += 1024) { sp += pr[i]; sy += yr[i]; }
+    mp = block_sum(sp, red) / V;
+    my = block_sum(sy, red) / V;
+  }
+  float suu = 0.f, stt = 0.f, sut = 0.f;
+  for (int i = tid; i < head; i += 1024) {
+    const float u = pr[i] - mp, t = yr[i] - my;
+    suu += u * u; stt += t * t; sut += u * t;
+  }
+  for (int k = tid; k < nvec; k += 1024) {
+    const f32x4 a = *reinterpret_cast<const f32x4*>(pr + head + 4 * k), c = *reinterpret_cast<const f32x4*>(yr + head + 4 * k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float u = a[j] - mp, t = c[j] - my;
+      suu += u * u; stt += t * t; sut += u * t;
+    }
+  }
+  for (int i = tail0 + tid; i < V; i += 1024) {
+    const float u = pr[i] - mp, t = yr[i] - my;
+    suu += u * u; stt += t * t; sut += u * t;
+  }
+  suu = block_sum(suu, red);
+  stt = block_sum(stt, red);
+  sut = block_sum(sut, red);
+  if (tid == 0) {
+    const float nu = fmaxf(sqrtf(suu), 1e-8f), nt = fmaxf(sqrtf(stt), 1e-8f);      // F.cosine_similarity's clamp
+    float* o = rowstat + (int64_t)b * 8;
+    o[0] = mp; o[1] = my; o[2] = suu; o[3] = stt; o[4] = sut; o[5] = sut / (nu * nt); o[6] = 0.f; o[7] = 0.f;
+  }
+}
+
+// loss_finalize_kernel for the correlation objectives: the same sums over lpart (so out[1] has the bits loss_finalize_kernel
+// gave it), the data term 1 - mean_b c_b from rowstat summed in clip order in double, and the plain MSE the ridge forward
+// accumulated anyway -> aux[0] (aux[1] = mean_b c_b).
+__global__ __launch_bounds__(256) void loss_finalize_corr_kernel(const float* __restrict__ lpart, int nblk, float inv_bv, float lambda,
+                                                                 const float* __restrict__ rowstat, int B, float* __restrict__ out,
+                                                                 float* __restrict__ aux) {
+  __shared__ double sm[2][256];
+  double mse = 0.0, w2 = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) { mse += lpart[2 * i]; w2 += lpart[2 * i + 1]; }
+  sm[0][threadIdx.x] = mse; sm[1][threadIdx.x] = w2;
+  __syncthreads();
+  for (int s2 = 128; s2 > 0; s2 >>= 1) {
+    if ((int)threadIdx.x < s2) { sm[0][threadIdx.x] += sm[0][threadIdx.x + s2]; sm[1][threadIdx.x] += sm[1][threadIdx.x + s2]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double cs = 0.0;
+    for (int b = 0; b < B; ++b) cs += rowstat[(int64_t)b * 8 + 5];
+    cs /= B;
+    out[0] = (float)(1.0 - cs);
+    out[1] = (float)(lambda * sm[1][0]);
+    out[2] = out[0] + out[1];
+    aux[0] = (float)(sm[0][0] * inv_bv);
+    aux[1] = (float)cs;
+  }
+}
+
+// backward of the correlation objectives, first launch: coef[b] = {a_b, b_b, mu_p, mu_y} from rowstat and loss_scale,
+//   b_b = -s / (B nu nt),  a_b = s c_b / (B nu ||u||)  (0 where ||u|| = 0).  Where the norm is not clamped that is
+// s c_b / (B nu^2).  Under the clamp it is what autograd gives for F.cosine_similarity, which clamps the norm's VALUE under
+// no_grad and differentiates the norm itself: the kernels follow autograd there, not the derivative of the clamped function.
+__global__ void head_loss_coef_kernel(const float* __restrict__ rowstat, float* __restrict__ coef, int B, float loss_scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const float* r = rowstat + (int64_t)b * 8;
+  const float ru = sqrtf(r[2]), nu = fmaxf(ru, 1e-8f), nt = fmaxf(sqrtf(r[3]), 1e-8f);
+  const float sb = loss_scale / (float)B;
+  coef[4 * b] = ru > 0.f ? sb * r[5] / (nu * ru) : 0.f;
+  coef[4 * b + 1] = -sb / (nu * nt);
+  coef[4 * b + 2] = r[0];
+  coef[4 * b + 3] = r[1];
+}
+
+// d pred of the correlation objectives (CORR forms of the three kernels below): coef[b] = {a_b, b_b, mu_p, mu_y}, filled by
+// head_loss_coef_kernel;  d pred[b,v] = a_b (p - mu_p) + b_b (y - mu_y).  The centred form: rows may sit on a large offset.
+__device__ __forceinline__ float dpred_corr(const float* __restrict__ coef, int b, float p, float yv) {
+  const float* c = coef + 4 * b;
+  return c[0] * (p - c[2]) + c[1] * (yv - c[3]);
+}
+
 // d pred^T as the skinny-wgrad G operand: dpT[v, b] = gscale * (pred[b,v] - y[b,v]) for b < B, 0 for b < 16
+template <bool CORR>
 __global__ void dpred_t_kernel(const float* __restrict__ pred, const float* __restrict__ y, bf16* __restrict__ dpT, int B,
-                               int V, float gscale) {
+                               int V, float gscale, const float* __restrict__ coef) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= (int64_t)V * 16) return;
   const int v = i >> 4, b = i & 15;
-  dpT[i] = (bf16)(b < B ? gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]) : 0.f);
+  if constexpr (CORR)
+    dpT[i] = (bf16)(b < B ? dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]) : 0.f);
+  else
+    dpT[i] = (bf16)(b < B ? gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]) : 0.f);
 }
 
 // ---------------------------------------------------------------- backward 1: dW, dbias   (z staged in LDS)
+template <bool CORR>
 __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict__ W, const bf16* __restrict__ z,
                                                           const float* __restrict__ pred, const float* __restrict__ y,
                                                           float* __restrict__ dW, float* __restrict__ dbias, int B, int E,
-                                                          int V, float gscale, float l2coef) {
+                                                          int V, float gscale, float l2coef, const float* __restrict__ coef) {
   extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int b0 = 0; b0 < B; b0 += BMAX) {
@@ -390,7 +513,10 @@ __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict
       float db = 0.f;
 #pragma unroll
       for (int i = 0; i < BMAX; ++i) {
-        dp[i] = i < nb ? gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]) : 0.f;
+        if constexpr (CORR)
+          dp[i] = i < nb ? dpred_corr(coef, b0 + i, pred[(int64_t)(b0 + i) * V + v], y[(int64_t)(b0 + i) * V + v]) : 0.f;
+        else
+          dp[i] = i < nb ? gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]) : 0.f;
         db += dp[i];
       }
       if (lane == 0) dbias[v] = (b0 == 0 ? 0.f : dbias[v]) + db;
@@ -424,9 +550,10 @@ __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict
 }
 // ---------------------------------------------------------------- backward 2: dz partials over V splits
 // grid (ceil(E/512), DZ_SPLIT), block 256 (4 waves share a split's rows); out part[split][B][E]
+template <bool CORR>
 __global__ __launch_bounds__(256) void ridge_bwd_z_kernel(const bf16* __restrict__ W, const float* __restrict__ pred,
                                                           const float* __restrict__ y, float* __restrict__ part, int B,
-                                                          int E, int V, float gscale) {
+                                                          int E, int V, float gscale, const float* __restrict__ coef) {
   __shared__ float red[3][BMAX][512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 512 + lane * 8;
@@ -445,7 +572,9 @@ __global__ __launch_bounds__(256) void ridge_bwd_z_kernel(const bf16* __restrict
 #pragma unroll
         for (int i = 0; i < BMAX; ++i) {
           if (i < nb) {
-            const float dp = gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]);
+            float dp;
+            if constexpr (CORR) dp = dpred_corr(coef, b0 + i, pred[(int64_t)(b0 + i) * V + v], y[(int64_t)(b0 + i) * V + v]);
+            else dp = gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]);
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] += dp * w[j];
           }
@@ -628,7 +757,9 @@ int reserve_ridge_lds(int bytes) {
   static int reserved = 0;
   if (bytes > reserved) {
     hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e2 == hipSuccess)
+      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e1 != hipSuccess || e2 != hipSuccess) { vlb_set_error("head: cannot reserve %d bytes of LDS for z", bytes); return VLB_ERR_LAUNCH; }
     reserved = bytes;
   }
@@ -647,6 +778,21 @@ int launch_pool(const bf16* hidden, const float* wmask, float* partial, float* s
   hipLaunchKernelGGL((head_pool_kernel<NI>), grid, dim3(512), lds, st, hidden, wmask, partial, stats, S, E, eps, cu);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
+}
+
+// floats of ws the backward uses (the dz partials, or the skinny-wgrad slabs + dz16 + d pred^T): the coefficients of the
+// correlation objectives (4 per clip) sit right behind, wherever vlb_head_fwd put its own slabs.
+int64_t head_bwd_ws_floats(int B, int E, int V) {
+  const int64_t dz = (int64_t)DZ_SPLIT * B * E;
+  const int64_t dz_mfma = (int64_t)vlb_wgrad_splits(V) * 16 * E + (int64_t)16 * E + ((int64_t)V * 16 + 1) / 2 + 64;
+  return dz_mfma > dz ? dz_mfma : dz;
+}
+
+// (sum err^2, sum W^2) pairs head_fwd_tail's ridge launch leaves in lpart: one per block, a restatement of its grid
+int ridge_fwd_parts(int B, int E, int V) {
+  const bool mfma = B <= 16 && E % 128 == 0 && E <= 4096;
+  const int ntiles = (V + 15) / 16;
+  return mfma ? (ntiles < 2048 ? ntiles : 2048) : (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
 }
 
 // LN1 affine + LN2 + dropout -> z, ridge GEMV, loss: everything of the forward that reads only (pooled_raw, sumw).
@@ -692,14 +838,24 @@ int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, c
                     const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd, const void* z,
                     const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
                     float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, float l2_lambda,
-                    float loss_scale, float l2_scale, void* stream) {
+                    float loss_scale, float l2_scale, void* stream, int loss_kind = 0, const float* rowstat = nullptr) {
   hipStream_t st = as_stream(stream);
   const float gscale = loss_scale * 2.f / ((float)B * (float)V);
   const int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
   const int zlds = (B < BMAX ? B : BMAX) * E * 2;
   if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
-  hipLaunchKernelGGL(ridge_bwd_w_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
-                     d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda);
+  // correlation objectives: the per-clip coefficients live behind everything the backward keeps in ws
+  float* coef = ws + head_bwd_ws_floats(B, E, V);
+  const bool corr = loss_kind != 0;
+  if (corr) {
+    hipLaunchKernelGGL(head_loss_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rowstat, coef, B, loss_scale);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ridge_bwd_w_kernel<true>, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
+                       d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda, coef);
+  } else {
+    hipLaunchKernelGGL(ridge_bwd_w_kernel<false>, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
+                       d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda, coef);
+  }
   VLB_LAUNCH_CHECK();
   if (B <= 16 && E % 8 == 0) {
     // dz[b,e] = sum_v dpred[b,v] W[v,e]: contraction over the ROWS of W -> the MFMA skinny-wgrad kernel
@@ -708,15 +864,18 @@ int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, c
     float* wg_ws = ws;                                             // [splits][16][E]
     float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
     bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [V][16] bf16
-    hipLaunchKernelGGL(dpred_t_kernel, dim3((unsigned)(((int64_t)V * 16 + 255) / 256)), dim3(256), 0, st, pred, y, dpT, B, V, gscale);
+    const dim3 tgrid((unsigned)(((int64_t)V * 16 + 255) / 256));
+    if (corr) hipLaunchKernelGGL(dpred_t_kernel<true>, tgrid, dim3(256), 0, st, pred, y, dpT, B, V, gscale, coef);
+    else hipLaunchKernelGGL(dpred_t_kernel<false>, tgrid, dim3(256), 0, st, pred, y, dpT, B, V, gscale, coef);
     VLB_LAUNCH_CHECK();
     int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, V, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
     if (rc3 != VLB_OK) return rc3;
     hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
     VLB_LAUNCH_CHECK();
   } else {
-    hipLaunchKernelGGL(ridge_bwd_z_kernel, dim3((E + 511) / 512, DZ_SPLIT), dim3(256), 0, st, (const bf16*)ridge_w, pred,
-                       y, ws, B, E, V, gscale);
+    const dim3 zgrid((E + 511) / 512, DZ_SPLIT);
+    if (corr) hipLaunchKernelGGL(ridge_bwd_z_kernel<true>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, ws, B, E, V, gscale, coef);
+    else hipLaunchKernelGGL(ridge_bwd_z_kernel<false>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, ws, B, E, V, gscale, coef);
     VLB_LAUNCH_CHECK();
     hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
     VLB_LAUNCH_CHECK();
@@ -734,11 +893,9 @@ extern "C" int vlb_head_partial_rows(int S) { return (S + POOL_ROWS - 1) / POOL_
 extern "C" int64_t vlb_head_ws_floats(int B, int S, int E, int V) {
   const int64_t pool = (int64_t)B * vlb_head_partial_rows(S) * (E + 2);
   const int64_t ridge = 2 * (int64_t)((V + RIDGE_ROWS - 1) / RIDGE_ROWS);
-  const int64_t dz = (int64_t)DZ_SPLIT * B * E;
-  const int64_t dz_mfma = (int64_t)vlb_wgrad_splits(V) * 16 * E + (int64_t)16 * E + ((int64_t)V * 16 + 1) / 2 + 64;
-  int64_t m = pool + ridge;
-  if (dz > m) m = dz;
-  return dz_mfma > m ? dz_mfma : m;
+  const int64_t bwd = head_bwd_ws_floats(B, E, V) + 4 * (int64_t)B;      // + coef[B][4] of the correlation objectives
+  const int64_t m = pool + ridge;
+  return bwd > m ? bwd : m;
 }
 
 extern "C" int vlb_head_fwd(const void* hidden, const float* wmask, const void* ln1_w, const void* ln1_b,
@@ -836,6 +993,75 @@ extern "C" int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const v
   return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
                          d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
                          stream);
+}
+
+// ---------------------------------------------------------------- correlation objectives: entry points
+extern "C" int vlb_head_loss_fwd(const float* pred, const float* y, const float* ws, float* rowstat, float* loss_terms,
+                                 float* loss_aux, int B, int S, int E, int V, int loss_kind, float l2_lambda, void* stream) {
+  VLB_REQUIRE(pred && y && ws && rowstat && loss_terms && loss_aux, "head_loss_fwd: null argument");
+  VLB_REQUIRE(loss_kind != VLB_LOSS_MSE, "head_loss_fwd: loss_kind 0 (mse) is what vlb_head_fwd itself computes");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_loss_fwd: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(B > 0 && S >= 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_loss_fwd: bad shape B=%d S=%d E=%d V=%d", B, S, E, V);
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_loss_fwd: pearson needs V >= 2 (V=%d)", V);
+  hipStream_t st = as_stream(stream);
+  // where the forward left the ridge partials: behind the pooling slabs (vlb_head_fwd), or at ws (vlb_head_fwd_cached)
+  const float* lpart = ws + (S > 0 ? (int64_t)B * vlb_head_partial_rows(S) * (E + 2) : 0);
+  if (loss_kind == VLB_LOSS_PEARSON) hipLaunchKernelGGL(head_rowstat_kernel<true>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+  else hipLaunchKernelGGL(head_rowstat_kernel<false>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_finalize_corr_kernel, dim3(1), dim3(256), 0, st, lpart, ridge_fwd_parts(B, E, V),
+                     1.f / ((float)B * (float)V), l2_lambda, rowstat, B, loss_terms, loss_aux);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_bwd_loss(const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w,
+                                 const void* ridge_w, const float* y, const float* keep_scale, const float* stats,
+                                 const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd,
+                                 const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w,
+                                 float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws,
+                                 void* dhidden, int B, int S, int E, int V, float eps, float l2_lambda, float loss_scale,
+                                 float l2_scale, const int* cu_rows, int total_rows, void* stream, int loss_kind,
+                                 const float* rowstat) {
+  (void)eps;
+  VLB_REQUIRE(hidden && wmask && ln1_w && ln2_w && ridge_w && y && stats && pooled_raw && sumw && zhat && ln2_rstd && z &&
+                  pred && d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws && rowstat,
+              "head_bwd_loss: null argument");
+  VLB_REQUIRE(loss_kind != VLB_LOSS_MSE, "head_bwd_loss: loss_kind 0 (mse) is vlb_head_bwd's");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_bwd_loss: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_loss: bad shape");
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_loss: pearson needs V >= 2 (V=%d)", V);
+  const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
+  VLB_REQUIRE(!dhidden || (rows > 0 && rows <= (int64_t)B * S), "head_bwd_loss: total_rows=%d out of range", total_rows);
+  if (int rc = head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
+                               d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale,
+                               l2_scale, stream, loss_kind, rowstat))
+    return rc;
+  if (dhidden) {
+    hipLaunchKernelGGL(head_dhidden_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), (const bf16*)hidden,
+                       wmask, stats, dpooled_ws, (bf16*)dhidden, S, E, rows, B, cu_rows);
+    VLB_LAUNCH_CHECK();
+  }
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
+                                        const float* keep_scale, const float* pooled_raw, const float* sumw, const float* zhat,
+                                        const float* ln2_rstd, const void* z, const float* pred, float* d_ridge_w,
+                                        float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws,
+                                        float* dz_ws, float* dpooled_ws, int B, int E, int V, float eps, float l2_lambda,
+                                        float loss_scale, float l2_scale, void* stream, int loss_kind, const float* rowstat) {
+  (void)eps;
+  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w && d_ridge_b &&
+                  d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws && rowstat,
+              "head_bwd_cached_loss: null argument");
+  VLB_REQUIRE(loss_kind != VLB_LOSS_MSE, "head_bwd_cached_loss: loss_kind 0 (mse) is vlb_head_bwd_cached's");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_bwd_cached_loss: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(B > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_cached_loss: bad shape");
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_cached_loss: pearson needs V >= 2 (V=%d)", V);
+  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
+                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
+                         stream, loss_kind, rowstat);
 }
 
 // ---------------------------------------------------------------- the exported layers on their own

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
-from .head import HEAD_PARAMS, BrainHead
+from .head import HEAD_PARAMS, BrainHead, check_loss
 from .optim import VlbAdamW
 
 
@@ -167,6 +167,7 @@ class VLBLitModuleConfig:
     cache_features: bool = False    # frozen backbone only: keep each clip's pooled features, later epochs run the head alone
     feature_cache_dir: str | None = None    # persist the feature caches there (feature_cache.py; loaded on a matching fingerprint)
     merge_lora_for_eval: bool = False   # LoRA only: eval-mode forwards run the frozen-path decoder on merged weights (LoraState.merge)
+    loss: str = "mse"               # "mse" (reference :302) | "cosine" (its docstring's alternative, :290-301) | "pearson"; + l2 always
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -176,6 +177,7 @@ class VLBLitModuleConfig:
                              "with LoRA or a full fine-tune the backbone's output changes every step")
         if self.merge_lora_for_eval and not self.use_lora:
             raise ValueError("merge_lora_for_eval=True needs use_lora=True: without adapters there is nothing to merge")
+        check_loss(self.loss, self.num_target)
 
 
 def resolve_geometry(cfg: VLBLitModuleConfig) -> Geometry:
@@ -267,7 +269,8 @@ class VLBLitModule(_Base):
         self.backbone = Backbone(g, weights)
         self.nnmodule = _Attr(config=_Attr(hidden_size=g.dim, tokenizer_model_max_length=g.max_len,
                                            num_frames=g.num_frames, use_cache=False), backbone=self.backbone)
-        self.head = BrainHead(g.dim, cfg.num_target, cfg.l2_lambda, g.ln_eps, dev, sd=head_state, seed=cfg.init_seed)
+        self.head = BrainHead(g.dim, cfg.num_target, cfg.l2_lambda, g.ln_eps, dev, sd=head_state, seed=cfg.init_seed,
+                              loss=getattr(cfg, "loss", "mse"))
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -606,7 +609,9 @@ class VLBLitModule(_Base):
             opt.accumulate(j, last)
             self._micro, self._window_closed = j + 1, last
         self._attach_gradients()
-        self.log("train/brain_loss", terms[2])
+        self.log("train/brain_loss", terms[2])           # the objective being trained (config.loss) + l2
+        if self.head.loss_kind:
+            self.log("train/brain_mse", self.head.loss_aux[0])       # the plain MSE, which the ridge forward sums anyway
         if _LP is None:
             return terms[2]          # no Lightning in this process: the plain loss value, as the built-in runner reads it
         # a scalar Lightning's automatic optimisation can call .backward() on (see _ExplicitLoss)
@@ -621,6 +626,8 @@ class VLBLitModule(_Base):
         self.train(was)
         loss = terms[2].clone()
         self.log("val/brain_loss", loss)
+        if self.head.loss_kind:
+            self.log("val/brain_mse", self.head.loss_aux[0].clone())
         return {"loss": loss, "brain_preds": pred.clone(), "brain_vals": y}
 
     # ------------------------------------------------------------------ hooks Lightning's fit loop calls (reference train.py:41-56)

@@ -1,6 +1,7 @@
 """Achieved HBM GB/s of the memory-bound kernels at the 7B / B=5 shapes (algorithmic bytes / HIP-event time).
 
   python tools/bench_hbm_kernels.py            # prints a table; peak HBM3E = 8000 GB/s spec, ~6300 achievable
+  python tools/bench_hbm_kernels.py --head-loss [mse,cosine,pearson]    # only: head forward + backward per training objective
 """
 import os
 import sys
@@ -114,5 +115,29 @@ def main():
         torch.cuda.empty_cache()
 
 
+def head_loss(losses=("mse", "cosine", "pearson")):
+    """Head forward and backward (parameter gradients, no d hidden) per training objective at B=3, S=2048, E=4096: the
+    correlation objectives add vlb_head_loss_fwd's two launches to the forward and one coefficient launch to the backward."""
+    B, S, E = 3, 2048, 4096
+    g = torch.Generator(device=dev).manual_seed(0)
+    x = torch.randn(B * S, E, device=dev, generator=g).to(BF)
+    wm = torch.rand(B, S, device=dev, generator=g)
+    wm[:, :700] = 0
+    print(f"{'objective':10s} {'V':>6s} {'fwd us':>9s} {'bwd us':>9s} {'fwd+bwd us':>11s}")
+    for Vh in (2048, 65536):
+        yy = torch.randn(B, Vh, device=dev, generator=g)
+        for loss in losses:
+            head = BrainHead(E, Vh, 1e-3, 1e-5, dev, **({} if loss == "mse" else {"loss": loss}))
+            t_f = min(timeit(lambda: head.forward(x, wm, yy), reps=20) for _ in range(3))
+            t_b = min(timeit(lambda: head.backward(need_dhidden=False), reps=20) for _ in range(3))
+            print(f"{loss:10s} {Vh:6d} {t_f * 1e3:9.1f} {t_b * 1e3:9.1f} {(t_f + t_b) * 1e3:11.1f}", flush=True)
+            del head
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    main()
+    if "--head-loss" in sys.argv:
+        i = sys.argv.index("--head-loss")
+        head_loss(tuple(sys.argv[i + 1].split(",")) if len(sys.argv) > i + 1 else ("mse", "cosine", "pearson"))
+    else:
+        main()
