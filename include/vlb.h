@@ -90,13 +90,13 @@ int vlb_gemm_swiglu_save(const void* A, int lda, const void* W_il, int ldw, void
                          int K, const void* A2, int lda2, const void* W2_il, int ldw2, int K2, void* ws, int64_t ws_bytes,
                          void* stream);
 int64_t vlb_gemm_workspace_bytes(void);
-/* How a long-K GEMM (K + K2 >= 4096, N % 256 == 0) is cut on the four-wave kernel: tile rows (192|256) * 1000 +
- * tail mode * 100 + K splits; tail mode 0 = whole tiles, 1 = partial wave re-cut into 256x128 halves, 2 = split-K
- * through the workspace.  0 for other shapes.  with_workspace: 0 none, 1 vlb_gemm_bf16_ws, 3 vlb_gemm_bf16_masked_pair_ws
- * (K2 = 64).  Pure host arithmetic (tests). */
+/* How a long-K GEMM (K + K2 >= 4096, N % 256 == 0) is cut on the four-wave kernel's 256-column tiles: tile rows
+ * (192|256) * 1000 + tail mode * 100 + K splits; tail mode 0 = whole tiles, 1 = partial wave re-cut into 256x128 halves,
+ * 2 = split-K through the workspace.  0 for other shapes.  with_workspace: 0 none, 1 vlb_gemm_bf16_ws,
+ * 3 vlb_gemm_bf16_masked_pair_ws (K2 = 64).  This is the planner the dispatch runs (the route the GEMM entry points
+ * launch from), asked with every alignment rule met; pure host arithmetic (tests). */
 int vlb_gemm_plan(int M, int N, int K, int K2, int with_workspace);
 
-/* Which kernel vlb_gemm_bf16 picks for a shape: 0 = generic 64x64, 1 = 256x256, 2 = 256x128. */
 /* LoRA backward through dropout in ONE GEMM (peft: dx = dy.W + dropout_mask * (u.A) / (1-p)):
  *   C[M,N] = A[M,K].W[N,K]^T + keep(m,n)/(1-p) * (A2[M,64].W2[N,64]^T)
  * keep(m,n) is the counter-based mask of vlb_lora_down / vlb_lora_dx_masked for an [M,N] activation under `seed`
@@ -121,6 +121,8 @@ int vlb_gemm_masked_pair_swiglu_bwd(const void* dY, int lddy, const void* Wt, in
                                     int lddgu, int M, int ff, int K, const void* U, int ldu, const void* At, int ldat,
                                     float drop_p, uint32_t seed, void* ws, int64_t ws_bytes, void* stream);
 
+/* Which tile vlb_gemm_bf16 picks for a shape: 0 = generic 64x64, 1 = 256x256, 2 = 256x128.  The same planner the dispatch
+ * runs, asked with every alignment rule met (an unaligned operand sends the call to the generic kernel). */
 int vlb_gemm_kernel_choice(int M, int N, int K, int K2);
 
 /* out[C,R] = in[R,C]^T (bf16).  Used once per frozen weight to lay down W^T for dgrad. */

@@ -16,11 +16,6 @@ constexpr int NW = 4;      // waves per workgroup
 constexpr int QB = QW * NW;
 constexpr float NEG = -1e30f;
 
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                   (void __attribute__((address_space(3)))*)l, 16, 0, 0);
-}
-
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 // ds_read_b64_tr_b16 through inline asm.  hipcc treats the builtin as possibly aliasing a pending LDS-DMA

@@ -47,7 +47,28 @@ static inline hipStream_t as_stream(void* s) {
   return reinterpret_cast<hipStream_t>(s);
 }
 
+// ---- dropout counter hash ----
+// The one mixer behind every dropout mask of the library (LoRA masks in lora.hip, the masked-pair GEMM epilogue in
+// gemm.hip, head dropout in ops.hip): kernels hash the element counter, the host hashes the seed into the key.
+// Statement form for the masked-pair epilogue, which mixes in place between its register fences.
+#define VLB_LOWBIAS32_STEPS(x) x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16
+__host__ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+  VLB_LOWBIAS32_STEPS(x);
+  return x;
+}
+// 16-bit keep threshold of a LoRA mask: an element is kept when its 16 hash bits are >= thresh16(p)
+inline uint32_t thresh16(float p) {
+  if (p <= 0.f) return 0;
+  uint32_t t = (uint32_t)(p * 65536.f + 0.5f);
+  return t > 65535u ? 65535u : t;
+}
+
 // ---- device helpers ----
+// 16 bytes per lane straight from global memory into LDS (global_load_lds_dwordx4)
+__device__ __forceinline__ void glds16(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
+                                   (void __attribute__((address_space(3)))*)l, 16, 0, 0);
+}
 __device__ __forceinline__ float bf2f(bf16 x) { return (float)x; }
 __device__ __forceinline__ bf16 f2bf(float x) { return (bf16)x; }
 

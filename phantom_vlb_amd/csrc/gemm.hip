@@ -209,11 +209,6 @@ __device__ __forceinline__ bf16x4 w4_frag_value(const GemmArgs& p, f32x4 v, int 
 // ds_read_b128 lane group touches land on 16 distinct 16-byte slots: conflict-free.
 __device__ __forceinline__ int lds_off(int r, int c) { return r * ROW_BYTES + ((c ^ ((r >> 1) & 7)) << 4); }
 
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                   (void __attribute__((address_space(3)))*)l, 16, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Ping-pong 8-wave tile kernel.  The 8 waves form two groups of 4 (one wave of each group per
 // SIMD).  Every K-tile is two phases (k-steps of 32); a phase is a LOAD segment (12 ds_read_b128 of
@@ -773,7 +768,7 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
           uint32_t h = (rb + pair0 + q) ^ p.drop_key;
-          h ^= h >> 16; h *= 0x7feb352dU; h ^= h >> 15; h *= 0x846ca68bU; h ^= h >> 16;      // lowbias32
+          VLB_LOWBIAS32_STEPS(h);
           v[2 * q] = (h & 0xffffu) >= m_thresh ? v[2 * q] * m_scale : 0.f;
           v[2 * q + 1] = (h >> 16) >= m_thresh ? v[2 * q + 1] * m_scale : 0.f;
         }
@@ -907,20 +902,19 @@ int launch_w4_splitk(GemmArgs& a, hipStream_t s) {
   return VLB_OK;
 }
 
-// Kernel selection.  The product library (libvlb.so) is built WITHOUT VLB_TOOLS: the selection below is a
-// compile-time constant, no ablation is instantiated and no switch is exported.
+// Kernel selection.  The product library (libvlb.so) is built WITHOUT VLB_TOOLS: the switches below are
+// compile-time constants, no ablation is instantiated and no switch is exported.
 // `make tools` builds libvlb_tools.so with -DVLB_TOOLS for tools/bench_gemm_variants.py & co: timing-only ablations of
 // the product kernels (results wrong by construction) and switches that force one of the planner's or the router's
 // own choices; nothing under phantom_vlb_amd/, bench.py or tests/ loads it.
 #ifdef VLB_TOOLS
 #define VLB_TUNABLE
+constexpr bool kTools = true;
+int g_variant = 3, g_force_tile = 0;      // kernel variant (3: the product's routing) and forced tile (0: none), see tools_override
 #else
 #define VLB_TUNABLE constexpr
+constexpr bool kTools = false;
 #endif
-VLB_TUNABLE int g_variant = 3;      // 1: ping-pong wave groups, 2: four-wave 128x128 blocks,
-                                    // 3 (default): four-wave kernel for long K (>= 4096), ping-pong otherwise, 192-row tiles
-                                    // when the cost model prefers them; 5 (A/B): like 3 but always 192-row tiles for long K
-VLB_TUNABLE int g_force_tile = 0;   // 0: heuristic, 1: 256x256, 2: 256x128 (tuning only)
 VLB_TUNABLE int g_tail_split = 1;   // split a mostly idle last wave of tiles into 256x128 tiles
 VLB_TUNABLE int g_tile_order = 3;   // GemmArgs::order: bit 0 column bands of 8, bit 1 XCD chunks dealt per round, bit 2 16x16 rounds (A/B: variant bits 10-12 XOR 3)
 VLB_TUNABLE int g_order_auto = 1;   // pick_order's shape rule (A/B: variant bit 13 disables it)
@@ -977,64 +971,196 @@ int launch_pp(GemmArgs& a, hipStream_t s, int lds) {
   return VLB_OK;
 }
 
-template <int BM, int BN, int WM, int WN>
-int launch_tile(GemmArgs& a, hipStream_t s) {
-  constexpr int LDS = 2 * (BM + BN) * ROW_BYTES;
-  if (a.grid == 0) {          // plain launch: the whole GEMM with BM x BN tiles
-    a.tiles_m = (a.M + BM - 1) / BM;
-    a.tiles_n = a.N / BN;
-    a.tile0 = 0; a.split_n = 1;
-    a.grid = a.tiles_m * a.tiles_n;
+// ------------------------------------------------------------------------------------------------
+// Routing: plan_route states how one GEMM is cut into launches, run_route issues them; vlb_gemm_kernel_choice and
+// vlb_gemm_plan export the same plan.
+enum { FAM_GENERIC = 0, FAM_PP = 1, FAM_W4 = 2, FAM_NONE = 3 };     // generic 64x64 / ping-pong / four-wave kernel (NONE: tools build, unknown variant)
+struct GemmRoute {
+  int family;                 // kernel of the main launch
+  int tail_family;            // ... of a column-halves tail launch (= family; the tools build can force them apart)
+  int rows, cols;             // tile rows 256 | 192 (four-wave kernel only), tile columns 256 | 128
+  int tiles_m, tiles_n;       // grid of parent tiles
+  int main_tiles;             // parent tiles in the main launch (the full waves when there is a tail)
+  int tail, tail_tiles;       // TailPlan::mode and the parent tiles of the partial last wave it covers
+  int k_splits;               // K ranges per tail tile (tail mode 2)
+  bool masked;                // the masked-pair kernels
+  int abl;                    // 0; tools build: timing-only ablation of the main launch's kernel (results wrong by construction)
+};
+// What the routing depends on beyond the shape
+struct RouteFacts {
+  bool vec_ok;                // the tile kernels' pointer and stride rules hold (else: generic kernel)
+  bool w4_ok;                 // the four-wave kernel may run: 16-byte stores (GemmArgs::wide) and 32-bit operand offsets (fits32)
+  bool ws_ok;                 // the caller passed a split-K workspace
+  bool w4_only;               // four-wave 256-column tiles are given (N % 256 == 0, K % 64 == 0): only the rows and the tail are planned
+  bool masked;                // masked-pair rules: w4_only, the masked kernels, and no split-K at 256 rows
+};
+// the 4-wave kernel addresses operands with 32-bit byte offsets
+inline bool fits32(int M, int N, int lda, int ldw, int lda2, int ldw2) {
+  return (int64_t)M * lda < (1ll << 31) && (int64_t)N * ldw < (1ll << 31) && (int64_t)M * lda2 < (1ll << 31) && (int64_t)N * ldw2 < (1ll << 31);
+}
+
+// Cuts the output into tiles of r.cols columns for the kernel family already chosen: 192 or 256 rows (rows = 0: the
+// cost model decides; 192 only on the four-wave kernel), full waves in the main launch, the partial last wave as planned.
+//
+// Tail split: when the 256x256 grid ends in a mostly idle last wave of tiles (e.g. 2576 tiles = 10.06
+// waves for gate/up at M=5861), the full waves run as 256x256 tiles and the tiles of the partial wave
+// are re-cut into 256x128 halves in a second launch, which spreads them over twice as many CUs for
+// half as long.  Both launches walk the same tile order (map_tile), so the cut can be at any tile.
+// Row quantisation: 192-row tiles (four-wave kernel only) when they cut the row count into fewer, fuller
+// waves - e.g. M=5861, N=4096: 23x16 = 368 tiles of 256 rows cost (1 + 0.62 tail) x 256 = 415 row-units,
+// 31x16 = 496 tiles of 192 rows cost 2 x 192 = 384.  Cost = waves x tile rows; a re-cut partial wave = 0.62.
+inline void cut_waves(GemmRoute& r, int M, int N, int Ktot, bool ws_ok, bool splitk256, int rows = 0) {
+  const bool w4 = r.family == FAM_W4;
+  TailPlan p256{0, 1, 0.0}, p192 = p256;
+  bool use192 = r.cols == 256 && plan_rows(M, N, Ktot, ws_ok && w4, p256, p192, splitk256) && w4;
+  if (rows) use192 = rows == 192;
+  const TailPlan& t = use192 ? p192 : p256;
+  r.rows = use192 ? 192 : 256;
+  r.tiles_m = (M + r.rows - 1) / r.rows; r.tiles_n = N / r.cols;
+  r.tail = t.mode; r.k_splits = t.splits;
+  r.tail_tiles = t.mode ? r.tiles_m * r.tiles_n % 256 : 0;
+  r.main_tiles = r.tiles_m * r.tiles_n - r.tail_tiles;
+}
+
+// The launches of one GEMM.  Pure host arithmetic: no HIP call, nothing read but its arguments (and, in the tools
+// build, the planner switches above).
+inline GemmRoute plan_route(int M, int N, int K, int K2, const RouteFacts& f) {
+  const int cus = 256;
+  GemmRoute r{FAM_GENERIC, FAM_GENERIC, 64, 64, 0, 0, 0, 0, 0, 1, f.masked, 0};
+  if (f.w4_only) {
+    r.cols = 256;
+  } else {
+    if (!f.vec_ok || K % BK != 0 || K2 % BK != 0 || K == 0 || M < 128) return r;
+    // the 256x256 tile has the better MFMA:LDS ratio; fall back to 256x128 only when the grid
+    // would leave more than half of the chip idle
+    if (N % 256 == 0) r.cols = ((M + 255) / 256) * (N / 256) < cus / 2 ? 128 : 256;
+    else if (N % 128 == 0) r.cols = 128;
+    else return r;
   }
-  // the 4-wave kernel addresses operands with 32-bit byte offsets
-  // ... and stores 16 bytes per lane (a.wide: C / aux rows 16-byte aligned)
-  const bool fits32 = a.wide && (int64_t)a.M * a.lda < (1ll << 31) && (int64_t)a.N * a.ldw < (1ll << 31) &&
-                      (int64_t)a.M * a.lda2 < (1ll << 31) && (int64_t)a.N * a.ldw2 < (1ll << 31);
-#ifndef VLB_TOOLS
   // the four-wave kernel wins once the K loop is long enough to amortise its serial prologue and epilogue (one
   // workgroup per CU, nothing to overlap them with): measured crossover K ~ 3072-4096
-  if constexpr (BM == 256 && BN == 256) {
-    if (fits32 && a.K + a.K2 >= 4096) return launch_w4<8, 0>(a, s);
-  } else if constexpr (BM == 256 && BN == 128) {
-    if (fits32 && a.K + a.K2 >= 4096) return launch_w4<4, 0>(a, s);
+  r.family = r.tail_family = (f.w4_only || (f.w4_ok && K + K2 >= 4096)) ? FAM_W4 : FAM_PP;
+  // (no split-K for the 256-row masked kernel: with 64 accumulator tiles + the mask temporaries the register
+  // allocator starts rotating accumulator tuples behind the asm MFMAs; 192-row tiles are fine)
+  cut_waves(r, M, N, K + K2, f.ws_ok, !f.masked);
+  return r;
+}
+
+#ifdef VLB_TOOLS
+// libvlb_tools.so only: vlb_gemm_set_variant's kernel variant (g_variant) and forced tile (g_force_tile) applied to the
+// planned route.  (Its planner switches - variant bits 8-13 - act inside plan_tail and pick_order.)
+//   variant 1: ping-pong kernel; 2: four-wave kernel whenever it may run (256x128 tiles: for long K); 3: the product's
+//   choice; 4: like 3 without row planning, 8-wave kernel for the re-cut tail; 5: like 3 but always 192-row tiles for
+//   long K; 6: like 3 but never 192-row tiles; 0x11-0x17 / 0x21-0x28 / 0x41-0x43 / 0x30-0x3b: ablations of the ping-pong
+//   256x256 / four-wave 256-row (0x4n: W / A / both always from panel 0, L2-resident) / four-wave 192-row kernel
+//   force_tile 1: 256x256 tiles, 2: 256x128 tiles (both: no row planning, no split-K); masked pair: 3 / 4 = 256- / 192-row tiles
+inline void tools_override(GemmRoute& r, int M, int N, int K, int K2, const RouteFacts& f) {
+  const int v = g_variant, ft = g_force_tile, Ktot = K + K2;
+  if (f.masked) {
+    if (ft == 3 || ft == 4) cut_waves(r, M, N, Ktot, f.ws_ok, false, ft == 3 ? 256 : 192);
+    return;
   }
-  return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
+  if (r.family == FAM_GENERIC) return;
+  if (ft == 1 && N % 256 == 0) r.cols = 256;
+  if (ft == 2) r.cols = 128;
+  const bool w4 = f.w4_ok && Ktot >= 4096, known = (v >= 1 && v <= 6) || v >= 0x10;
+  r.tail_family = !known ? FAM_NONE : ((v == 2 || v == 3 || v == 5 || v == 6) && w4) ? FAM_W4 : FAM_PP;
+  r.family = r.cols == 128 ? r.tail_family : FAM_W4;
+  // the row planner and the split-K tail: variants 3, 5, 6 and the 192-row ablations, long K, no forced tile
+  const bool planned = r.cols == 256 && (v == 3 || v == 5 || v == 6 || (v & 0xf0) == 0x30) && w4 && ft == 0;
+  const bool multi_wave = ((M + 255) / 256) * (N / 256) > 256;
+  cut_waves(r, M, N, Ktot, planned && f.ws_ok, true, !planned || v == 6 ? 256 : v == 3 ? 0 : multi_wave ? 192 : 256);
+  if (r.cols == 128) return;
+  if (r.rows == 192) {
+    r.tail_family = FAM_W4;
+    constexpr int abl192[16] = {0, 1, 2, 0, 4, 0, 0, 7, 8, 16, 32, 48, 0, 0, 0, 0};      // 0x39 / 0x3a / 0x3b: W / A / both always from panel 0
+    if ((v & 0xf0) == 0x30) r.abl = abl192[v & 0xf];
+    if (r.abl) r.tail = 0;          // whole-tile launches only
+    return;
+  }
+  const int lo = v & 0xf;
+  r.family = !known ? FAM_NONE : (v == 2 ? f.w4_ok : v <= 6 ? v >= 3 && w4 : false) ? FAM_W4 : FAM_PP;
+  if ((v & 0xf0) == 0x10 && (lo == 1 || lo == 2 || lo == 3 || lo == 4 || lo == 6 || lo == 7)) r.abl = lo;
+  if ((v & 0xf0) == 0x20 && (lo == 1 || lo == 2 || lo == 4 || lo == 7 || lo == 8) && f.w4_ok) { r.family = FAM_W4; r.abl = lo; }
+  if (v >= 0x41 && v <= 0x43 && f.w4_ok) { r.family = FAM_W4; r.abl = 16 * (v & 3); }
+}
 #else
-  if constexpr (BM == 256 && BN == 256) {
-    if (!fits32 && (g_variant == 2 || (g_variant >= 0x20 && g_variant < 0x30))) return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
-    if (g_variant == 2) return launch_w4<8, 0>(a, s);
-    if (g_variant == 3 || g_variant == 4 || g_variant == 5 || g_variant == 6) {      // 4 (A/B only): four-wave main launch, 8-wave kernel for the re-cut tail
-      if (fits32 && a.K + a.K2 >= 4096) return launch_w4<8, 0>(a, s);
-      return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
-    }
-    if (g_variant == 0x21) return launch_w4<8, 1>(a, s);     // timing-only ablations (wrong results)
-    if (g_variant == 0x22) return launch_w4<8, 2>(a, s);
-    if (g_variant == 0x24) return launch_w4<8, 4>(a, s);
-    if (g_variant == 0x27) return launch_w4<8, 7>(a, s);
-    if (g_variant == 0x28) return launch_w4<8, 8>(a, s);
-    if (g_variant == 0x41) return launch_w4<8, 16>(a, s);    // W always from panel 0 (L2-resident)
-    if (g_variant == 0x42) return launch_w4<8, 32>(a, s);    // A always from panel 0
-    if (g_variant == 0x43) return launch_w4<8, 48>(a, s);    // both
-  } else {
-    if constexpr (BM == 256 && BN == 128) {
-      if ((g_variant == 2 || g_variant == 3 || g_variant == 5 || g_variant == 6) && fits32 && a.K + a.K2 >= 4096) return launch_w4<4, 0>(a, s);
-    }
-    if (g_variant == 2 || g_variant == 3 || g_variant == 4 || g_variant == 5 || g_variant == 6 || g_variant >= 0x20) return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
-  }
-  if (g_variant == 1) return launch_pp<BM, BN, WM, WN, (BM + BN) / 64, 0, 0, 0>(a, s, LDS);
-  constexpr int T = (BM + BN) / 64;     // LDS-DMA instructions per thread per K-tile
-  if constexpr (BM == 256 && BN == 256) {   // timing-only ablations of the 256x256 kernel (wrong results!)
-    if (g_variant == 0x11) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 1>(a, s, LDS);
-    if (g_variant == 0x12) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 2>(a, s, LDS);
-    if (g_variant == 0x14) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 4>(a, s, LDS);
-    if (g_variant == 0x13) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 3>(a, s, LDS);
-    if (g_variant == 0x17) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 7>(a, s, LDS);
-    if (g_variant == 0x16) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0, 6>(a, s, LDS);
-  }
-  if (g_variant >= 0x10) return launch_pp<BM, BN, WM, WN, T, 0, 0, 0>(a, s, LDS);   // ablations exist for 256x256 only
-  vlb_set_error("gemm: unknown kernel variant %d", g_variant);
-  return VLB_ERR_INVALID;
+inline void tools_override(GemmRoute&, int, int, int, int, const RouteFacts&) {}
 #endif
+
+// Route -> kernel instantiation, the only place a tile kernel is named on the host.
+constexpr int kernel_key(int family, int rows, int cols, bool masked = false, bool splitk = false, int abl = 0) {
+  return family | (rows / 64) << 2 | (cols / 64) << 5 | masked << 8 | splitk << 9 | abl << 10;
+}
+template <bool TOOLS>
+int launch_kernel(int key, GemmArgs& a, hipStream_t s) {
+  constexpr int PP = FAM_PP, W4 = FAM_W4, T = TOOLS;
+  switch (key) {
+    case kernel_key(FAM_GENERIC, 64, 64):
+      hipLaunchKernelGGL(gemm_generic_kernel, dim3((a.N + 63) / 64, (a.M + 63) / 64), dim3(256), 0, s, a);
+      VLB_LAUNCH_CHECK();
+      return VLB_OK;
+    case kernel_key(PP, 256, 256): return launch_pp<256, 256, 2, 4, 8, 0, 0, 0>(a, s, 2 * (256 + 256) * ROW_BYTES);
+    case kernel_key(PP, 256, 128): return launch_pp<256, 128, 4, 2, 6, 0, 0, 0>(a, s, 2 * (256 + 128) * ROW_BYTES);
+    case kernel_key(W4, 256, 256): return launch_w4<8, 0, 8>(a, s);
+    case kernel_key(W4, 256, 128): return launch_w4<4, 0, 8>(a, s);
+    case kernel_key(W4, 192, 256): return launch_w4<8, 0, 6>(a, s);
+    case kernel_key(W4, 192, 128): return launch_w4<4, 0, 6>(a, s);
+    case kernel_key(W4, 256, 256, false, true): return launch_w4_splitk<8>(a, s);
+    case kernel_key(W4, 192, 256, false, true): return launch_w4_splitk<6>(a, s);
+    case kernel_key(W4, 256, 256, true): return launch_w4<8, 0, 8, true>(a, s);
+    case kernel_key(W4, 256, 128, true): return launch_w4<4, 0, 8, true>(a, s);
+    case kernel_key(W4, 192, 256, true): return launch_w4<8, 0, 6, true>(a, s);
+    case kernel_key(W4, 192, 128, true): return launch_w4<4, 0, 6, true>(a, s);
+    case kernel_key(W4, 192, 256, true, true): return launch_w4_splitk<6, true>(a, s);
+  }
+  if constexpr (TOOLS) {      // timing-only ablations of the main launch (ABL * T: instantiated in the tools build only)
+    switch (key) {
+#define VLB_ABL_PP(ABL) case kernel_key(PP, 256, 256, false, false, ABL): return launch_pp<256, 256, 2, 4, 8, 0, 0, 0, ABL * T>(a, s, 2 * (256 + 256) * ROW_BYTES);
+#define VLB_ABL_W4(ABL)                                                                        \
+  case kernel_key(W4, 256, 256, false, false, ABL): return launch_w4<8, ABL * T, 8>(a, s);      \
+  case kernel_key(W4, 192, 256, false, false, ABL): return launch_w4<8, ABL * T, 6>(a, s);
+      VLB_ABL_PP(1) VLB_ABL_PP(2) VLB_ABL_PP(3) VLB_ABL_PP(4) VLB_ABL_PP(6) VLB_ABL_PP(7)
+      VLB_ABL_W4(1) VLB_ABL_W4(2) VLB_ABL_W4(4) VLB_ABL_W4(7) VLB_ABL_W4(8) VLB_ABL_W4(16) VLB_ABL_W4(32) VLB_ABL_W4(48)
+#undef VLB_ABL_PP
+#undef VLB_ABL_W4
+    }
+  }
+  vlb_set_error("gemm: no kernel for this route (tools build: unknown kernel variant)");
+  return VLB_ERR_INVALID;
+}
+
+// Issues a route: the main launch, then the partial last wave as column halves or as a split-K pair of launches.
+inline int run_route(const GemmRoute& r, GemmArgs a, float* ws, hipStream_t s) {
+  if (r.family == FAM_GENERIC) return launch_kernel<kTools>(kernel_key(FAM_GENERIC, 64, 64), a, s);
+  a.tiles_m = r.tiles_m; a.tiles_n = r.tiles_n;
+  a.grid = r.main_tiles;
+  int rc = launch_kernel<kTools>(kernel_key(r.family, r.rows, r.cols, r.masked, false, r.abl), a, s);
+  if (rc != VLB_OK || !r.tail) return rc;
+  a.tile0 = r.main_tiles;
+  if (r.tail == 2) {
+    a.ws = ws; a.k_splits = r.k_splits; a.tail_tiles = r.tail_tiles;
+    return launch_kernel<kTools>(kernel_key(FAM_W4, r.rows, 256, r.masked, true), a, s);
+  }
+  a.split_n = 2; a.grid = 2 * r.tail_tiles;
+  return launch_kernel<kTools>(kernel_key(r.tail_family, r.rows, 128, r.masked), a, s);
+}
+
+// The kernels' argument block for one GEMM; the launch fields (tiles, tile0, grid, split-K) are run_route's.
+inline GemmArgs gemm_args(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K, const void* bias,
+                          const void* residual, int ldr, int act, const void* A2, int lda2, const void* W2, int ldw2, int K2,
+                          void* aux, int ldaux) {
+  GemmArgs a;
+  a.A = (const bf16*)A; a.W = (const bf16*)W; a.C = (bf16*)C;
+  a.A2 = (const bf16*)A2; a.W2 = (const bf16*)W2;
+  a.bias = (const bf16*)bias; a.residual = (const bf16*)residual;
+  a.M = M; a.N = N; a.K = K; a.K2 = K2;
+  a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.lda2 = lda2; a.ldw2 = ldw2;
+  a.act = act; a.tiles_m = 0; a.tiles_n = 0; a.tile0 = 0; a.split_n = 1; a.grid = 0; a.drop_thresh = 0; a.drop_key = 0; a.drop_scale = 1.f;
+  a.ws = nullptr; a.k_splits = 0; a.tail_tiles = 0; a.order = pick_order(M, N, K); a.aux = (bf16*)aux; a.ldaux = ldaux; a.reserved = 0;
+  // ... and stores 16 bytes per lane (a.wide: C / aux rows 16-byte aligned)
+  a.wide = ((uintptr_t)C % 16) == 0 && ldc % 8 == 0 && (!aux || (((uintptr_t)aux % 16) == 0 && ldaux % 8 == 0 && (N / 2) % 8 == 0));
+  return a;
 }
 
 // 16x16 LDS-tiled transpose, 32x32 elements per block
@@ -1054,57 +1180,22 @@ __global__ void transpose_kernel(const bf16* __restrict__ in, bf16* __restrict__
 
 }  // namespace
 
-// Tile choice exported for tests / DESIGN.md: 0 generic, 1 = 256x256, 2 = 256x128
+// The planner the dispatch runs (plan_route), for tests / DESIGN.md, with every alignment rule taken as met:
+// the tile vlb_gemm_bf16 picks: 0 generic, 1 = 256x256, 2 = 256x128
 extern "C" int vlb_gemm_kernel_choice(int M, int N, int K, int K2) {
-  if (K % BK != 0 || K2 % BK != 0 || K == 0 || M < 128) return 0;
-  const int cus = 256;
-  if (N % 256 == 0) {
-    const int t256 = ((M + 255) / 256) * (N / 256);
-    // the 256x256 tile has the better MFMA:LDS ratio; fall back to 256x128 only when the grid
-    // would leave more than half of the chip idle
-    if (t256 < cus / 2) return 2;
-    return 1;
-  }
-  if (N % 128 == 0) return 2;
-  return 0;
+  const GemmRoute r = plan_route(M, N, K, K2, RouteFacts{true, true, false, false, false});
+  return r.family == FAM_GENERIC ? 0 : r.cols == 256 ? 1 : 2;
 }
 
-// Tuning / test aid: how a long-K GEMM on the four-wave kernel is cut: rows*1000 + tail mode*100 + K splits
+// ... and how a long-K GEMM on the four-wave kernel's 256-column tiles is cut: rows*1000 + tail mode*100 + K splits
 // (tail mode 0 whole tiles, 1 re-cut halves, 2 split-K).
 extern "C" int vlb_gemm_plan(int M, int N, int K, int K2, int with_workspace) {
   if (N % 256 != 0 || K + K2 < 4096) return 0;
-  TailPlan p256, p192;
-  const bool use192 = plan_rows(M, N, K + K2, (with_workspace & 1) != 0, p256, p192, !(with_workspace & 2));     // bit 1: masked-pair rules
-  const TailPlan& t = use192 ? p192 : p256;
-  return (use192 ? 192 : 256) * 1000 + t.mode * 100 + t.splits;
+  const GemmRoute r = plan_route(M, N, K, K2, RouteFacts{true, true, (with_workspace & 1) != 0, true, (with_workspace & 2) != 0});     // bit 1: masked-pair rules
+  return r.rows * 1000 + r.tail * 100 + r.k_splits;
 }
 
 extern "C" int64_t vlb_gemm_workspace_bytes(void) { return 256ll * 256 * 256 * 4; }   // <= 256 work items x one 256x256 fp32 tile
-
-extern "C" int vlb_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
-                             const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
-                             const void* W2, int ldw2, int K2, void* stream) {
-  return vlb_gemm_bf16_ws(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, A2, lda2, W2, ldw2, K2, nullptr, 0, stream);
-}
-
-static int gemm_impl(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
-                     const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
-                     const void* W2, int ldw2, int K2, void* ws, int64_t ws_bytes, void* stream, void* aux, int ldaux);
-
-extern "C" int vlb_gemm_bf16_ws(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
-                                const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
-                                const void* W2, int ldw2, int K2, void* ws, int64_t ws_bytes, void* stream) {
-  return gemm_impl(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, A2, lda2, W2, ldw2, K2, ws, ws_bytes, stream, nullptr, 0);
-}
-
-extern "C" int vlb_gemm_swiglu_save(const void* A, int lda, const void* W_il, int ldw, void* H, int ldh, void* GU, int ldgu, int M, int N,
-                                    int K, const void* A2, int lda2, const void* W2_il, int ldw2, int K2, void* ws, int64_t ws_bytes,
-                                    void* stream) {
-  VLB_REQUIRE(GU && ldgu >= N && ldgu % 4 == 0 && N % 8 == 0 && ((uintptr_t)GU % 8) == 0,
-              "gemm_swiglu_save: [gate | up] rows must hold N columns, 8-byte aligned (N=%d ldgu=%d)", N, ldgu);
-  return gemm_impl(A, lda, W_il, ldw, H, ldh, M, N, K, nullptr, nullptr, 0, VLB_ACT_SWIGLU_PAIR, A2, lda2, W2_il, ldw2, K2, ws, ws_bytes,
-                   stream, GU, ldgu);
-}
 
 static int gemm_impl(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                      const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
@@ -1125,118 +1216,68 @@ static int gemm_impl(const void* A, int lda, const void* W, int ldw, void* C, in
   if (act == VLB_ACT_SWIGLU_PAIR) {
     VLB_REQUIRE(N % 32 == 0 && !bias && !residual && ldc >= N / 2, "gemm: SWIGLU_PAIR needs N %% 32 == 0, no bias/residual, ldc >= N/2");
   }
-  GemmArgs a;
-  a.A = (const bf16*)A; a.W = (const bf16*)W; a.C = (bf16*)C;
-  a.A2 = (const bf16*)A2; a.W2 = (const bf16*)W2;
-  a.bias = (const bf16*)bias; a.residual = (const bf16*)residual;
-  a.M = M; a.N = N; a.K = K; a.K2 = K2;
-  a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.lda2 = lda2; a.ldw2 = ldw2;
-  a.act = act; a.tiles_m = 0; a.tiles_n = 0; a.tile0 = 0; a.split_n = 1; a.grid = 0; a.drop_thresh = 0; a.drop_key = 0; a.drop_scale = 1.f;
-  a.ws = nullptr; a.k_splits = 0; a.tail_tiles = 0; a.order = pick_order(M, N, K); a.aux = (bf16*)aux; a.ldaux = ldaux;
-  a.wide = ((uintptr_t)C % 16) == 0 && ldc % 8 == 0 && (!aux || (((uintptr_t)aux % 16) == 0 && ldaux % 8 == 0 && (N / 2) % 8 == 0));
-  hipStream_t s = as_stream(stream);
+  const GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, A2, lda2, W2, ldw2, K2, aux, ldaux);
   const bool vec_ok = (ldc % 4 == 0) && (!residual || ldr % 4 == 0) && (!aux || (ldaux % 4 == 0 && (N / 2) % 4 == 0)) &&
                       (((uintptr_t)C | (uintptr_t)residual | (uintptr_t)bias | (uintptr_t)aux) % 8 == 0) &&
                       (((uintptr_t)A | (uintptr_t)W | (uintptr_t)A2 | (uintptr_t)W2) % 16 == 0);
-  int choice = vec_ok ? vlb_gemm_kernel_choice(M, N, K, K2) : 0;
-  if (choice != 0 && g_force_tile == 1 && N % 256 == 0) choice = 1;
-  if (choice != 0 && g_force_tile == 2 && N % 128 == 0) choice = 2;
-  if (choice == 1) {
-    // Tail split: when the 256x256 grid ends in a mostly idle last wave of tiles (e.g. 2576 tiles = 10.06
-    // waves for gate/up at M=5861), the full waves run as 256x256 tiles and the tiles of the partial wave
-    // are re-cut into 256x128 halves in a second launch, which spreads them over twice as many CUs for
-    // half as long.  Both launches walk the same tile order (map_tile), so the cut can be at any tile.
-    const int cus = 256, tn = N / 256, tm = (M + 255) / 256;
-    const int tiles = tm * tn, rem = tiles % cus;
-    // Row quantisation: 192-row tiles (four-wave kernel only) when they cut the row count into fewer, fuller
-    // waves - e.g. M=5861, N=4096: 23x16 = 368 tiles of 256 rows cost (1 + 0.62 tail) x 256 = 415 row-units,
-    // 31x16 = 496 tiles of 192 rows cost 2 x 192 = 384.  Cost = waves x tile rows; a re-cut partial wave = 0.62.
-    {
-      const bool fits32 = a.wide && (int64_t)M * lda < (1ll << 31) && (int64_t)N * ldw < (1ll << 31) &&
-                          (int64_t)M * lda2 < (1ll << 31) && (int64_t)N * ldw2 < (1ll << 31);
-#ifdef VLB_TOOLS
-      const int abl192 = (g_variant >= 0x30 && g_variant < 0x40) ? (g_variant & 0xf) : 0;     // timing-only ablations of the 192-row kernel
-      const bool w4 = (g_variant == 3 || g_variant == 5 || g_variant == 6 || (g_variant >= 0x30 && g_variant < 0x40)) && fits32 && K + K2 >= 4096;    // 6 (A/B): never 192-row tiles
-#else
-      const bool w4 = (g_variant == 3 || g_variant == 5) && fits32 && K + K2 >= 4096;      // four-wave kernel shapes
-#endif
-      const int tm192 = (M + 191) / 192, tiles192 = tm192 * tn;
-      TailPlan p256, p192;
-      bool use192 = plan_rows(M, N, K + K2, ws_ok && w4, p256, p192);
-#ifdef VLB_TOOLS
-      if (g_variant == 6) use192 = false;
-#endif
-      if (w4 && g_force_tile == 0 && tiles > cus && (g_variant == 5 || (g_variant >= 0x30 && g_variant < 0x40) || use192)) {
-        GemmArgs hi = a;
-        hi.tiles_m = tm192; hi.tiles_n = tn; hi.tile0 = 0; hi.split_n = 1;
-        const int rem192 = tiles192 % cus;
-        hi.grid = p192.mode ? tiles192 - rem192 : tiles192;
-#ifdef VLB_TOOLS
-        if (abl192 == 1) return launch_w4<8, 1, 6>(hi, s);       // results wrong by construction: whole-tile launches only
-        if (abl192 == 2) return launch_w4<8, 2, 6>(hi, s);
-        if (abl192 == 4) return launch_w4<8, 4, 6>(hi, s);
-        if (abl192 == 8) return launch_w4<8, 8, 6>(hi, s);
-        if (abl192 == 7) return launch_w4<8, 7, 6>(hi, s);
-        if (abl192 == 9) return launch_w4<8, 16, 6>(hi, s);      // 0x39: W always from panel 0
-        if (abl192 == 10) return launch_w4<8, 32, 6>(hi, s);     // 0x3a: A always from panel 0
-        if (abl192 == 11) return launch_w4<8, 48, 6>(hi, s);     // 0x3b: both
-#endif
-        int rc = launch_w4<8, 0, 6>(hi, s);
-        if (rc != VLB_OK || !p192.mode) return rc;
-        GemmArgs lo = hi;
-        lo.tile0 = tiles192 - rem192;
-        if (p192.mode == 2) {
-          lo.ws = (float*)ws; lo.k_splits = p192.splits; lo.tail_tiles = rem192;
-          return launch_w4_splitk<6>(lo, s);
-        }
-        lo.split_n = 2; lo.grid = 2 * rem192;
-        return launch_w4<4, 0, 6>(lo, s);
-      }
-      if (w4 && g_force_tile == 0 && p256.mode == 2) {
-        GemmArgs hi = a;
-        hi.tiles_m = tm; hi.tiles_n = tn; hi.tile0 = 0; hi.split_n = 1; hi.grid = tiles - rem;
-        int rc = launch_w4<8, 0, 8>(hi, s);
-        if (rc != VLB_OK) return rc;
-        GemmArgs lo = hi;
-        lo.tile0 = tiles - rem; lo.ws = (float*)ws; lo.k_splits = p256.splits; lo.tail_tiles = rem;
-        return launch_w4_splitk<8>(lo, s);
-      }
-    }
-    if (g_tail_split && tiles > cus && rem != 0 && rem <= cus * 5 / 8) {
-      GemmArgs hi = a, lo = a;
-      hi.tiles_m = lo.tiles_m = tm;
-      hi.tiles_n = lo.tiles_n = tn;
-      hi.tile0 = 0; hi.split_n = 1; hi.grid = tiles - rem;
-      lo.tile0 = tiles - rem; lo.split_n = 2; lo.grid = 2 * rem;
-      int rc = launch_tile<256, 256, 2, 4>(hi, s);
-      if (rc != VLB_OK) return rc;
-      return launch_tile<256, 128, 4, 2>(lo, s);
-    }
-    return launch_tile<256, 256, 2, 4>(a, s);
-  }
-  if (choice == 2) return launch_tile<256, 128, 4, 2>(a, s);
-  dim3 grid((N + 63) / 64, (M + 63) / 64);
-  hipLaunchKernelGGL(gemm_generic_kernel, grid, dim3(256), 0, s, a);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  const RouteFacts f{vec_ok, a.wide && fits32(M, N, lda, ldw, lda2, ldw2), ws_ok, false, false};
+  GemmRoute r = plan_route(M, N, K, K2, f);
+  tools_override(r, M, N, K, K2, f);      // empty in the product library
+  return run_route(r, a, (float*)ws, as_stream(stream));
 }
 
-namespace {
-inline uint32_t lowbias32_h(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
+extern "C" int vlb_gemm_bf16(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
+                             const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
+                             const void* W2, int ldw2, int K2, void* stream) {
+  return vlb_gemm_bf16_ws(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, A2, lda2, W2, ldw2, K2, nullptr, 0, stream);
 }
-}  // namespace
+
+extern "C" int vlb_gemm_bf16_ws(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
+                                const void* bias, const void* residual, int ldr, int act, const void* A2, int lda2,
+                                const void* W2, int ldw2, int K2, void* ws, int64_t ws_bytes, void* stream) {
+  return gemm_impl(A, lda, W, ldw, C, ldc, M, N, K, bias, residual, ldr, act, A2, lda2, W2, ldw2, K2, ws, ws_bytes, stream, nullptr, 0);
+}
+
+extern "C" int vlb_gemm_swiglu_save(const void* A, int lda, const void* W_il, int ldw, void* H, int ldh, void* GU, int ldgu, int M, int N,
+                                    int K, const void* A2, int lda2, const void* W2_il, int ldw2, int K2, void* ws, int64_t ws_bytes,
+                                    void* stream) {
+  VLB_REQUIRE(GU && ldgu >= N && ldgu % 4 == 0 && N % 8 == 0 && ((uintptr_t)GU % 8) == 0,
+              "gemm_swiglu_save: [gate | up] rows must hold N columns, 8-byte aligned (N=%d ldgu=%d)", N, ldgu);
+  return gemm_impl(A, lda, W_il, ldw, H, ldh, M, N, K, nullptr, nullptr, 0, VLB_ACT_SWIGLU_PAIR, A2, lda2, W2_il, ldw2, K2, ws, ws_bytes,
+                   stream, GU, ldgu);
+}
+
+// Same wave-quantisation choice as vlb_gemm_bf16 (256- or 192-row tiles; partial wave re-cut or split along K), always on
+// the four-wave kernel.
+static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
+                            const void* A2, int lda2, const void* W2, int ldw2, float drop_p, uint32_t seed,
+                            void* ws, int64_t ws_bytes, void* stream, int act, const void* residual, int ldr) {
+  VLB_REQUIRE(!ws || ((uintptr_t)ws % 16) == 0, "gemm_masked_pair: workspace must be 16-byte aligned");
+  const bool ws_ok = ws && ws_bytes >= vlb_gemm_workspace_bytes();
+  VLB_REQUIRE(A && W && C && A2 && W2, "gemm_masked_pair: null operand");
+  VLB_REQUIRE(M > 0 && N % 256 == 0 && K >= 128 && K % 64 == 0, "gemm_masked_pair: needs N %% 256 == 0, K %% 64 == 0, K >= 128 (N=%d K=%d)", N, K);
+  VLB_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda2 % 8 == 0 && ldw2 % 8 == 0 && lda >= K && ldw >= K && lda2 >= 64 && ldw2 >= 64 &&
+                  ldc % 4 == 0 && ldc >= N, "gemm_masked_pair: bad leading dimensions");
+  VLB_REQUIRE((((uintptr_t)A | (uintptr_t)W | (uintptr_t)A2 | (uintptr_t)W2 | (uintptr_t)C) % 16) == 0 && ldc % 8 == 0,
+              "gemm_masked_pair: operands and C rows must be 16-byte aligned");
+  VLB_REQUIRE(drop_p > 0.f && drop_p < 1.f, "gemm_masked_pair: drop_p must be in (0,1) - use vlb_gemm_bf16 when p == 0");
+  VLB_REQUIRE(fits32(M, N, lda, ldw, lda2, ldw2) && (int64_t)M * (N >> 1) < (1ll << 32),
+              "gemm_masked_pair: operand too large for 32-bit offsets / the 32-bit dropout counter");
+  GemmArgs a = gemm_args(A, lda, W, ldw, C, ldc, M, N, K, nullptr, residual, ldr, act, A2, lda2, W2, ldw2, 64, nullptr, 0);
+  a.drop_thresh = thresh16(drop_p);
+  a.drop_key = lowbias32(seed);
+  a.drop_scale = 1.f / (1.f - drop_p);
+  const RouteFacts f{true, true, ws_ok, true, true};
+  GemmRoute r = plan_route(M, N, K, 64, f);
+  tools_override(r, M, N, K, 64, f);      // empty in the product library
+  return run_route(r, a, (float*)ws, as_stream(stream));
+}
 
 extern "C" int vlb_gemm_bf16_masked_pair(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                                          const void* A2, int lda2, const void* W2, int ldw2, float drop_p, uint32_t seed,
                                          void* stream) {
   return vlb_gemm_bf16_masked_pair_ws(A, lda, W, ldw, C, ldc, M, N, K, A2, lda2, W2, ldw2, drop_p, seed, nullptr, 0, stream);
 }
-
-static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
-                            const void* A2, int lda2, const void* W2, int ldw2, float drop_p, uint32_t seed,
-                            void* ws, int64_t ws_bytes, void* stream, int act, const void* residual, int ldr);
 
 extern "C" int vlb_gemm_bf16_masked_pair_ws(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
                                             const void* A2, int lda2, const void* W2, int ldw2, float drop_p, uint32_t seed,
@@ -1252,63 +1293,6 @@ extern "C" int vlb_gemm_masked_pair_swiglu_bwd(const void* dY, int lddy, const v
               "gemm_masked_pair_swiglu_bwd: [gate|up] rows must hold 2*ff columns; gu and d gu rows 16-byte aligned (ff=%d ldgu=%d lddgu=%d)", ff, ldgu, lddgu);
   return masked_pair_impl(dY, lddy, Wt, ldw, dgu, lddgu, M, ff, K, U, ldu, At, ldat, drop_p, seed, ws, ws_bytes, stream,
                           VLB_ACT_SWIGLU_BWD, gu, ldgu);
-}
-
-static int masked_pair_impl(const void* A, int lda, const void* W, int ldw, void* C, int ldc, int M, int N, int K,
-                            const void* A2, int lda2, const void* W2, int ldw2, float drop_p, uint32_t seed,
-                            void* ws, int64_t ws_bytes, void* stream, int act, const void* residual, int ldr) {
-  VLB_REQUIRE(!ws || ((uintptr_t)ws % 16) == 0, "gemm_masked_pair: workspace must be 16-byte aligned");
-  const bool ws_ok = ws && ws_bytes >= vlb_gemm_workspace_bytes();
-  VLB_REQUIRE(A && W && C && A2 && W2, "gemm_masked_pair: null operand");
-  VLB_REQUIRE(M > 0 && N % 256 == 0 && K >= 128 && K % 64 == 0, "gemm_masked_pair: needs N %% 256 == 0, K %% 64 == 0, K >= 128 (N=%d K=%d)", N, K);
-  VLB_REQUIRE(lda % 8 == 0 && ldw % 8 == 0 && lda2 % 8 == 0 && ldw2 % 8 == 0 && lda >= K && ldw >= K && lda2 >= 64 && ldw2 >= 64 &&
-                  ldc % 4 == 0 && ldc >= N, "gemm_masked_pair: bad leading dimensions");
-  VLB_REQUIRE((((uintptr_t)A | (uintptr_t)W | (uintptr_t)A2 | (uintptr_t)W2 | (uintptr_t)C) % 16) == 0 && ldc % 8 == 0,
-              "gemm_masked_pair: operands and C rows must be 16-byte aligned");
-  VLB_REQUIRE(drop_p > 0.f && drop_p < 1.f, "gemm_masked_pair: drop_p must be in (0,1) - use vlb_gemm_bf16 when p == 0");
-  VLB_REQUIRE((int64_t)M * lda < (1ll << 31) && (int64_t)N * ldw < (1ll << 31) && (int64_t)M * lda2 < (1ll << 31) &&
-                  (int64_t)N * ldw2 < (1ll << 31) && (int64_t)M * (N >> 1) < (1ll << 32),
-              "gemm_masked_pair: operand too large for 32-bit offsets / the 32-bit dropout counter");
-  GemmArgs a;
-  a.A = (const bf16*)A; a.W = (const bf16*)W; a.C = (bf16*)C;
-  a.A2 = (const bf16*)A2; a.W2 = (const bf16*)W2;
-  a.bias = nullptr; a.residual = (const bf16*)residual;
-  a.M = M; a.N = N; a.K = K; a.K2 = 64;
-  a.lda = lda; a.ldw = ldw; a.ldc = ldc; a.ldr = ldr; a.lda2 = lda2; a.ldw2 = ldw2;
-  a.act = act; a.tiles_m = 0; a.tiles_n = 0; a.tile0 = 0; a.split_n = 1; a.grid = 0;
-  a.ws = nullptr; a.k_splits = 0; a.tail_tiles = 0; a.order = pick_order(M, N, K); a.aux = nullptr; a.ldaux = 0;
-  a.wide = 1;
-  uint32_t t = (uint32_t)(drop_p * 65536.f + 0.5f);
-  a.drop_thresh = t > 65535u ? 65535u : t;
-  a.drop_key = lowbias32_h(seed);
-  a.drop_scale = 1.f / (1.f - drop_p);
-  hipStream_t s = as_stream(stream);
-  // same wave-quantisation choice as vlb_gemm_bf16 (256- or 192-row tiles; partial wave re-cut or split along K)
-  const int cus = 256, tn = N / 256;
-  TailPlan p256, p192;
-  // (no split-K for the 256-row masked kernel: with 64 accumulator tiles + the mask temporaries the register
-  // allocator starts rotating accumulator tuples behind the asm MFMAs; 192-row tiles are fine)
-  bool use192 = plan_rows(M, N, K + 64, ws_ok, p256, p192, false);
-#ifdef VLB_TOOLS
-  if (g_force_tile == 3) use192 = false;      // A/B only: force 256- / 192-row tiles for the masked-pair kernel
-  if (g_force_tile == 4) use192 = true;
-#endif
-  const TailPlan& tp = use192 ? p192 : p256;
-  const int tm = use192 ? (M + 191) / 192 : (M + 255) / 256;
-  const int tiles = tm * tn, rem = tiles % cus;
-  GemmArgs hi = a;
-  hi.tiles_m = tm; hi.tiles_n = tn; hi.tile0 = 0; hi.split_n = 1;
-  hi.grid = tp.mode ? tiles - rem : tiles;
-  int rc = use192 ? launch_w4<8, 0, 6, true>(hi, s) : launch_w4<8, 0, 8, true>(hi, s);
-  if (rc != VLB_OK || !tp.mode) return rc;
-  GemmArgs lo = hi;
-  lo.tile0 = tiles - rem;
-  if (tp.mode == 2) {
-    lo.ws = (float*)ws; lo.k_splits = tp.splits; lo.tail_tiles = rem;
-    return launch_w4_splitk<6, true>(lo, s);
-  }
-  lo.split_n = 2; lo.grid = 2 * rem;
-  return use192 ? launch_w4<4, 0, 6, true>(lo, s) : launch_w4<4, 0, 8, true>(lo, s);
 }
 
 #ifdef VLB_TOOLS

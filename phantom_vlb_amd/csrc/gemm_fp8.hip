@@ -30,10 +30,6 @@ struct Fp8Args {
 constexpr int FBK = 128;            // K bytes per tile row
 constexpr int FROW = 128;           // LDS row bytes
 __device__ __forceinline__ int f_off(int r, int c) { return r * FROW + ((c ^ ((r >> 1) & 7)) << 4); }
-__device__ __forceinline__ void glds16f(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 16, 0, 0);
-}
-
 __device__ __forceinline__ void glds4f(const void* g, void* l) {
   __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g, (void __attribute__((address_space(3)))*)l, 4, 0, 0);
 }
@@ -101,12 +97,12 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_pipe_kernel(Fp8Args p, Fp8L
   const char* const baseSA = reinterpret_cast<const char*>(p.sA); const char* const baseSW = reinterpret_cast<const char*>(p.sW);
   auto dmaW = [&](int st, int kt, int pc) {                  // piece pc of W(kt): 0..NT-1 image, NT scale words
     char* base = smem + st * STAGE;
-    if (pc < NT) glds16f(baseW + (int64_t)kt * FBK + offW[pc], base + A_BYTES + (wave * NT + pc) * 1024);
+    if (pc < NT) glds16(baseW + (int64_t)kt * FBK + offW[pc], base + A_BYTES + (wave * NT + pc) * 1024);
     else glds4f(baseSW + kt * 4 + offSW, base + SW_OFF + wave * 256);
   };
   auto dmaA = [&](int st, int kt, int pc) {                  // piece pc of A(kt): 0..MT-1 image, MT scale words
     char* base = smem + st * STAGE;
-    if (pc < MT) glds16f(baseA + (int64_t)kt * FBK + offA[pc], base + (wave * MT + pc) * 1024);
+    if (pc < MT) glds16(baseA + (int64_t)kt * FBK + offA[pc], base + (wave * MT + pc) * 1024);
     else glds4f(baseSA + kt * 4 + offSA, base + SA_OFF + wave * 256);
   };
   const int fr = lane & 15, g = lane >> 4;

@@ -12,10 +12,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
 // 16 random bits for element (m, k) of an [M,K] activation under `seed` (K even)
 __device__ __forceinline__ uint32_t drop_bits_pair(uint32_t seed, int64_t m, int K, int kpair) {
   const uint64_t c = (uint64_t)m * (uint64_t)(K >> 1) + (uint64_t)kpair;
@@ -206,10 +202,6 @@ constexpr int WG_STEP = 32;     // rows of M per MFMA k-step
 typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef short s16x8_t __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void glds16_l(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)g,
-                                   (void __attribute__((address_space(3)))*)l, 16, 0, 0);
-}
 // 32-byte pair slot swizzle of the X tile: rows r and r+8 and the 4 rows of a transposed read all differ
 __device__ __forceinline__ int xsw(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
 
@@ -277,7 +269,7 @@ __global__ __launch_bounds__(256) void wgrad_mfma_kernel(const bf16* __restrict_
       const int chunk = (((pc >> 1) ^ xsw(r)) << 1) | (pc & 1);
       const int m = min(m0 + r, M - 1);                        // rows past the end are zeroed through G
       const int col = min(c0 + chunk * 8, K - 8);
-      glds16_l(X + (int64_t)m * ldx + col, xb + piece * 1024);
+      glds16(X + (int64_t)m * ldx + col, xb + piece * 1024);
     }
   };
   auto g_store = [&](int buf, const bf16x8& gv) {
@@ -558,23 +550,14 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(const bf16* __restrict_
   }
 }
 
-inline uint32_t lowbias32_host(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
 inline Seeds make_seeds(const uint32_t* seeds_host, int groups, int M, int K) {
   Seeds sd{};
   for (int g = 0; g < groups; ++g) {
     sd.s[g] = seeds_host ? seeds_host[g] : 0u;
-    sd.key[g] = lowbias32_host(sd.s[g]);
+    sd.key[g] = lowbias32(sd.s[g]);
   }
   sd.fast = ((int64_t)M * (K >> 1) < (1ll << 32)) ? 1u : 0u;
   return sd;
-}
-inline uint32_t thresh16(float p) {
-  if (p <= 0.f) return 0;
-  uint32_t t = (uint32_t)(p * 65536.f + 0.5f);
-  return t > 65535u ? 65535u : t;
 }
 }  // namespace
 

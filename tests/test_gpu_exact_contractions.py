@@ -4,9 +4,10 @@ contractions of lora.hip against the exact reference of tests/exact_ints.py, one
 Operands are ternary, so fp32 accumulation is exact in any order and the outputs are integers bf16 holds exactly: the
 linear epilogues are checked with ``assert_bits_equal`` (no tolerance), the non-linear ones with the derived element-wise
 bar of ``assert_within_ulp``.  Every case names the route it is meant to enter and asserts the library's own decision
-(``vlb_gemm_kernel_choice`` / ``vlb_gemm_plan``) first, so a planner change fails loudly instead of silently testing
-another kernel.  What the library does not export (the tile order, the 16-byte-store rule, the pointer rules of the
-generic kernel) is restated next to the case from gemm_impl.
+first (``vlb_gemm_kernel_choice`` / ``vlb_gemm_plan``: encodings of plan_route, the planner the dispatch runs, with the
+alignment facts taken as met), so a planner change fails loudly instead of silently testing another kernel.  What the
+library does not export - pick_order's tile order and the facts plan_route takes from the call itself (the 16-byte-store
+rule, the pointer rules of the generic kernel) - is named next to the case that turns on it.
 
 Shapes up to 2^30 multiply-adds take the reference from CPU fp64; larger ones build operands and the whole reference on
 the device (fp32 matmul, exact on these operands) and confirm it against CPU fp64 on a row subsample.
