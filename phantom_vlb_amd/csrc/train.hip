@@ -262,7 +262,14 @@ __global__ __launch_bounds__(256) void adamw_g16_kernel(float* __restrict__ p, b
 __device__ __forceinline__ float act_grad(float x, int act) {
   if (act == VLB_ACT_SILU) { const float s = sigmoid_f(x); return s * (1.f + x * (1.f - s)); }
   if (act == VLB_ACT_GELU) return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-  if (act == VLB_ACT_QUICK_GELU) { const float s = sigmoid_f(1.702f * x); return s * (1.f + 1.702f * x * (1.f - s)); }
+  if (act == VLB_ACT_QUICK_GELU) {
+    // 1.702 x overflows for |x| > 2e38 and inf * (1 - s) = inf * 0 (or 0 * -inf below) was NaN; beyond 3e38 s is exactly
+    // 0 or 1 and the finite stand-in gives the limit.  Every other argument, NaN included: the same bits as before.
+    const float t = 1.702f * x;
+    const float a = fabsf(t) > 3.0e38f ? copysignf(3.0e38f, t) : t;
+    const float s = sigmoid_f(a);
+    return s * (1.f + a * (1.f - s));
+  }
   return 1.f;
 }
 __global__ __launch_bounds__(256) void act_bwd_kernel(const bf16* __restrict__ x, const bf16* __restrict__ dy, bf16* __restrict__ dx,
