@@ -330,6 +330,36 @@ int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, const void* r
                              int E, int V, float eps, float l2_lambda, float loss_scale, float l2_scale, void* stream,
                              int loss_kind, const float* rowstat);
 
+/* Reading the head from K chosen decoder layers with a learned convex mix (opt-in; every entry point above keeps its
+ * bits).  LN1's affine is per column and the pooling is linear, so the mix is taken on the pooled vectors:
+ *   P_k = pooled_raw of tapped layer k (vlb_head_pool),  alpha = softmax(a),  pooled_raw = sum_k alpha_k P_k,
+ * and the tail of the head runs on that pooled_raw (vlb_head_fwd_cached with rows = 0..B-1 / vlb_head_bwd_cached).
+ * vlb_head_pool: the pooling half of vlb_head_fwd on its own (the same launches: same input, same bits);  ws holds
+ *   vlb_head_ws_floats(B,S,E,V) floats, or B * vlb_head_partial_rows(S) * (E+2).
+ * vlb_feature_cache_gather: the copy vlb_head_fwd_cached starts with, on its own (one slab of a K-slab cache).
+ * vlb_head_mix_fwd: p_stack fp32 [K,B,E], a bf16 [K] (the logits' compute copy; NULL only for K = 1: alpha = 1) ->
+ *   alpha fp32 [K], pooled_raw fp32 [B,E].  Softmax in fp32, max-subtracted; the sum over k in ascending order.  K = 1
+ *   copies the bits of p_stack.  1 <= K <= 64.
+ * vlb_head_mix_bwd: draw = d loss / d pooled_raw [B,E] (what vlb_head_bwd_cached leaves in dpooled_ws) ->
+ *   d_a fp32 [K] (written, not accumulated; the softmax Jacobian applied: d_a_k = alpha_k (dalpha_k - sum_j alpha_j dalpha_j),
+ *   dalpha_k = <draw, P_k>) and draw_stack fp32 [K,B,E] = alpha_k * draw (K = 1: a bit copy).  The K dot products go
+ *   through per-block partials in ws (vlb_head_mix_ws_floats(K,B,E) floats) summed by one block in a fixed order.
+ * vlb_head_dhidden: vlb_head_bwd's last launch on its own: dx bf16 [rows,E] from hidden, stats and draw [B,E].
+ *   accumulate == 0: rows with w == 0 are zeroed, the others written (vlb_head_bwd's bits).  accumulate != 0: rows
+ *   with w != 0 become bf16(float(dx) + value), value as in write mode before its rounding; rows with w == 0 are
+ *   neither read nor written. */
+int vlb_head_pool(const void* hidden, const float* wmask, float* ws, float* stats, float* pooled_raw, float* sumw, int B,
+                  int S, int E, float eps, const int* cu_rows, void* stream);
+int vlb_feature_cache_gather(const float* cache_pooled, const float* cache_sumw, const int32_t* rows, float* pooled_raw,
+                             float* sumw, int B, int E, int n_rows, void* stream);
+int vlb_head_mix_fwd(const float* p_stack, const void* a, float* alpha, float* pooled_raw, int K, int B, int E,
+                     void* stream);
+int64_t vlb_head_mix_ws_floats(int K, int B, int E);
+int vlb_head_mix_bwd(const float* p_stack, const float* draw, const float* alpha, float* d_a, float* draw_stack, float* ws,
+                     int K, int B, int E, void* stream);
+int vlb_head_dhidden(const void* hidden, const float* wmask, const float* stats, const float* draw, void* dx, int B, int S,
+                     int E, const int* cu_rows, int total_rows, int accumulate, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * LoRA adapters (peft LoraConfig(r, lora_alpha, lora_dropout) + get_peft_model, litmodule :113-120):
  *   y = x W^T + s * B(A(dropout_p(x))),  s = alpha/r; only A [r,in] and B [out,r] train.

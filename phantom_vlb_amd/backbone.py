@@ -369,15 +369,30 @@ class Backbone:
         store.prefetch(i + direction)
         return {**lw, **full}
 
-    def decoder(self, x, key_mask, B, S, layer_outputs=None, layout=None, layers=None):
+    def decoder(self, x, key_mask, B, S, layer_outputs=None, layout=None, layers=None, stop=None, on_layer=None):
         """``layers``: per-layer weight dicts to run instead of ``self.w.layers`` (``LoraState.merge()``'s list); they are
-        used as they are, never gathered from the sharded store."""
-        for i in range(len(self.w.layers)):
+        used as they are, never gathered from the sharded store.
+        ``stop`` = k < L (``readout_layers``): only layers 1..k run, their weights alone are asked for, the final norm is
+        skipped and the residual stream after layer k comes back.  ``on_layer(k, h)`` is called with every HF
+        ``hidden_states[k]`` as soon as it exists - the output of layer k for k < L, the final norm's output for k = L -
+        so a caller can pool a tapped layer and keep nothing."""
+        L = len(self.w.layers)
+        stop = L if stop is None else int(stop)
+        if not 1 <= stop <= L:
+            raise ValueError(f"decoder: stop={stop} outside [1, {L}]")
+        for i in range(stop):
             lw = self.layer_weights(i) if layers is None else layers[i]
             x = self.decoder_layer(x, lw, key_mask, B, S, layout=layout)
             if layer_outputs is not None:
                 layer_outputs.append(x)
-        return ops.rmsnorm(x, self.w.final_norm, self.g.rms_eps)
+            if on_layer is not None and i + 1 < L:
+                on_layer(i + 1, x)
+        if stop < L:
+            return x
+        x = ops.rmsnorm(x, self.w.final_norm, self.g.rms_eps)
+        if on_layer is not None:
+            on_layer(L, x)
+        return x
 
     # ---------------- frozen vision side one step ahead (software pipelining across steps)
     # The CLIP tower and the STC connector are frozen in the frozen-backbone and LoRA configurations (reference :86-99), so their
@@ -470,9 +485,10 @@ class Backbone:
                     break
         return self._vision_compute(vision_f32, tower_only)
 
-    def forward(self, vision_f32, ids, stages=None, layout=None):
+    def forward(self, vision_f32, ids, stages=None, layout=None, stop=None, on_layer=None):
         """vision fp32 [B,T,3,H,W], ids int64 [B,L] -> hidden bf16 [rows, dim], key_mask uint8.
-        rows = B*S (mask [B,S]) or, with a packed ``layout``, the clips' unpadded tokens (mask [rows])."""
+        rows = B*S (mask [B,S]) or, with a packed ``layout``, the clips' unpadded tokens (mask [rows]).
+        ``stop`` / ``on_layer``: see ``decoder``."""
         g = self.g
         B = vision_f32.shape[0]
         if stages is None:
@@ -483,7 +499,8 @@ class Backbone:
             vid = self.connector(feats, B)
         emb, key_mask = self.splice(ids, vid, layout)
         louts = [] if stages is not None else None
-        hidden = self.decoder(emb, key_mask, B, g.max_len, louts, layout)
+        tap_kw = {} if stop is None and on_layer is None else dict(stop=stop, on_layer=on_layer)
+        hidden = self.decoder(emb, key_mask, B, g.max_len, louts, layout, **tap_kw)
         if stages is not None:
             stages.update(vit_tokens=feats, video_tokens=vid, inputs_embeds=emb, key_mask=key_mask,
                           layer_outputs=louts, hidden=hidden)

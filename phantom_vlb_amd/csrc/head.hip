@@ -699,6 +699,149 @@ __global__ __launch_bounds__(256) void head_dhidden_kernel(const bf16* __restric
   }
 }
 
+// ---------------------------------------------------------------- backward 4, accumulate form: dx += d hidden of a lower tap
+// head_dhidden_kernel's value added into a dx that already holds the gradient from the layers above: live rows (w != 0) are
+// read, added to in fp32 and rounded once; rows with w == 0 are neither read nor written.  One wave per token, one writer
+// per element, no atomics.  HBM-bound: a live row of hidden is read ONCE and held in registers (raw bf16, NI = ceil(E/512)
+// chunks of 8 columns per lane, all loads in flight together, as head_pool_kernel keeps its row) across the two passes,
+// and dx is read while the sums are formed; the additions run in head_dhidden_kernel's order (chunk, then column).
+template <int NI>
+__global__ __launch_bounds__(256) void head_dhidden_acc_kernel(const bf16* __restrict__ hidden, const float* __restrict__ wmask,
+                                                               const float* __restrict__ stats, const float* __restrict__ draw,
+                                                               bf16* __restrict__ dh, int S, int E, int64_t rows, int B,
+                                                               const int* __restrict__ cu) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  int64_t b = row / S, dense = row;
+  if (cu) {
+    int bb = 0;
+    while (bb + 1 < B && row >= cu[bb + 1]) ++bb;
+    b = bb; dense = b * S + (row - cu[bb]);
+  }
+  const float w = wmask[dense];
+  if (w == 0.f) return;
+  bf16* dr = dh + row * E;
+  const float mu = stats[dense * 2], rstd = stats[dense * 2 + 1];
+  const bf16* xr = hidden + row * E;
+  const float* u = draw + b * E;
+  bf16x8 xs[NI], ds[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane * 8 + i * 512;
+    xs[i] = c < E ? *reinterpret_cast<const bf16x8*>(xr + c) : bf16x8{};
+  }
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane * 8 + i * 512;
+    ds[i] = c < E ? *reinterpret_cast<const bf16x8*>(dr + c) : bf16x8{};
+  }
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane * 8 + i * 512;
+    if (c < E) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float g = w * u[c + j]; s1 += g; s2 += g * ((float)xs[i][j] - mu) * rstd; }
+    }
+  }
+  const float m1 = wave_sum(s1) / E, m2 = wave_sum(s2) / E;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int c = lane * 8 + i * 512;
+    if (c < E) {
+      float val[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) val[j] = rstd * (w * u[c + j] - m1 - ((float)xs[i][j] - mu) * rstd * m2);
+      bf16x8 o;
+      {
+#pragma clang fp contract(off)        // the add stays an add: val is the write-mode value, rounded to fp32 as there
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (bf16)((float)ds[i][j] + val[j]);
+      }
+      *reinterpret_cast<bf16x8*>(dr + c) = o;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- layer mix: pooled_raw = sum_k softmax(a)_k P_k
+// P_k [B,E] fp32 are the pooled vectors of the K tapped layers (head_reduce_kernel's output per tap); a bf16 [K] the logits'
+// compute copy (null: K = 1, alpha = 1).  Every thread recomputes the softmax (K <= 64 exps, no LDS, no second launch) and
+// owns 4 consecutive elements; the sum over k runs in ascending order starting FROM the k = 0 term, so K = 1 gives
+// 1.0f * P_0 = the bits of P_0 (a signed zero included).  Thread 0 leaves alpha for the backward.
+constexpr int MIX_KMAX = 64;
+constexpr int MIX_CHUNK = 1024;    // elements per block: 256 threads x f32x4
+
+__device__ __forceinline__ void mix_softmax_stats(const bf16* __restrict__ a, int K, float& amax, float& inv) {
+  amax = (float)a[0];
+  for (int k = 1; k < K; ++k) amax = fmaxf(amax, (float)a[k]);
+  float s = 0.f;
+  for (int k = 0; k < K; ++k) s += expf((float)a[k] - amax);
+  inv = 1.f / s;
+}
+
+__global__ __launch_bounds__(256) void head_mix_fwd_kernel(const float* __restrict__ pstack, const bf16* __restrict__ a,
+                                                           float* __restrict__ alpha, float* __restrict__ pooled_raw, int K,
+                                                           int64_t n) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  float amax = 0.f, inv = 1.f;
+  if (a) mix_softmax_stats(a, K, amax, inv);
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (int k = 0; k < K; ++k) alpha[k] = a ? expf((float)a[k] - amax) * inv : 1.f;
+  if (i >= n) return;                                  // n is a multiple of 8 (E % 8 == 0)
+  auto al_of = [&](int k) { return a ? expf((float)a[k] - amax) * inv : 1.f; };
+  const float al0 = al_of(0);
+  const f32x4 p0 = *reinterpret_cast<const f32x4*>(pstack + i);
+  f32x4 acc = f32x4{al0 * p0[0], al0 * p0[1], al0 * p0[2], al0 * p0[3]};
+  for (int k = 1; k < K; ++k) {
+    const float al = al_of(k);
+    const f32x4 p = *reinterpret_cast<const f32x4*>(pstack + (int64_t)k * n + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] += al * p[j];
+  }
+  *reinterpret_cast<f32x4*>(pooled_raw + i) = acc;
+}
+
+// backward 1: block blk owns elements [blk*1024, +1024) of [B,E]: slab[blk][k] = sum over them of draw * P_k (a thread's 4
+// products in order, then block_sum: fixed order), and draw_stack[k] = alpha_k * draw on the way (K = 1: alpha = 1.0f, a copy).
+__global__ __launch_bounds__(256) void head_mix_bwd_kernel(const float* __restrict__ pstack, const float* __restrict__ draw,
+                                                           const float* __restrict__ alpha, float* __restrict__ slab,
+                                                           float* __restrict__ draw_stack, int K, int64_t n) {
+  __shared__ float red[16];
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  const bool live = i < n;
+  const f32x4 d = live ? *reinterpret_cast<const f32x4*>(draw + i) : f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k = 0; k < K; ++k) {
+    float dot = 0.f;
+    if (live) {
+      const f32x4 p = *reinterpret_cast<const f32x4*>(pstack + (int64_t)k * n + i);
+      const float al = alpha[k];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) dot += d[j] * p[j];
+      *reinterpret_cast<f32x4*>(draw_stack + (int64_t)k * n + i) = f32x4{al * d[0], al * d[1], al * d[2], al * d[3]};
+    }
+    dot = block_sum(dot, red);
+    if (threadIdx.x == 0) slab[(int64_t)blockIdx.x * K + k] = dot;
+  }
+}
+
+// backward 2, one block of 64: thread k sums its column of the slab in block order, then the softmax Jacobian
+//   d a_k = alpha_k (dalpha_k - sum_j alpha_j dalpha_j),  the inner sum in ascending j.  Written, not accumulated.
+__global__ __launch_bounds__(64) void head_mix_da_kernel(const float* __restrict__ slab, const float* __restrict__ alpha,
+                                                         float* __restrict__ d_a, int K, int nblk) {
+  __shared__ float dal[MIX_KMAX];
+  const int k = threadIdx.x;
+  float s = 0.f;
+  if (k < K)
+    for (int blk = 0; blk < nblk; ++blk) s += slab[(int64_t)blk * K + k];
+  dal[k] = s;
+  __syncthreads();
+  if (k >= K) return;
+  float dot = 0.f;
+  for (int j = 0; j < K; ++j) dot += alpha[j] * dal[j];
+  d_a[k] = alpha[k] * (s - dot);
+}
+
 // ---------------------------------------------------------------- standalone HRFConvolveLayer (src/utils.py:44-56)
 // out[b,e] = sum_s w[b,s] * x[b,s,e]: one pass over x, HBM-bound.  grid (HRF_SPLITS, ceil(E/512), B), 4 waves per block; a wave
 // walks every 4th token of its split (tokens with zero weight are skipped), a lane owns 8 columns; the four waves are summed
@@ -776,6 +919,24 @@ int launch_pool(const bf16* hidden, const float* wmask, float* partial, float* s
   if (attr != hipSuccess) { vlb_set_error("head: LDS reservation failed: %s", hipGetErrorString(attr)); return VLB_ERR_LAUNCH; }
   dim3 grid((S + POOL_ROWS - 1) / POOL_ROWS, B);
   hipLaunchKernelGGL((head_pool_kernel<NI>), grid, dim3(512), lds, st, hidden, wmask, partial, stats, S, E, eps, cu);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// LN1 statistics + weighted pool into per-block slabs (at ws), then their fixed-order sum: the pooling half of the forward.
+// vlb_head_fwd and vlb_head_pool both run this, so they give the same (stats, pooled_raw, sumw) bits for the same input.
+int head_pool(const void* hidden, const float* wmask, float* partial, float* stats, float* pooled_raw, float* sumw, int B, int S,
+              int E, float eps, const int* cu_rows, hipStream_t st) {
+  const int nblk = (S + POOL_ROWS - 1) / POOL_ROWS;
+  const int ni = (E + 511) / 512;
+  int rc;
+  if (ni <= 1) rc = launch_pool<1>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
+  else if (ni <= 2) rc = launch_pool<2>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
+  else if (ni <= 4) rc = launch_pool<4>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
+  else if (ni <= 8) rc = launch_pool<8>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
+  else rc = launch_pool<16>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
+  if (rc != VLB_OK) return rc;
+  hipLaunchKernelGGL(head_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, partial, nblk, pooled_raw, sumw, E);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
@@ -907,19 +1068,8 @@ extern "C" int vlb_head_fwd(const void* hidden, const float* wmask, const void* 
                   pooled_raw && sumw && zhat && ln2_rstd && z && pred && loss_terms, "head_fwd: null argument");
   VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_fwd: bad shape B=%d S=%d E=%d V=%d", B, S, E, V);
   hipStream_t st = as_stream(stream);
-  const int nblk = vlb_head_partial_rows(S);
-  float* partial = ws;
-  float* lpart = ws + (int64_t)B * nblk * (E + 2);
-  const int ni = (E + 511) / 512;
-  int rc;
-  if (ni <= 1) rc = launch_pool<1>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
-  else if (ni <= 2) rc = launch_pool<2>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
-  else if (ni <= 4) rc = launch_pool<4>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
-  else if (ni <= 8) rc = launch_pool<8>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
-  else rc = launch_pool<16>((const bf16*)hidden, wmask, partial, stats, B, S, E, eps, cu_rows, st);
-  if (rc != VLB_OK) return rc;
-  hipLaunchKernelGGL(head_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, partial, nblk, pooled_raw, sumw, E);
-  VLB_LAUNCH_CHECK();
+  float* lpart = ws + (int64_t)B * vlb_head_partial_rows(S) * (E + 2);
+  if (int rc = head_pool(hidden, wmask, ws, stats, pooled_raw, sumw, B, S, E, eps, cu_rows, st)) return rc;
   return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, lpart, zhat, ln2_rstd,
                        z, pred, loss_terms, B, E, V, eps, l2_lambda, st);
 }
@@ -1062,6 +1212,79 @@ extern "C" int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, co
   return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
                          d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
                          stream, loss_kind, rowstat);
+}
+
+// ---------------------------------------------------------------- readout from chosen layers: pool, mix, d hidden on their own
+extern "C" int vlb_head_pool(const void* hidden, const float* wmask, float* ws, float* stats, float* pooled_raw, float* sumw, int B,
+                             int S, int E, float eps, const int* cu_rows, void* stream) {
+  VLB_REQUIRE(hidden && wmask && ws && stats && pooled_raw && sumw, "head_pool: null argument");
+  VLB_REQUIRE(B > 0 && S > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_pool: bad shape B=%d S=%d E=%d", B, S, E);
+  return head_pool(hidden, wmask, ws, stats, pooled_raw, sumw, B, S, E, eps, cu_rows, as_stream(stream));
+}
+
+extern "C" int vlb_feature_cache_gather(const float* cache_pooled, const float* cache_sumw, const int* rows, float* pooled_raw,
+                                        float* sumw, int B, int E, int n_rows, void* stream) {
+  VLB_REQUIRE(cache_pooled && cache_sumw && rows && pooled_raw && sumw, "feature_cache_gather: null argument");
+  VLB_REQUIRE(B > 0 && E > 0 && n_rows > 0, "feature_cache_gather: bad shape B=%d E=%d n_rows=%d", B, E, n_rows);
+  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, as_stream(stream), cache_pooled,
+                     cache_sumw, rows, pooled_raw, sumw, E, n_rows);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_mix_fwd(const float* p_stack, const void* a, float* alpha, float* pooled_raw, int K, int B, int E,
+                                void* stream) {
+  VLB_REQUIRE(p_stack && alpha && pooled_raw, "head_mix_fwd: null argument");
+  VLB_REQUIRE(K >= 1 && K <= MIX_KMAX && B > 0 && E > 0 && E % 8 == 0, "head_mix_fwd: bad shape K=%d B=%d E=%d", K, B, E);
+  VLB_REQUIRE(a || K == 1, "head_mix_fwd: K=%d layers need their logits (a is null)", K);
+  const int64_t n = (int64_t)B * E;
+  hipLaunchKernelGGL(head_mix_fwd_kernel, dim3((unsigned)((n + MIX_CHUNK - 1) / MIX_CHUNK)), dim3(256), 0, as_stream(stream), p_stack,
+                     (const bf16*)a, alpha, pooled_raw, K, n);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int64_t vlb_head_mix_ws_floats(int K, int B, int E) {
+  return (int64_t)K * (((int64_t)B * E + MIX_CHUNK - 1) / MIX_CHUNK);
+}
+
+extern "C" int vlb_head_mix_bwd(const float* p_stack, const float* draw, const float* alpha, float* d_a, float* draw_stack,
+                                float* ws, int K, int B, int E, void* stream) {
+  VLB_REQUIRE(p_stack && draw && alpha && d_a && draw_stack && ws, "head_mix_bwd: null argument");
+  VLB_REQUIRE(K >= 1 && K <= MIX_KMAX && B > 0 && E > 0 && E % 8 == 0, "head_mix_bwd: bad shape K=%d B=%d E=%d", K, B, E);
+  hipStream_t st = as_stream(stream);
+  const int64_t n = (int64_t)B * E;
+  const int nblk = (int)((n + MIX_CHUNK - 1) / MIX_CHUNK);
+  hipLaunchKernelGGL(head_mix_bwd_kernel, dim3(nblk), dim3(256), 0, st, p_stack, draw, alpha, ws, draw_stack, K, n);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_mix_da_kernel, dim3(1), dim3(64), 0, st, ws, alpha, d_a, K, nblk);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_dhidden(const void* hidden, const float* wmask, const float* stats, const float* draw, void* dx, int B,
+                                int S, int E, const int* cu_rows, int total_rows, int accumulate, void* stream) {
+  VLB_REQUIRE(hidden && wmask && stats && draw && dx, "head_dhidden: null argument");
+  VLB_REQUIRE(B > 0 && S > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_dhidden: bad shape B=%d S=%d E=%d", B, S, E);
+  const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
+  VLB_REQUIRE(rows > 0 && rows <= (int64_t)B * S, "head_dhidden: total_rows=%d out of range", total_rows);
+  hipStream_t st = as_stream(stream);
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (accumulate) {
+    const int ni = (E + 511) / 512;          // <= 16: E <= 8192
+#define VLB_DH_ACC(NI) hipLaunchKernelGGL(head_dhidden_acc_kernel<NI>, grid, dim3(256), 0, st, (const bf16*)hidden, wmask, stats, draw, \
+                                          (bf16*)dx, S, E, rows, B, cu_rows)
+    if (ni <= 1) VLB_DH_ACC(1);
+    else if (ni <= 2) VLB_DH_ACC(2);
+    else if (ni <= 4) VLB_DH_ACC(4);
+    else if (ni <= 8) VLB_DH_ACC(8);
+    else VLB_DH_ACC(16);
+#undef VLB_DH_ACC
+  } else
+    hipLaunchKernelGGL(head_dhidden_kernel, grid, dim3(256), 0, st, (const bf16*)hidden, wmask, stats, draw, (bf16*)dx, S, E, rows,
+                       B, cu_rows);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
 }
 
 // ---------------------------------------------------------------- the exported layers on their own

@@ -7,6 +7,11 @@ fp32 quantities per clip: ``P[e] = sum_s w_s rstd_s (x_se - mu_s)
 alone (``vlb_head_fwd_cached`` / ``vlb_head_bwd_cached``), on the same fp32 inputs and through the same kernels as the
 uncached step.  Rows are written once (first write wins) and never change afterwards.
 
+With ``readout_layers`` (K tapped decoder layers) a clip is K such vectors, one per tap and taken before the
+learned mix, so the cache does not depend on the mix: ``FeatureCache(layers=K)`` keeps ``pooled`` as ``[K,N,E]`` (``sumw`` is the
+same for every tap) and the fingerprint carries the normalised tap list.  Without the option nothing changes, in memory, on
+disk or in the fingerprint.
+
 Hit or miss is decided on a host-side bitmap (no device sync); the row indices are checked on the host before they are
 uploaded.  Storage is allocated on first use: N * (E + 1) * 4 bytes for a split of N clips.
 """
@@ -22,6 +27,7 @@ import numpy as np
 import torch
 
 from ._lib import LIB_PATH, check, lib
+from .head import check_readout_layers
 from .ops import _stream
 
 FORMAT_VERSION = 1
@@ -72,23 +78,29 @@ def fingerprint(cfg, dataset, lib_path: str | None = None) -> str:
     doc = {"format": FORMAT_VERSION, "geometry": g, "pack_tokens": bool(getattr(cfg, "pack_tokens", True)),
            "weights": weights, "dataset": {"files": files, "n": len(dataset)},
            "libvlb_sha256": _sha256(lib_path or LIB_PATH)}
+    taps = getattr(cfg, "readout_layers", None)
+    if taps is not None:                  # only when set: fingerprints (and caches) from before the option stay valid
+        doc["readout_layers"] = [int(k) for k in check_readout_layers(taps, g["layers"])]
     return hashlib.sha256(json.dumps(doc, sort_keys=True).encode()).hexdigest()
 
 
 class FeatureCache:
     """(pooled_raw, sumw) per dataset index of one split (train and val index spaces differ: one instance each)."""
 
-    def __init__(self, split: str, n: int, dim: int, device):
-        if n <= 0 or dim <= 0:
-            raise ValueError(f"FeatureCache({split!r}): n={n}, dim={dim}")
+    def __init__(self, split: str, n: int, dim: int, device, layers: int | None = None):
+        """``layers`` = K with ``readout_layers`` set (K tapped layers: one ``pooled`` slab each, [K,N,E]; ``sumw`` does
+        not depend on the layer); None: the single [N,E] slab of the last layer, in memory and on disk as ever."""
+        if n <= 0 or dim <= 0 or (layers is not None and layers <= 0):
+            raise ValueError(f"FeatureCache({split!r}): n={n}, dim={dim}, layers={layers}")
         self.split, self.n, self.E, self.dev = split, int(n), int(dim), torch.device(device)
+        self.layers = None if layers is None else int(layers)
         self.valid = np.zeros(self.n, dtype=bool)        # host-side: hit / miss never syncs the device
         self.pooled = self.sumw = None                    # fp32 [N,E] / [N] on the device, allocated on first store
         self.hits = self.lookups = 0                      # batches since the last reset_counters()
 
     @property
     def nbytes(self) -> int:
-        return self.n * (self.E + 1) * 4
+        return self.n * ((self.layers or 1) * self.E + 1) * 4
 
     def _indices(self, indices) -> np.ndarray:
         idx = np.asarray(indices.cpu() if torch.is_tensor(indices) else indices, dtype=np.int64).reshape(-1)
@@ -102,9 +114,12 @@ class FeatureCache:
             host = host.pin_memory()
         return host.to(self.dev, non_blocking=True)
 
+    def _pooled_shape(self) -> tuple:
+        return (self.n, self.E) if self.layers is None else (self.layers, self.n, self.E)
+
     def _alloc(self):
         if self.pooled is None:
-            self.pooled = torch.zeros(self.n, self.E, dtype=torch.float32, device=self.dev)
+            self.pooled = torch.zeros(*self._pooled_shape(), dtype=torch.float32, device=self.dev)
             self.sumw = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
 
     def lookup(self, indices) -> bool:
@@ -139,9 +154,15 @@ class FeatureCache:
         rows[fresh] = idx[fresh]
         self._alloc()
         dev_rows = self._upload(rows)
-        check(lib.vlb_feature_cache_store(head.pooled_raw.data_ptr(), head.sumw.data_ptr(), dev_rows.data_ptr(),
-                                          self.pooled.data_ptr(), self.sumw.data_ptr(), idx.size, self.E, self.n, _stream()),
-              "vlb_feature_cache_store")
+        if (self.layers or 0) != getattr(head, "K", 0):
+            raise ValueError(f"feature cache {self.split!r}: {self.layers} slab(s) per clip, the head taps {head.K} layer(s)")
+        # per slab: the tap's pooled vector (before the mix, so the cache outlives any change of the mix); sumw is the taps' own
+        slabs = [(head.pooled_raw, head.sumw, self.pooled)] if self.layers is None else \
+            [(head.p_stack[k], head.tap_sumw, self.pooled[k]) for k in range(self.layers)]
+        for src, sw, dst in slabs:
+            check(lib.vlb_feature_cache_store(src.data_ptr(), sw.data_ptr(), dev_rows.data_ptr(), dst.data_ptr(),
+                                              self.sumw.data_ptr(), idx.size, self.E, self.n, _stream()),
+                  "vlb_feature_cache_store")
         self.valid[idx[fresh]] = True
         return int(fresh.sum())
 
@@ -172,7 +193,10 @@ class FeatureCache:
             os.replace(tmp, path)
         tmp = jp + ".tmp"
         with open(tmp, "w") as f:
-            json.dump({"format": FORMAT_VERSION, "fingerprint": fp, "n": self.n, "dim": self.E, "split": self.split}, f)
+            meta = {"format": FORMAT_VERSION, "fingerprint": fp, "n": self.n, "dim": self.E, "split": self.split}
+            if self.layers is not None:
+                meta["layers"] = self.layers
+            json.dump(meta, f)
         os.replace(tmp, jp)
 
     def load(self, d: str, fp: str) -> bool:
@@ -183,12 +207,12 @@ class FeatureCache:
             return False
         with open(jp) as f:
             meta = json.load(f)
-        if meta.get("fingerprint") != fp or meta.get("n") != self.n or meta.get("dim") != self.E:
+        if meta.get("fingerprint") != fp or meta.get("n") != self.n or meta.get("dim") != self.E or meta.get("layers") != self.layers:
             warnings.warn(f"feature cache {self.split!r} under {d}: fingerprint mismatch (model, data, geometry or libvlb "
                           "changed) - ignored, the features are recomputed and the files overwritten")
             return False
         pooled, sumw = np.load(pp), np.load(sp)
-        if pooled.shape != (self.n, self.E) or sumw.shape != (self.n,) or pooled.dtype != np.float32 or sumw.dtype != np.float32:
+        if pooled.shape != self._pooled_shape() or sumw.shape != (self.n,) or pooled.dtype != np.float32 or sumw.dtype != np.float32:
             warnings.warn(f"feature cache {self.split!r} under {d}: arrays do not match their metadata - ignored")
             return False
         self._alloc()

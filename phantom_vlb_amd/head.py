@@ -4,6 +4,9 @@
 Mirrors the reference's head modules (``layer_norm1``, ``hrf_layer``, ``layer_norm2``, ``dropout``,
 ``ridge_layer.linear``; src/litmodule/videollama2_vlb_litmodule.py:210-226,245-254 and
 src/utils.py:40-73) but runs as the fused vlb_head_fwd / vlb_head_bwd kernels.
+Opt-in, ``readout_layers``: the head reads K chosen decoder layers instead of the last one - each is pooled on its own
+(vlb_head_pool), the pooled vectors are mixed by softmax(``layer_mix.weight``) (vlb_head_mix_fwd / _bwd) and the rest of the
+head runs on the mix; see ``begin`` / ``tap`` / ``forward_tapped`` / ``backward_tapped`` / ``dhidden`` and DESIGN §5.3.3.
 Trainable parameters keep an fp32 master (what AdamW updates) and the bf16 copy the kernels read -
 the reference stores them in bf16 (``dtype=self.config.dtype``), i.e. the kernels see the same values.
 """
@@ -31,12 +34,57 @@ def check_loss(loss, num_target):
         raise ValueError(f"loss='pearson' needs num_target >= 2 (got {num_target}): one target has no spread to correlate")
 
 
+LAYER_MIX = "layer_mix.weight"       # logits of the learned mix over the tapped layers (K > 1 only), fp32 master [K]
+MAX_TAPS = 64                        # MIX_KMAX of head.hip
+
+
+def check_readout_layers(layers, num_layers: int | None = None):
+    """``readout_layers`` as the module takes it: None, or a non-empty list of decoder layers to read the head from.
+    k in [1, L] is the output of decoder layer k (HF ``hidden_states[k]``; L = what the head reads by default, after the
+    final norm); k in [-L, -1] counts from the end (``-1`` = L).  With ``num_layers`` = L known the list is returned
+    normalised and must be strictly ascending; without it only what needs no L is checked and the list comes back as is."""
+    if layers is None:
+        return None
+    if isinstance(layers, (str, bytes)) or not hasattr(layers, "__iter__"):
+        raise ValueError(f"readout_layers={layers!r}: a list of decoder layer numbers is needed")
+    out = list(layers)
+    if not out:
+        raise ValueError("readout_layers=[]: at least one decoder layer is needed (None reads the last one, as ever)")
+    for k in out:
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"readout_layers={out!r}: {k!r} is not an integer layer number")
+        if k == 0:
+            raise ValueError(f"readout_layers={out!r}: 0 (the spliced embeddings) cannot be tapped; layers count from 1")
+    if num_layers is None:
+        return out
+    L = int(num_layers)
+    norm = []
+    for k in out:
+        if not (1 <= k <= L or -L <= k <= -1):
+            raise ValueError(f"readout_layers={out!r}: {k} is outside [1, {L}] and [-{L}, -1] (the decoder has {L} layers)")
+        norm.append(k if k > 0 else k + L + 1)
+    for prev, k in zip(norm, norm[1:]):
+        if k <= prev:
+            raise ValueError(f"readout_layers={out!r}: layer {k} after layer {prev} - the (normalised) list {norm} must be "
+                             "strictly ascending")
+    if len(norm) > MAX_TAPS:
+        raise ValueError(f"readout_layers={out!r}: {len(norm)} layers, at most {MAX_TAPS} can be mixed")
+    return norm
+
+
 class BrainHead:
     def __init__(self, dim: int, num_target: int, l2_lambda: float, eps: float, device, sd: dict | None = None,
-                 seed: int = 1234, loss: str = "mse"):
+                 seed: int = 1234, loss: str = "mse", readout_layers=None):
         check_loss(loss, num_target)
         self.loss, self.loss_kind = loss, LOSS_KINDS[loss]
         self.E, self.V, self.l2_lambda, self.eps, self.dev = dim, num_target, float(l2_lambda), float(eps), device
+        # taps (normalised by the caller: check_readout_layers with L); K = 0: the fused path on one hidden tensor, as ever
+        self.readout_layers = None if readout_layers is None else tuple(int(k) for k in readout_layers)
+        self.K = 0 if self.readout_layers is None else len(self.readout_layers)
+        if self.readout_layers is not None and not 1 <= self.K <= MAX_TAPS:
+            raise ValueError(f"readout_layers={list(self.readout_layers)!r}: 1 to {MAX_TAPS} layers are needed")
+        self.param_names = HEAD_PARAMS + ((LAYER_MIX,) if self.K > 1 else ())
+        self._tap_cap = None
         self.master: dict[str, torch.Tensor] = {}
         if sd is None:
             gen = torch.Generator(device="cpu").manual_seed(seed)
@@ -49,10 +97,16 @@ class BrainHead:
             }
             # the reference creates these modules in bf16 (dtype=self.config.dtype): start from bf16-representable values
             sd = {n: t.to(BF16).float() for n, t in sd.items()}
-        for n in HEAD_PARAMS:
+        for n in self.param_names:
             # handed-in tensors are taken as they are (bf16 checkpoints widen exactly; an fp32 checkpoint of the
             # masters resumes at full precision)
+            if n == LAYER_MIX and n not in sd:        # optional on load: a uniform mix, softmax(0)
+                self.master[n] = torch.zeros(self.K, dtype=torch.float32, device=device)
+                continue
             self.master[n] = sd[n].detach().to(device=device, dtype=torch.float32).contiguous()
+        if self.K > 1 and tuple(self.master[LAYER_MIX].shape) != (self.K,):
+            raise ValueError(f"{LAYER_MIX}: {tuple(self.master[LAYER_MIX].shape)} handed in, readout_layers="
+                             f"{list(self.readout_layers)} needs ({self.K},)")
         self.compute = {n: t.to(BF16) for n, t in self.master.items()}
         self.grads = {n: torch.zeros_like(t) for n, t in self.master.items()}
         self._cap = None
@@ -141,6 +195,15 @@ class BrainHead:
         rows = cache.rows(indices)
         if rows.numel() != B:
             raise ValueError(f"head: {rows.numel()} cache rows for a batch of {B}")
+        if self.K:                        # K slabs per clip -> the taps' pooled vectors, then the tapped forward as uncached
+            if cache.layers != self.K:
+                raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for {self.K} tapped layer(s)")
+            self.begin(B, self._cap[1] if self._cap is not None and self._cap[0] == B else 1)
+            for k in range(self.K):
+                check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
+                                                   self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
+                                                   _stream()), "vlb_feature_cache_gather")
+            return self.forward_tapped(y, keep_scale)
         if self._cap is None or self._cap[0] != B:
             self._buffers(B, 1)           # no pooling workspace needed; buffers of an uncached step of this B serve as they are
         self._saved_cached = (y, keep_scale)
@@ -157,6 +220,92 @@ class BrainHead:
         if self.loss_kind:
             self._loss_fwd(y, B, 0)
         return self.pred, self.loss_terms
+
+    # ------------------------------------------------------------------ readout from chosen decoder layers (readout_layers)
+    # Per step: begin(B, S); tap(i, hidden_i, wmask, layout) as each tapped layer's output exists (only its LN1 statistics
+    # [B,S,2] and pooled vector P_i [B,E] are kept, never the tensor); forward_tapped(y, keep); backward_tapped(...);
+    # dhidden(i, hidden_i, into) for the taps' terms of d loss / d hidden, highest tap first (write), lower ones added.
+    def begin(self, B, S):
+        if not self.K:
+            raise RuntimeError("head: begin() / tap() are the readout_layers API; this head reads one hidden tensor (forward())")
+        if self._cap is None or self._cap[0] != B or self._cap[1] < S:
+            self._buffers(B, S)
+        if self._tap_cap != (B, S):
+            d, E, K, f32 = self.dev, self.E, self.K, torch.float32
+            self.tap_stats = torch.zeros(K, B, S, 2, dtype=f32, device=d)
+            self.p_stack = torch.empty(K, B, E, dtype=f32, device=d)           # P_k: pooled_raw of tap k
+            self.tap_sumw = torch.empty(B, dtype=f32, device=d)                # the same for every tap (same mask, same order)
+            self.mixed = torch.empty(B, E, dtype=f32, device=d)                # sum_k alpha_k P_k
+            self.alpha = torch.empty(K, dtype=f32, device=d)
+            self.draw_stack = torch.empty(K, B, E, dtype=f32, device=d)        # alpha_k * d loss / d pooled_raw
+            self.mix_ws = torch.empty(max(1, lib.vlb_head_mix_ws_floats(K, B, E)), dtype=f32, device=d)
+            self._d_a1 = torch.empty(1, dtype=f32, device=d)                   # K = 1: no logit, its (zero) gradient lands here
+            self.identity_rows = torch.arange(B, dtype=torch.int32, device=d)
+            self._tap_cap = (B, S)
+        self._tap_meta = None
+
+    def tap(self, i, hidden, wmask, layout=None):
+        """LN1 statistics and pooled vector of tap i (0-based position in ``readout_layers``) from its hidden tensor
+        (bf16 rows x E, dense [B*S] or packed by ``layout``): the pooling half of vlb_head_fwd."""
+        B, S = wmask.shape
+        packed = layout is not None and layout.packed
+        rows = layout.rows if packed else B * S
+        if hidden.numel() != rows * self.E or (packed and (layout.B, layout.S) != (B, S)):
+            raise ValueError(f"head: hidden has {hidden.numel() // self.E} rows, layout expects {rows}")
+        if self._tap_cap != (B, S) or not 0 <= i < self.K:
+            raise ValueError(f"head: tap({i}) of a [{B},{S}] mask after begin{self._tap_cap} with {self.K} tap(s)")
+        cu = layout.cu if packed else None
+        self._tap_meta = (wmask, cu, rows)
+        check(lib.vlb_head_pool(hidden.data_ptr(), wmask.data_ptr(), self.ws.data_ptr(), self.tap_stats[i].data_ptr(),
+                                self.p_stack[i].data_ptr(), self.tap_sumw.data_ptr(), B, S, self.E, self.eps,
+                                None if cu is None else cu.data_ptr(), _stream()), "vlb_head_pool")
+
+    def forward_tapped(self, y, keep_scale=None):
+        """alpha = softmax(layer_mix.weight), pooled_raw = sum_k alpha_k P_k, then the tail of the head as
+        vlb_head_fwd_cached runs it on (pooled_raw, sumw) -> (pred f32 [B,V], loss_terms f32[3])."""
+        B = y.shape[0]
+        c = self.compute
+        check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), c[LAYER_MIX].data_ptr() if self.K > 1 else None,
+                                   self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
+              "vlb_head_mix_fwd")
+        self._saved_cached = (y, keep_scale)
+        check(lib.vlb_head_fwd_cached(self.mixed.data_ptr(), self.tap_sumw.data_ptr(), self.identity_rows.data_ptr(),
+                                      c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
+                                      c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
+                                      c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
+                                      y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
+                                      self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
+                                      self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
+                                      self.loss_terms.data_ptr(), B, self.E, self.V, B, self.eps, self.l2_lambda,
+                                      _stream()), "vlb_head_fwd_cached")
+        if self.loss_kind:
+            self._loss_fwd(y, B, 0)
+        return self.pred, self.loss_terms
+
+    def backward_tapped(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
+        """Head gradients on the mixed pooled vector (vlb_head_bwd_cached: fills self.grads), then the mix's own:
+        grads['layer_mix.weight'] (K > 1; written) and draw_stack[k] = alpha_k * d loss / d pooled_raw for dhidden()."""
+        self.backward_cached(loss_scale, l2_scale)
+        B = self._saved_cached[0].shape[0]
+        d_a = self.grads[LAYER_MIX] if self.K > 1 else self._d_a1
+        check(lib.vlb_head_mix_bwd(self.p_stack.data_ptr(), self.dpooled.data_ptr(), self.alpha.data_ptr(), d_a.data_ptr(),
+                                   self.draw_stack.data_ptr(), self.mix_ws.data_ptr(), self.K, B, self.E, _stream()),
+              "vlb_head_mix_bwd")
+
+    def dhidden(self, i, hidden, into=None):
+        """Tap i's term of d loss / d hidden_i (bf16 [rows,E]) from its hidden tensor, statistics and draw_stack[i].
+        ``into`` None: a fresh tensor, zero-weight rows zeroed (vlb_head_bwd's last launch).  ``into`` = dx: added to dx
+        in place on the rows with a non-zero weight; the others are not touched."""
+        wmask, cu, rows = self._tap_meta
+        B, S = wmask.shape
+        if hidden.numel() != rows * self.E or (into is not None and (into.numel() != rows * self.E or into.dtype != BF16)):
+            raise ValueError(f"head: dhidden({i}) needs bf16 [{rows},{self.E}] tensors")
+        dx = torch.empty(rows, self.E, dtype=BF16, device=self.dev) if into is None else into
+        check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), self.tap_stats[i].data_ptr(),
+                                   self.draw_stack[i].data_ptr(), dx.data_ptr(), B, S, self.E,
+                                   None if cu is None else cu.data_ptr(), rows, 0 if into is None else 1, _stream()),
+              "vlb_head_dhidden")
+        return dx
 
     def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
         """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
-from .head import HEAD_PARAMS, BrainHead, check_loss
+from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers
 from .optim import VlbAdamW
 
 
@@ -168,6 +168,9 @@ class VLBLitModuleConfig:
     feature_cache_dir: str | None = None    # persist the feature caches there (feature_cache.py; loaded on a matching fingerprint)
     merge_lora_for_eval: bool = False   # LoRA only: eval-mode forwards run the frozen-path decoder on merged weights (LoraState.merge)
     loss: str = "mse"               # "mse" (reference :302) | "cosine" (its docstring's alternative, :290-301) | "pearson"; + l2 always
+    # decoder layers the head reads (HF hidden_states[k], k in [1, L] or [-L, -1]; more than one: a learned softmax mix of their
+    # pooled features, ``layer_mix.weight``); the decoder stops at the highest.  None: hidden_states[-1], as the reference
+    readout_layers: list[int] | None = None
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -178,6 +181,13 @@ class VLBLitModuleConfig:
         if self.merge_lora_for_eval and not self.use_lora:
             raise ValueError("merge_lora_for_eval=True needs use_lora=True: without adapters there is nothing to merge")
         check_loss(self.loss, self.num_target)
+        if self.readout_layers is not None:
+            if not self.freeze_backbone and not self.use_lora:
+                raise ValueError("readout_layers with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported: "
+                                 "the connector and embedding backward below a tapped layer is out of scope.  Use "
+                                 "freeze_backbone=True or use_lora=True")
+            # the geometry name fixes L here already; configure_model checks again against the geometry it builds
+            self.readout_layers = check_readout_layers(self.readout_layers, resolve_geometry(self).layers)
 
 
 def resolve_geometry(cfg: VLBLitModuleConfig) -> Geometry:
@@ -263,14 +273,18 @@ class VLBLitModule(_Base):
                 state_dict = Weights.random_state_dict(g, dev, seed=cfg.init_seed)
         weights = Weights(g, state_dict, dev, keep_transposed=bool(cfg.use_lora) or full_ft, gate_up_interleaved=not full_ft)
         lora_state = {k: v for k, v in state_dict.items() if ".lora_" in k} or None
+        taps = check_readout_layers(getattr(cfg, "readout_layers", None), g.layers)
+        if taps is not None and full_ft:
+            raise ValueError("readout_layers with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported")
         if head_state is None and all(n in state_dict for n in HEAD_PARAMS):
-            head_state = {n: state_dict[n] for n in HEAD_PARAMS}
+            # layer_mix.weight is optional on load: a checkpoint from before the taps starts from the uniform mix
+            head_state = {n: state_dict[n] for n in HEAD_PARAMS + (LAYER_MIX,) if n in state_dict}
         del state_dict
         self.backbone = Backbone(g, weights)
         self.nnmodule = _Attr(config=_Attr(hidden_size=g.dim, tokenizer_model_max_length=g.max_len,
                                            num_frames=g.num_frames, use_cache=False), backbone=self.backbone)
         self.head = BrainHead(g.dim, cfg.num_target, cfg.l2_lambda, g.ln_eps, dev, sd=head_state, seed=cfg.init_seed,
-                              loss=getattr(cfg, "loss", "mse"))
+                              loss=getattr(cfg, "loss", "mse"), readout_layers=taps)
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -290,7 +304,7 @@ class VLBLitModule(_Base):
     def _named_masters(self):
         """(name, fp32 master tensor) of everything AdamW updates: head always; LoRA A/B when use_lora
         (reference :86-120: backbone frozen / peft freezes the base)."""
-        out = [(n, self.head.master[n]) for n in HEAD_PARAMS]
+        out = [(n, self.head.master[n]) for n in self.head.param_names]
         if self.lora is not None:
             out += self.lora.named_masters()
         if self.full is not None:       # full fine-tune: every backbone tensor outside the vision tower (kernel layouts)
@@ -342,7 +356,7 @@ class VLBLitModule(_Base):
     def trainable_state_dict(self) -> dict:
         """Trainables on the host under their upstream / peft names and layouts (LoRA B as [out, r], rank padding
         removed): what checkpoints store and what ``configure_model(state_dict=...)`` / peft accept."""
-        sd = {n: self.head.master[n].detach().cpu().clone() for n in HEAD_PARAMS}
+        sd = {n: self.head.master[n].detach().cpu().clone() for n in self.head.param_names}
         if self.lora is not None:
             sd.update({n: t.cpu() for n, t in self.lora.state_dict().items()})
         if self.full is not None:
@@ -351,7 +365,7 @@ class VLBLitModule(_Base):
 
     def load_trainable_state_dict(self, sd: dict) -> None:
         """Inverse of ``trainable_state_dict`` into the fp32 masters; bf16 copies and derived layouts are rebuilt."""
-        for n in HEAD_PARAMS:
+        for n in self.head.param_names:
             self.head.master[n].copy_(sd[n].to(self.device, torch.float32))
             self.head.compute[n].copy_(self.head.master[n])
         if self.lora is not None:
@@ -395,17 +409,26 @@ class VLBLitModule(_Base):
         vis = self._vision_tensor(x_video)
         ids = x_lang.to(self.device, torch.int64).contiguous()
         B = ids.shape[0]
+        taps = self.head.readout_layers
+        tap_kw = {}
+        if taps is not None:
+            # the decoder stops at the highest tap; every tapped layer is pooled as soon as it exists (nothing is kept here)
+            self.head.begin(*weight_mask.shape)
+            tap_kw = dict(stop=taps[-1], on_layer=lambda k, h: self.head.tap(taps.index(k), h, weight_mask, layout) if k in taps else None)
         if self.lora is not None and not self.training and getattr(self.config, "merge_lora_for_eval", False):
-            hidden, key_mask = self._merged_forward(vis, ids, layout)      # the same adapters, folded into the weights
+            hidden, key_mask = self._merged_forward(vis, ids, layout, **tap_kw)      # the same adapters, folded into the weights
         elif self.lora is not None:      # eval mode keeps the adapters (peft eval: dropout off), like the reference's validation
-            hidden, key_mask = self.lora.forward(self.backbone, vis, ids, layout, train=self.training)
+            hidden, key_mask = self.lora.forward(self.backbone, vis, ids, layout, train=self.training, **tap_kw)
         elif self.full is not None and self.training:      # full fine-tune: forward that keeps what backward needs
             hidden, key_mask = self.full.forward(vis, ids, layout, ids_host=ids_host)
         else:
-            hidden, key_mask = self.backbone.forward(vis, ids, layout=layout)
+            hidden, key_mask = self.backbone.forward(vis, ids, layout=layout, **tap_kw)
         if y is None:
             y = torch.zeros(B, self.config.num_target, dtype=torch.float32, device=self.device)
-        pred, terms = self.head.forward(hidden, weight_mask, y, keep_scale, layout)
+        if taps is not None:
+            pred, terms = self.head.forward_tapped(y, keep_scale)
+        else:
+            pred, terms = self.head.forward(hidden, weight_mask, y, keep_scale, layout)
         self._loss_terms = terms
         return pred, terms[1]
 
@@ -419,13 +442,14 @@ class VLBLitModule(_Base):
                              "every rank holds 1/world of each layer, and merging gathered shards is out of scope")
         return self.lora.merge()
 
-    def _merged_forward(self, vis, ids, layout):
+    def _merged_forward(self, vis, ids, layout, stop=None, on_layer=None):
         """Eval-mode forward of a LoRA module on merged weights: the frozen path (``Backbone.decoder_layer``: one GEMM per
         projection, SwiGLU in the epilogue) instead of ``LoraState.decoder_forward(train=False)``."""
         bb, g = self.backbone, self.geometry
         layers = self._merged_layers()
         emb, key_mask = bb.splice(ids, bb.video_tokens(vis), layout)
-        return bb.decoder(emb, key_mask, vis.shape[0], g.max_len, layout=layout, layers=layers), key_mask
+        tap_kw = {} if stop is None and on_layer is None else dict(stop=stop, on_layer=on_layer)
+        return bb.decoder(emb, key_mask, vis.shape[0], g.max_len, layout=layout, layers=layers, **tap_kw), key_mask
 
     def merged_state_dict(self) -> dict:
         """The decoder linears with the adapters merged in (``W + (alpha/r) B A``, bf16, host) under their upstream names,
@@ -436,7 +460,7 @@ class VLBLitModule(_Base):
             lins = destack_decoder_layer(self.geometry, mw["wqkv"], mw["wo"], mw["wdown"], mw.get("wgu"), mw.get("wgu_il"))
             for n, t in lins.items():
                 sd[f"model.layers.{i}.{n}.weight"] = t.detach().cpu().contiguous().clone()
-        sd.update({n: self.head.master[n].detach().cpu().clone() for n in HEAD_PARAMS})
+        sd.update({n: self.head.master[n].detach().cpu().clone() for n in self.head.param_names})
         return sd
 
     def save_merged(self, path: str) -> str:
@@ -501,7 +525,8 @@ class VLBLitModule(_Base):
             ds.with_index = True
             c = self.feature_caches.get(split)
             if c is None or c.n != len(ds):
-                c = self.feature_caches[split] = FeatureCache(split, len(ds), self.geometry.dim, self.device)
+                c = self.feature_caches[split] = FeatureCache(split, len(ds), self.geometry.dim, self.device,
+                                                              layers=self.head.K or None)     # one slab per tapped layer
             fps[split] = fingerprint(cfg, ds)
             if cfg.feature_cache_dir and not c.complete():
                 c.load(cfg.feature_cache_dir, fps[split])
@@ -549,6 +574,18 @@ class VLBLitModule(_Base):
     def on_validation_epoch_end(self):
         if self.config.cache_features:
             self.feature_cache_end("val")
+        self.log_readout_alpha()
+
+    def log_readout_alpha(self):
+        """``readout/alpha_<layer>`` = softmax(layer_mix.weight) of the bf16 copy the kernels read, once per validation
+        epoch (both runners call this at its end); nothing without ``readout_layers``."""
+        head = getattr(self, "head", None)
+        taps = None if head is None else head.readout_layers
+        if taps is None:
+            return
+        alpha = torch.softmax(head.compute[LAYER_MIX].float(), 0).tolist() if head.K > 1 else [1.0]
+        for k, a in zip(taps, alpha):
+            self.log(f"readout/alpha_{k}", a)
 
     def prefetch_vision(self, batch, ready_event=None):
         """Start the frozen vision side (CLIP tower + STC connector) of a FUTURE batch on a side stream, so that it runs under
@@ -596,12 +633,18 @@ class VLBLitModule(_Base):
         self.backbone.launch_deferred_video_tokens()         # a future batch's frozen vision side: behind this forward, under this backward
         need_dh = self.lora is not None or self.full is not None
         scale = 1.0 / (self.world_size * k)
-        if self._cached_step:
+        tapped = self.head.readout_layers is not None
+        if tapped:          # cached or not: the head's gradients on the mixed features, then the mix's own (and alpha_k * draw)
+            self.head.backward_tapped(loss_scale=scale, l2_scale=scale)
+            dh = None
+        elif self._cached_step:
             self.head.backward_cached(loss_scale=scale, l2_scale=scale)
             dh = None
         else:
             dh = self.head.backward(need_dhidden=need_dh, loss_scale=scale, l2_scale=scale)
-        if self.lora is not None:
+        if self.lora is not None and tapped:
+            self.lora.backward(self.backbone, None, head=self.head)      # d hidden enters at the taps
+        elif self.lora is not None:
             self.lora.backward(self.backbone, dh)
         elif self.full is not None:
             self.full.backward(dh)

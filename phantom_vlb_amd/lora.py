@@ -328,27 +328,38 @@ class LoraState:
         gu, t = self._adapted(x, lw["wgu"], blk, seeds, slot=slot, p=p)
         return ops.swiglu(gu), gu, t
 
-    def forward(self, backbone, vision_f32, ids, layout=None, train=True):
+    def forward(self, backbone, vision_f32, ids, layout=None, train=True, stop=None, on_layer=None):
         """Forward of the whole backbone with the adapters.  train=True: dropout on, decoder activations kept for
         backward.  train=False (validation; peft in eval mode): same adapters, no dropout, nothing kept.
-        ``layout``: packed RowLayout (rows without the clips' padded tails) or None for dense [B,S]."""
+        ``layout``: packed RowLayout (rows without the clips' padded tails) or None for dense [B,S].
+        ``stop`` / ``on_layer``: see ``decoder_forward``."""
         g = self.g
         B = vision_f32.shape[0]
         vid = backbone.video_tokens(vision_f32)          # frozen: no activations kept; may have been started one step ahead
         x, key_mask = backbone.splice(ids, vid, layout)
-        return self.decoder_forward(backbone, x, key_mask, B, layout, train=train)
+        if stop is None and on_layer is None:          # the default path's call, as it was
+            return self.decoder_forward(backbone, x, key_mask, B, layout, train=train)
+        return self.decoder_forward(backbone, x, key_mask, B, layout, train=train, stop=stop, on_layer=on_layer)
 
-    def decoder_forward(self, backbone, x, key_mask, B, layout=None, train=True):
+    def decoder_forward(self, backbone, x, key_mask, B, layout=None, train=True, stop=None, on_layer=None):
         """The adapted decoder on spliced embeddings x [rows, dim].  train=True draws this step's dropout masks and keeps
         every layer's activations for backward().  train=False (validation / inference) runs the same layers with dropout
         off and keeps nothing: it touches neither ``step`` (the dropout seed sequence) nor what a pending backward() reads
-        (``saved``, ``x_last``, ``key_mask``, ``B``, ``layout``), and no activation outlives the layer after its own."""
+        (``saved``, ``x_last``, ``key_mask``, ``B``, ``layout``), and no activation outlives the layer after its own.
+        ``stop`` = k < L and ``on_layer(k, h)`` as in ``Backbone.decoder`` (``readout_layers``): layers above k are not run,
+        draw no dropout seeds and save nothing, and the residual stream after layer k comes back instead of the final
+        norm's output.  In training a tapped layer k < L is the next layer's saved ``x`` (or ``x_last`` for k = stop) and
+        the final norm's output is kept as ``h_last``: what backward(head=...) hands to the head's dhidden."""
         g, w = self.g, self.w
+        L = len(self.layers)
+        stop = L if stop is None else int(stop)
+        if not 1 <= stop <= L:
+            raise ValueError(f"decoder_forward: stop={stop} outside [1, {L}]")
         p = None if train else 0.0                  # None: the configured dropout (_lora_t)
         if train:
             self.saved = []
             self.step += 1
-        for li, lay in enumerate(self.layers):
+        for li, lay in enumerate(self.layers[:stop]):
             lw = backbone.layer_weights(li)
             sd = [self._seed(li, k) for k in range(7)] if train else [None] * 7     # no dropout: no seeds
             h1 = ops.rmsnorm(x, lw["in_norm"], g.rms_eps)
@@ -363,9 +374,18 @@ class LoraState:
                 self.saved.append(dict(x=x, h1=h1, qkv=qkv, a=a, lse=lse, x2=x2, h2=h2, gu=gu, hh=hh, t_qkv=t_qkv, t_o=t_o,
                                        t_gu=t_gu, t_d=t_d, seeds=sd))
             x = x3
+            if on_layer is not None and li + 1 < L:
+                on_layer(li + 1, x)
         if train:
-            self.x_last, self.key_mask, self.B, self.layout = x, key_mask, B, layout
-        return ops.rmsnorm(x, w.final_norm, g.rms_eps), key_mask
+            self.x_last, self.key_mask, self.B, self.layout, self.stop, self.h_last = x, key_mask, B, layout, stop, None
+        if stop < L:
+            return x, key_mask
+        h = ops.rmsnorm(x, w.final_norm, g.rms_eps)
+        if on_layer is not None:
+            on_layer(L, h)
+            if train:
+                self.h_last = h
+        return h, key_mask
 
     # ------------------------------------------------------------------ backward
     def _group_backward(self, li, gname, dy, x_in, t, seeds, W_t, need_dx, swiglu_gu=None):
@@ -417,13 +437,45 @@ class LoraState:
                 lora_dx_masked(u[:, r0:], lay["At"][:, r0:], dx, n, self.p, gs[r0 // 16:(r0 + n) // 16])
         return dx if swiglu_gu is None else ops.swiglu_bwd(swiglu_gu, dx)
 
-    def backward(self, backbone, dhidden):
-        """dhidden: d loss / d (post-final-norm hidden) bf16 [B*S, dim].  Fills self.grads."""
+    def _zero_layer_grads(self, li):
+        """Adapter gradients of a layer the step did not run: exactly zero.  Only backward() writes them, so a layer zeroed
+        once stays zero until it runs again (``_zero_layers``)."""
+        zl = self.__dict__.setdefault("_zero_layers", set())
+        if li in zl:
+            return
+        for gname, targets in GROUPS:
+            self.grad_A[li][gname].zero_()
+            for t in targets:
+                self.grads[f"model.layers.{li}.{t}.lora_B.weight"].zero_()
+        zl.add(li)
+
+    def backward(self, backbone, dhidden, head=None):
+        """dhidden: d loss / d (post-final-norm hidden) bf16 [B*S, dim].  Fills self.grads.
+        ``head`` (``readout_layers``; dhidden is None): the gradient enters at the taps instead.  The pass starts at the
+        highest tap t_K = ``stop`` - tap L through the final norm's backward, a lower one straight from the head's dhidden
+        (write mode) - and once an iteration has formed dx = d loss / d H_li, a tap at li adds its term in place (accumulate
+        mode).  Layers above t_K get zero gradients; ``grad_hook`` still fires once for every layer, highest first."""
         g, w = self.g, self.w
         B, layout = self.B, self.layout
-        dx = ops.rmsnorm_bwd(self.x_last, w.final_norm, dhidden, g.rms_eps)
+        stop, lower = g.layers, {}
+        if head is None:
+            dx = ops.rmsnorm_bwd(self.x_last, w.final_norm, dhidden, g.rms_eps)
+        else:
+            taps, stop = head.readout_layers, self.stop
+            if taps[-1] != stop:
+                raise RuntimeError(f"LoRA backward: the forward stopped at layer {stop}, the head's highest tap is {taps[-1]}")
+            if stop == g.layers:
+                dx = ops.rmsnorm_bwd(self.x_last, w.final_norm, head.dhidden(len(taps) - 1, self.h_last), g.rms_eps)
+            else:
+                dx = head.dhidden(len(taps) - 1, self.x_last)
+            lower = {t: i for i, t in enumerate(taps[:-1])}
+            for li in range(g.layers - 1, stop - 1, -1):
+                self._zero_layer_grads(li)
+                if self.grad_hook is not None:
+                    self.grad_hook(li)
+        self.__dict__.setdefault("_zero_layers", set()).difference_update(range(stop))
         delta = torch.empty(B, g.heads, g.max_len, dtype=torch.float32, device=self.dev)
-        for li in range(g.layers - 1, -1, -1):
+        for li in range(stop - 1, -1, -1):
             lw, sv = backbone.layer_weights(li, transposed=True, direction=-1), self.saved[li]
             sd = sv["seeds"]
             d_gu = self._group_backward(li, "down", dx, sv["hh"], sv["t_d"], sd[6:7], lw["wdown_t"], True, swiglu_gu=sv["gu"])
@@ -435,6 +487,8 @@ class LoraState:
             d_h1 = self._group_backward(li, "qkv", dqkv, sv["h1"], sv["t_qkv"], sd[0:3], lw["wqkv_t"], need_dx)
             if need_dx:
                 dx = ops.rmsnorm_bwd(sv["x"], lw["in_norm"], d_h1, g.rms_eps, dx_in=dx2)
+                if li in lower:               # H_li is tapped: its own term of the head's gradient joins the stream's
+                    head.dhidden(lower[li], sv["x"], into=dx)
             if self.grad_hook is not None:
                 self.grad_hook(li)            # data parallel: this layer's gradients are final
         self.saved = []

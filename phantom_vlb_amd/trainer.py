@@ -251,7 +251,10 @@ class Trainer:
         metrics = {"val/brain_loss": (float(tot) if tot is not None else 0.0) / max(n, 1)}
         if self._feature_cache and (rate := model.feature_cache_end("val")) is not None:
             metrics["feature_cache/val_hit_rate"] = rate
-        metrics.update({k: float(v) for k, v in getattr(model, "logged", {}).items() if k.startswith("val_corr_avg")})
+        if getattr(getattr(model, "head", None), "readout_layers", None) is not None:
+            model.log_readout_alpha()             # readout/alpha_<layer>: the learned mix over the tapped layers
+        metrics.update({k: float(v) for k, v in getattr(model, "logged", {}).items()
+                        if k.startswith("val_corr_avg") or k.startswith("readout/alpha_")})
         for c in self.callbacks:
             if hasattr(c, "on_validation_end") and isinstance(c, TrainableCheckpoint):
                 c.on_validation_end(self, model, metrics)
