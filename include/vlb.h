@@ -330,6 +330,38 @@ int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, const void* r
                              int E, int V, float eps, float l2_lambda, float loss_scale, float l2_scale, void* stream,
                              int loss_kind, const float* rowstat);
 
+/* Per-subject ridge heads on one trunk (opt-in; every entry point above keeps its bits).  LN1, the pool, LN2 and dropout
+ * are shared; ridge_w is bf16 [G*V, E] and ridge_b bf16 [G*V] (head g = rows [g*V, (g+1)*V)); group: DEVICE int32 [B],
+ * the head of clip b.  Its values MUST lie in [0, G): they cannot be checked here without a sync, the caller checks them
+ * on the host before the upload.  pred and y stay [B, V]:
+ *   pred[b,v] = W[group[b]*V + v, :] . z[b,:] + bias[group[b]*V + v],
+ *   loss_terms = {data term over the [B,V] batch as for one head, lambda * sum over ALL G heads of ||W_g||^2, their sum},
+ *   dW[g] = l2_scale*2*lambda*W[g] + sum_{b: group[b]=g} dpred[b,:]^T z[b,:],  dbias[g] = sum_{b: group[b]=g} dpred[b,:],
+ *   dz[b] = keep * sum_v dpred[b,v] W[group[b]*V + v, :],  dpred formed with the whole batch's B as the entries above do.
+ * A head without a clip in the batch gets dW[g] = the fp32 product l2_scale*2*lambda*W[g] and dbias[g] = 0 exactly.
+ * vlb_head_fwd_grouped: vlb_head_fwd_cached's arguments (gather from cache rows, LN2, dropout), then the grouped ridge and
+ *   the objective of loss_kind (VLB_LOSS_*), finished here: rowstat / loss_aux as vlb_head_loss_fwd fills them (may be NULL
+ *   for VLB_LOSS_MSE).  vlb_head_loss_fwd must not be run on its outputs.
+ * vlb_head_bwd_grouped: vlb_head_bwd_cached[_loss] for the stacked heads: d_ridge_w fp32 [G*V,E], d_ridge_b fp32 [G*V],
+ *   the four LN gradients, dz_ws and dpooled_ws (= d loss / d pooled_raw).  rowstat may be NULL for VLB_LOSS_MSE.
+ * ws: vlb_head_grouped_ws_floats(B,E,V,G) floats for both (0 for a shape the entries refuse).
+ * Limits: G >= 1 and G*V <= 2^27 rows; every element index is 64-bit, so G*V*E up to 2^27 * 8192 = 2^40 elements
+ * (16 heads of 65,536 x 4096 are 2^32).  All reductions keep a fixed order: a repeated call gives the same bits, and with
+ * G = 1 (group all zero) both entries give the bits of vlb_head_fwd_cached (+ vlb_head_loss_fwd) / vlb_head_bwd_cached[_loss]. */
+int64_t vlb_head_grouped_ws_floats(int B, int E, int V, int G);
+int vlb_head_fwd_grouped(const float* cache_pooled, const float* cache_sumw, const int32_t* rows, const void* ln1_w,
+                         const void* ln1_b, const void* ln2_w, const void* ln2_b, const void* ridge_w, const void* ridge_b,
+                         const float* y, const float* keep_scale, const int32_t* group, float* ws, float* pooled_raw,
+                         float* sumw, float* zhat, float* ln2_rstd, void* z, float* pred, float* rowstat, float* loss_terms,
+                         float* loss_aux, int B, int E, int V, int G, int n_rows, float eps, float l2_lambda, int loss_kind,
+                         void* stream);
+int vlb_head_bwd_grouped(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
+                         const int32_t* group, const float* pooled_raw, const float* sumw, const float* zhat,
+                         const float* ln2_rstd, const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b,
+                         float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws,
+                         float* dpooled_ws, const float* rowstat, int B, int E, int V, int G, float eps, float l2_lambda,
+                         float loss_scale, float l2_scale, int loss_kind, void* stream);
+
 /* Reading the head from K chosen decoder layers with a learned convex mix (opt-in; every entry point above keeps its
  * bits).  LN1's affine is per column and the pooling is linear, so the mix is taken on the pooled vectors:
  *   P_k = pooled_raw of tapped layer k (vlb_head_pool),  alpha = softmax(a),  pooled_raw = sum_k alpha_k P_k,

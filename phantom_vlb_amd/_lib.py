@@ -61,6 +61,9 @@ SIGNATURES = {
     "vlb_head_loss_fwd": [P] * 6 + [I, I, I, I, I, F, P],
     "vlb_head_bwd_loss": [P] * 24 + [I, I, I, I, F, F, F, F, P, I, P, I, P],
     "vlb_head_bwd_cached_loss": [P] * 20 + [I, I, I, F, F, F, F, P, I, P],
+    "vlb_head_grouped_ws_floats": [I, I, I, I],
+    "vlb_head_fwd_grouped": [P] * 22 + [I, I, I, I, I, F, F, I, P],
+    "vlb_head_bwd_grouped": [P] * 22 + [I, I, I, I, F, F, F, F, I, P],
     "vlb_head_pool": [P] * 6 + [I, I, I, F, P, P],
     "vlb_feature_cache_gather": [P] * 5 + [I, I, I, P],
     "vlb_head_mix_fwd": [P] * 4 + [I, I, I, P],
@@ -130,7 +133,7 @@ SIGNATURES = {
     "vlb_cast_f32_to_bf16": [P, P, L, P],
     "vlb_cast_bf16_to_f32": [P, P, L, P],
 }
-_RESTYPES = {"vlb_last_error": c_char_p, "vlb_hrf_pool_ws_floats": c_int64, "vlb_ridge_ws_floats": c_int64, "vlb_head_ws_floats": c_int64, "vlb_head_mix_ws_floats": c_int64, "vlb_wgrad_u_ws_floats": c_int64,
+_RESTYPES = {"vlb_last_error": c_char_p, "vlb_hrf_pool_ws_floats": c_int64, "vlb_ridge_ws_floats": c_int64, "vlb_head_ws_floats": c_int64, "vlb_head_mix_ws_floats": c_int64, "vlb_head_grouped_ws_floats": c_int64,"vlb_wgrad_u_ws_floats": c_int64,
              "vlb_gemm_workspace_bytes": c_int64, "vlb_reducescatter_stage_floats": c_int64, "vlb_comm_loopback_stage_bytes": c_int64,
              "vlb_norm_bwd_ws_floats": c_int64, "vlb_rmsnorm_bwd_full_ws_floats": c_int64, "vlb_colsum_ws_floats": c_int64, "vlb_dwconv3x3_bwd_w_ws_floats": c_int64}
 

@@ -1048,6 +1048,315 @@ int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, c
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
+
+// ================================================================ grouped ridge: G heads, one per subject
+// W is [G*V, E], bias [G*V]; group[b] in [0, G) names the head of clip b; pred / y stay [B, V]:
+//   pred[b, v] = W[group[b]*V + v, :] . z[b, :] + bias[group[b]*V + v].
+// Each kernel below is its ungrouped neighbour with the row index split into (head g, row v of the head) and a clip taking
+// part only in its own head's rows.  A clip's chain of additions is the one the ungrouped kernel runs on W[g] alone, the
+// blocks / tiles of head g come in the ungrouped order behind those of the heads before it, and the (sum err^2, sum W^2)
+// partials keep one pair per block: with G = 1 every output has the ungrouped bits.
+
+// scalar form: grid G * ceil(V/RIDGE_ROWS); block -> (g, RIDGE_ROWS rows of head g).  z staged in LDS as ridge_fwd_kernel.
+__global__ __launch_bounds__(256) void ridge_fwd_grouped_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
+                                                                const bf16* __restrict__ z, const float* __restrict__ y,
+                                                                const int* __restrict__ group, float* __restrict__ pred,
+                                                                float* __restrict__ lpart, int B, int E, int V, int bpg) {
+  extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
+  __shared__ float red[8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x / bpg, vb = blockIdx.x % bpg;           // head, block of rows inside the head
+  float mse = 0.f, w2 = 0.f;
+  for (int b0 = 0; b0 < B; b0 += BMAX) {
+    const int nb = min(BMAX, B - b0);
+    __syncthreads();
+    for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
+      *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
+    __syncthreads();
+    bool mine[BMAX];
+#pragma unroll
+    for (int i = 0; i < BMAX; ++i) mine[i] = i < nb && group[b0 + i] == g;
+    for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
+      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
+      if (v >= V) break;
+      const int64_t row = (int64_t)g * V + v;
+      const bf16* wr = W + row * E;
+      float acc[BMAX];
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) acc[i] = 0.f;
+#pragma unroll 4
+      for (int c = lane * 8; c < E; c += 512) {
+        float w[8]; ld8(wr + c, w);
+        if (b0 == 0) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) w2 += w[j] * w[j];
+        }
+#pragma unroll
+        for (int i = 0; i < BMAX; ++i) {
+          if (mine[i]) {
+            float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[i] += w[j] * zz[j];
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) {
+        if (mine[i]) {
+          const float pv = wave_sum(acc[i]) + (float)bias[row];
+          if (lane == 0) {
+            pred[(int64_t)(b0 + i) * V + v] = pv;
+            const float d = y ? pv - y[(int64_t)(b0 + i) * V + v] : 0.f;
+            mse += d * d;
+          }
+        }
+      }
+    }
+  }
+  w2 = wave_sum(w2);
+  if (lane == 0) { red[wave] = mse; red[4 + wave] = w2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lpart[blockIdx.x * 2] = red[0] + red[1] + red[2] + red[3];
+    lpart[blockIdx.x * 2 + 1] = red[4] + red[5] + red[6] + red[7];
+  }
+}
+
+// MFMA form (B <= 16, E % 128 == 0, E <= 4096): ridge_fwd_mfma_kernel's operand layout, unchanged (rows of the A operand =
+// 16 rows of W, columns of the B operand = clips, each wave one quarter of E with its z fragments in registers).  Persistent
+// over G * tpg row tiles, tpg = ceil(V/16): tile t is rows [16 tl, 16 tl + 16) of head g = t / tpg, tl = t % tpg - a tile
+// never spans two heads, the last tile of a head clamps its rows to the head's own last row.  All 16 clip columns are
+// contracted with every tile (no extra matrix work per head: the W stream is the cost); the epilogue keeps column b only
+// where group[b] == g.  sum W^2 counts every live row of every tile.
+template <int KSTEPS>
+__global__ __launch_bounds__(256) void ridge_fwd_grouped_mfma_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
+                                                                     const bf16* __restrict__ z, const float* __restrict__ y,
+                                                                     const int* __restrict__ group, float* __restrict__ pred,
+                                                                     float* __restrict__ lpart, int B, int E, int V, int tpg,
+                                                                     int ntiles) {
+  __shared__ float red[3][4][64];
+  __shared__ float lred[8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int kq = wave * KSTEPS * 32;                       // first column of this wave's quarter
+  // B operand: lane holds z[b = fr][kq + 32*s + 8*fq .. +8]  (zero rows for b >= B)
+  bf16x8 zf[KSTEPS];
+#pragma unroll
+  for (int s = 0; s < KSTEPS; ++s) {
+    zf[s] = bf16x8{};
+    if (fr < B) zf[s] = *reinterpret_cast<const bf16x8*>(z + (int64_t)fr * E + kq + 32 * s + 8 * fq);
+  }
+  const int myg = fr < B ? group[fr] : -1;                 // head of this lane's clip column
+  float mse = 0.f, w2 = 0.f;
+  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int g = t / tpg, tl = t % tpg;
+    const int v = min(tl * 16 + fr, V - 1);
+    const bf16* wr = W + ((int64_t)g * V + v) * E + kq + 8 * fq;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    const bool count = tl * 16 + fr < V;
+#pragma unroll
+    for (int s = 0; s < KSTEPS; ++s) {
+      const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wr + 32 * s);
+      if (count) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float f = (float)wf[j]; w2 += f * f; }
+      }
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, zf[s], acc, 0, 0, 0);
+    }
+    __syncthreads();                                       // red[] free again
+    if (wave > 0) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[wave - 1][e][lane] = acc[e];
+    }
+    __syncthreads();
+    if (wave == 0 && myg == g) {
+      // lane holds clip b = fr (of head g), rows v = tl*16 + 4*fq + e of that head
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int vv = tl * 16 + 4 * fq + e;
+        if (vv < V) {
+          const float pv = acc[e] + red[0][e][lane] + red[1][e][lane] + red[2][e][lane] + (float)bias[(int64_t)g * V + vv];
+          pred[(int64_t)fr * V + vv] = pv;
+          const float d = y ? pv - y[(int64_t)fr * V + vv] : 0.f;
+          mse += d * d;
+        }
+      }
+    }
+  }
+  mse = wave_sum(mse);
+  w2 = wave_sum(w2);
+  if (lane == 0) { lred[wave] = mse; lred[4 + wave] = w2; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    lpart[blockIdx.x * 2] = lred[0] + lred[1] + lred[2] + lred[3];
+    lpart[blockIdx.x * 2 + 1] = lred[4] + lred[5] + lred[6] + lred[7];
+  }
+}
+
+// d pred of clip b at row v of ITS head (both objectives); the other heads' rows see 0 for this clip.
+template <bool CORR>
+__device__ __forceinline__ float dpred_own(const float* __restrict__ pred, const float* __restrict__ y, int b, int v, int V,
+                                           float gscale, const float* __restrict__ coef) {
+  if constexpr (CORR) return dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]);
+  else return gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]);
+}
+
+// d pred^T over all G*V rows as the skinny-wgrad G operand: dpT[g*V + v, b] = d pred[b, v] where group[b] == g, else 0
+template <bool CORR>
+__global__ void dpred_t_grouped_kernel(const float* __restrict__ pred, const float* __restrict__ y, const int* __restrict__ group,
+                                       bf16* __restrict__ dpT, int B, int V, int64_t GV, float gscale,
+                                       const float* __restrict__ coef) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= GV * 16) return;
+  const int64_t row = i >> 4;
+  const int b = (int)(i & 15), g = (int)(row / V), v = (int)(row % V);
+  dpT[i] = (bf16)(b < B && group[b] == g ? dpred_own<CORR>(pred, y, b, v, V, gscale, coef) : 0.f);
+}
+
+// dW, dbias: grid G * ceil(V/RIDGE_ROWS), one row of dW per (g, v).  A clip of another head adds nothing to the row: it is
+// skipped, so a head without a clip gets the fp32 product l2coef * W and dbias = 0 exactly.
+template <bool CORR>
+__global__ __launch_bounds__(256) void ridge_bwd_w_grouped_kernel(const bf16* __restrict__ W, const bf16* __restrict__ z,
+                                                                  const float* __restrict__ pred, const float* __restrict__ y,
+                                                                  const int* __restrict__ group, float* __restrict__ dW,
+                                                                  float* __restrict__ dbias, int B, int E, int V, int bpg,
+                                                                  float gscale, float l2coef, const float* __restrict__ coef) {
+  extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x / bpg, vb = blockIdx.x % bpg;
+  for (int b0 = 0; b0 < B; b0 += BMAX) {
+    const int nb = min(BMAX, B - b0);
+    __syncthreads();
+    for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
+      *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
+    __syncthreads();
+    bool mine[BMAX];
+#pragma unroll
+    for (int i = 0; i < BMAX; ++i) mine[i] = i < nb && group[b0 + i] == g;
+    for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
+      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
+      if (v >= V) break;
+      const int64_t row = (int64_t)g * V + v;
+      float dp[BMAX];
+      float db = 0.f;
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) {
+        dp[i] = mine[i] ? dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef) : 0.f;
+        db += dp[i];
+      }
+      if (lane == 0) dbias[row] = (b0 == 0 ? 0.f : dbias[row]) + db;
+      const bf16* wr = W + row * E;
+#pragma unroll 4
+      for (int c = lane * 8; c < E; c += 512) {
+        float gr[8];
+        float* o = dW + row * E + c;
+        if (b0 == 0) {
+          float w[8]; ld8(wr + c, w);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) gr[j] = l2coef * w[j];
+        } else {
+          const f32x4 lo = *reinterpret_cast<const f32x4*>(o), hi = *reinterpret_cast<const f32x4*>(o + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) { gr[j] = lo[j]; gr[4 + j] = hi[j]; }
+        }
+#pragma unroll
+        for (int i = 0; i < BMAX; ++i) {
+          if (mine[i]) {
+            float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) gr[j] += dp[i] * zz[j];
+          }
+        }
+        *reinterpret_cast<f32x4*>(o) = f32x4{gr[0], gr[1], gr[2], gr[3]};
+        *reinterpret_cast<f32x4*>(o + 4) = f32x4{gr[4], gr[5], gr[6], gr[7]};
+      }
+    }
+  }
+}
+
+// dz partials over V splits (B > 16): ridge_bwd_z_kernel with the rows of every head walked in turn, heads ascending; clip b
+// accumulates only over the rows of head group[b], in the ungrouped order.  grid (ceil(E/512), DZ_SPLIT).
+template <bool CORR>
+__global__ __launch_bounds__(256) void ridge_bwd_z_grouped_kernel(const bf16* __restrict__ W, const float* __restrict__ pred,
+                                                                  const float* __restrict__ y, const int* __restrict__ group,
+                                                                  float* __restrict__ part, int B, int E, int V, int G,
+                                                                  float gscale, const float* __restrict__ coef) {
+  __shared__ float red[3][BMAX][512];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 512 + lane * 8;
+  const int per = (V + DZ_SPLIT - 1) / DZ_SPLIT;
+  const int v0 = blockIdx.y * per, v1 = min(V, v0 + per);
+  for (int b0 = 0; b0 < B; b0 += BMAX) {
+    const int nb = min(BMAX, B - b0);
+    int gi[BMAX];
+#pragma unroll
+    for (int i = 0; i < BMAX; ++i) gi[i] = i < nb ? group[b0 + i] : -1;
+    float acc[BMAX][8];
+#pragma unroll
+    for (int i = 0; i < BMAX; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+    if (c < E) {
+      for (int g = 0; g < G; ++g) {
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < BMAX; ++i) any = any || gi[i] == g;
+        if (!any) continue;                                  // no clip of this pass reads head g: skip its rows
+        for (int v = v0 + wave; v < v1; v += 4) {
+          float w[8]; ld8(W + ((int64_t)g * V + v) * E + c, w);
+#pragma unroll
+          for (int i = 0; i < BMAX; ++i) {
+            if (gi[i] == g) {
+              const float dp = dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef);
+#pragma unroll
+              for (int j = 0; j < 8; ++j) acc[i][j] += dp * w[j];
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (wave > 0) {
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[wave - 1][i][lane * 8 + j] = acc[i][j];
+    }
+    __syncthreads();
+    if (wave == 0 && c < E) {
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) {
+        if (i < nb) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            part[((int64_t)blockIdx.y * B + b0 + i) * E + c + j] =
+                acc[i][j] + red[0][i][lane * 8 + j] + red[1][i][lane * 8 + j] + red[2][i][lane * 8 + j];
+        }
+      }
+    }
+  }
+}
+
+int reserve_grouped_lds(int bytes) {
+  static int reserved = 0;
+  if (bytes > reserved) {
+    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_fwd_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_grouped_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e2 == hipSuccess)
+      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_grouped_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e1 != hipSuccess || e2 != hipSuccess) { vlb_set_error("head: cannot reserve %d bytes of LDS for z", bytes); return VLB_ERR_LAUNCH; }
+    reserved = bytes;
+  }
+  return VLB_OK;
+}
+
+// the grouped planner: which forward form, how many (sum err^2, sum W^2) pairs it leaves, which dz form
+constexpr int64_t GROUPED_MAX_ROWS = (int64_t)1 << 27;      // G*V: 16 bf16 per row of d pred^T and every tile count fit an int
+int grouped_fwd_parts(int B, int E, int V, int G) {
+  const bool mfma = B <= 16 && E % 128 == 0 && E <= 4096;
+  const int64_t ntiles = (int64_t)G * ((V + 15) / 16);
+  return mfma ? (int)(ntiles < 2048 ? ntiles : 2048) : G * ((V + RIDGE_ROWS - 1) / RIDGE_ROWS);
+}
 }  // namespace
 
 extern "C" int vlb_head_partial_rows(int S) { return (S + POOL_ROWS - 1) / POOL_ROWS; }
@@ -1212,6 +1521,139 @@ extern "C" int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, co
   return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
                          d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
                          stream, loss_kind, rowstat);
+}
+
+// ---------------------------------------------------------------- per-subject ridge heads on one trunk: the grouped tail
+extern "C" int64_t vlb_head_grouped_ws_floats(int B, int E, int V, int G) {
+  if (B <= 0 || E <= 0 || V <= 0 || G <= 0 || (int64_t)G * V > GROUPED_MAX_ROWS) return 0;
+  const int64_t fwd = 2 * (int64_t)G * ((V + 15) / 16);                  // >= 2 * grouped_fwd_parts, either form
+  const int64_t bwd = head_bwd_ws_floats(B, E, G * V) + 4 * (int64_t)B;  // + coef[B][4] of the correlation objectives
+  return bwd > fwd ? bwd : fwd;
+}
+
+extern "C" int vlb_head_fwd_grouped(const float* cache_pooled, const float* cache_sumw, const int* rows, const void* ln1_w,
+                                    const void* ln1_b, const void* ln2_w, const void* ln2_b, const void* ridge_w,
+                                    const void* ridge_b, const float* y, const float* keep_scale, const int* group, float* ws,
+                                    float* pooled_raw, float* sumw, float* zhat, float* ln2_rstd, void* z, float* pred,
+                                    float* rowstat, float* loss_terms, float* loss_aux, int B, int E, int V, int G, int n_rows,
+                                    float eps, float l2_lambda, int loss_kind, void* stream) {
+  VLB_REQUIRE(cache_pooled && cache_sumw && rows && ln1_w && ln1_b && ln2_w && ln2_b && ridge_w && ridge_b && y && group && ws &&
+                  pooled_raw && sumw && zhat && ln2_rstd && z && pred && loss_terms, "head_fwd_grouped: null argument");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON,
+              "head_fwd_grouped: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || (rowstat && loss_aux), "head_fwd_grouped: loss_kind %d needs rowstat and loss_aux", loss_kind);
+  VLB_REQUIRE(B > 0 && V > 0 && G >= 1 && n_rows > 0 && E % 8 == 0 && E > 0 && E <= 8192,
+              "head_fwd_grouped: bad shape B=%d E=%d V=%d G=%d n_rows=%d", B, E, V, G, n_rows);
+  VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_fwd_grouped: G*V = %lld rows, at most 2^27", (long long)G * V);
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_fwd_grouped: pearson needs V >= 2 (V=%d)", V);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
+                     pooled_raw, sumw, E, n_rows);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
+                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
+  VLB_LAUNCH_CHECK();
+  float* lpart = ws;
+  const int parts = grouped_fwd_parts(B, E, V, G);
+  if (B <= 16 && E % 128 == 0 && E <= 4096) {
+    const int tpg = (V + 15) / 16, ntiles = G * tpg;       // persistent over row tiles: parts = min(ntiles, 2048) blocks
+    switch (E / 128) {
+#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL(ridge_fwd_grouped_mfma_kernel<KS>, dim3(parts), dim3(256), 0, st, \
+                                                       (const bf16*)ridge_w, (const bf16*)ridge_b, (const bf16*)z, y, group, pred, lpart, \
+                                                       B, E, V, tpg, ntiles); break;
+      VLB_RIDGE_CASE(1) VLB_RIDGE_CASE(2) VLB_RIDGE_CASE(3) VLB_RIDGE_CASE(4) VLB_RIDGE_CASE(5) VLB_RIDGE_CASE(6) VLB_RIDGE_CASE(7)
+      VLB_RIDGE_CASE(8) VLB_RIDGE_CASE(9) VLB_RIDGE_CASE(10) VLB_RIDGE_CASE(11) VLB_RIDGE_CASE(12) VLB_RIDGE_CASE(13)
+      VLB_RIDGE_CASE(14) VLB_RIDGE_CASE(15) VLB_RIDGE_CASE(16) VLB_RIDGE_CASE(17) VLB_RIDGE_CASE(18) VLB_RIDGE_CASE(19)
+      VLB_RIDGE_CASE(20) VLB_RIDGE_CASE(21) VLB_RIDGE_CASE(22) VLB_RIDGE_CASE(23) VLB_RIDGE_CASE(24) VLB_RIDGE_CASE(25)
+      VLB_RIDGE_CASE(26) VLB_RIDGE_CASE(27) VLB_RIDGE_CASE(28) VLB_RIDGE_CASE(29) VLB_RIDGE_CASE(30) VLB_RIDGE_CASE(31)
+      VLB_RIDGE_CASE(32)
+#undef VLB_RIDGE_CASE
+    }
+  } else {
+    const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+    const int zlds = (B < BMAX ? B : BMAX) * E * 2;
+    if (int rc2 = reserve_grouped_lds(zlds)) return rc2;
+    hipLaunchKernelGGL(ridge_fwd_grouped_kernel, dim3(parts), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b,
+                       (const bf16*)z, y, group, pred, lpart, B, E, V, bpg);
+  }
+  VLB_LAUNCH_CHECK();
+  const float inv_bv = 1.f / ((float)B * (float)V);
+  if (loss_kind == VLB_LOSS_MSE) {
+    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, parts, inv_bv, l2_lambda, loss_terms);
+  } else {
+    if (loss_kind == VLB_LOSS_PEARSON) hipLaunchKernelGGL(head_rowstat_kernel<true>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+    else hipLaunchKernelGGL(head_rowstat_kernel<false>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loss_finalize_corr_kernel, dim3(1), dim3(256), 0, st, lpart, parts, inv_bv, l2_lambda, rowstat, B,
+                       loss_terms, loss_aux);
+  }
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_bwd_grouped(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
+                                    const float* keep_scale, const int* group, const float* pooled_raw, const float* sumw,
+                                    const float* zhat, const float* ln2_rstd, const void* z, const float* pred, float* d_ridge_w,
+                                    float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws,
+                                    float* dz_ws, float* dpooled_ws, const float* rowstat, int B, int E, int V, int G, float eps,
+                                    float l2_lambda, float loss_scale, float l2_scale, int loss_kind, void* stream) {
+  (void)eps;
+  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && group && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w &&
+                  d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
+              "head_bwd_grouped: null argument");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON,
+              "head_bwd_grouped: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || rowstat, "head_bwd_grouped: loss_kind %d needs rowstat", loss_kind);
+  VLB_REQUIRE(B > 0 && V > 0 && G >= 1 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_grouped: bad shape B=%d E=%d V=%d G=%d", B, E, V, G);
+  VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_bwd_grouped: G*V = %lld rows, at most 2^27", (long long)G * V);
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_grouped: pearson needs V >= 2 (V=%d)", V);
+  hipStream_t st = as_stream(stream);
+  const int GV = G * V;
+  const float gscale = loss_scale * 2.f / ((float)B * (float)V);      // B: the whole batch, whatever the heads' shares
+  const float l2coef = l2_scale * 2.f * l2_lambda;
+  const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+  const int zlds = (B < BMAX ? B : BMAX) * E * 2;
+  if (int rc2 = reserve_grouped_lds(zlds)) return rc2;
+  float* coef = ws + head_bwd_ws_floats(B, E, GV);
+  const bool corr = loss_kind != VLB_LOSS_MSE;
+  if (corr) {
+    hipLaunchKernelGGL(head_loss_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rowstat, coef, B, loss_scale);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ridge_bwd_w_grouped_kernel<true>, dim3(G * bpg), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z,
+                       pred, y, group, d_ridge_w, d_ridge_b, B, E, V, bpg, gscale, l2coef, coef);
+  } else {
+    hipLaunchKernelGGL(ridge_bwd_w_grouped_kernel<false>, dim3(G * bpg), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z,
+                       pred, y, group, d_ridge_w, d_ridge_b, B, E, V, bpg, gscale, l2coef, coef);
+  }
+  VLB_LAUNCH_CHECK();
+  if (B <= 16 && E % 8 == 0) {
+    // dz[b,e] = sum_{(g,v)} dpT[g*V+v, b] W[g*V+v, e]: one skinny-wgrad contraction over all G*V rows (zeros off the clip's head)
+    const int splits = vlb_wgrad_splits(GV);
+    float* wg_ws = ws;                                             // [splits][16][E]
+    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
+    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [G*V][16] bf16
+    const dim3 tgrid((unsigned)(((int64_t)GV * 16 + 255) / 256));
+    if (corr) hipLaunchKernelGGL(dpred_t_grouped_kernel<true>, tgrid, dim3(256), 0, st, pred, y, group, dpT, B, V, (int64_t)GV, gscale, coef);
+    else hipLaunchKernelGGL(dpred_t_grouped_kernel<false>, tgrid, dim3(256), 0, st, pred, y, group, dpT, B, V, (int64_t)GV, gscale, coef);
+    VLB_LAUNCH_CHECK();
+    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, GV, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
+    if (rc3 != VLB_OK) return rc3;
+    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
+    VLB_LAUNCH_CHECK();
+  } else {
+    const dim3 zgrid((E + 511) / 512, DZ_SPLIT);
+    if (corr) hipLaunchKernelGGL(ridge_bwd_z_grouped_kernel<true>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, group, ws, B, E, V, G, gscale, coef);
+    else hipLaunchKernelGGL(ridge_bwd_z_grouped_kernel<false>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, group, ws, B, E, V, G, gscale, coef);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
+    VLB_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(head_ln2_bwd_kernel, dim3(B), dim3(1024), 0, st, dz_ws, (const bf16*)ln2_w, zhat, ln2_rstd, dpooled_ws, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(head_param_grads_kernel, dim3((E + 255) / 256), dim3(256), 0, st, dz_ws, dpooled_ws, (const bf16*)ln1_w,
+                     pooled_raw, sumw, zhat, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, B, E);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
 }
 
 // ---------------------------------------------------------------- readout from chosen layers: pool, mix, d hidden on their own

@@ -57,6 +57,18 @@ class VLBDataModuleConfig:
     # extras
     geometry: str = "7b"
     num_target: int = 1000
+    # two or more subject names: ``lazyload_path`` holds the literal ``{subject}`` and is expanded per subject (``synthetic:NxM``:
+    # N files per subject), the subjects' datasets are concatenated in this order and every item carries "subject", its index
+    # into this list (litmodule.config.subjects must be the same list).  None: one subject, ``subject``, as the reference
+    subjects: list | None = None
+
+    def __post_init__(self):
+        from .head import check_subjects
+        if self.subjects is not None:
+            self.subjects = list(check_subjects(self.subjects))
+            if not self.lazyload_path.startswith("synthetic:") and "{subject}" not in self.lazyload_path:
+                raise ValueError(f"subjects={self.subjects!r} needs the literal {{subject}} in lazyload_path (it is expanded per "
+                                 f"subject); got {self.lazyload_path!r}")
 
 
 def open_h5(path):
@@ -106,10 +118,14 @@ class _SyntheticFile:
 class VLB_Dataset(Dataset):
     """``with_index`` adds the dataset index (``"index"``, int64) to every item; ``features_only`` makes an item
     ``{"index", "timeseries"}`` and reads nothing else from the file (a split whose frozen-backbone features are all
-    cached, feature_cache.py).  Both are off by default and may be switched between epochs."""
+    cached, feature_cache.py).  Both are off by default and may be switched between epochs.  ``subject_of`` (one index per
+    file, multi-subject runs) adds ``"subject"`` (int64) to every item, also under ``features_only``."""
 
-    def __init__(self, ds_paths, geometry="7b", num_target=1000):
+    def __init__(self, ds_paths, geometry="7b", num_target=1000, subject_of=None):
         self.ds_paths, self.geometry, self.num_target = list(ds_paths), geometry, num_target
+        self.subject_of = None if subject_of is None else [int(g) for g in subject_of]
+        if self.subject_of is not None and len(self.subject_of) != len(self.ds_paths):
+            raise ValueError(f"subject_of names {len(self.subject_of)} files, ds_paths {len(self.ds_paths)}")
         self.with_index = self.features_only = False
         self.ds_files, self.length, self.ranges = {}, 0, []
         for i, p in enumerate(ds_paths):
@@ -130,13 +146,15 @@ class VLB_Dataset(Dataset):
         i = get_idx(self.ranges, idx)
         f = self.ds_files[i]["ds_file"]
         k = idx - self.ds_files[i]["idx_from"]
+        subject = {} if self.subject_of is None else {"subject": torch.tensor(self.subject_of[i], dtype=torch.int64)}
         if self.features_only:
             return {"index": torch.tensor(int(idx), dtype=torch.int64),
-                    "timeseries": torch.from_numpy(np.asarray(f.get(k, "timeseries"))).float()}
+                    "timeseries": torch.from_numpy(np.asarray(f.get(k, "timeseries"))).float(), **subject}
         item = {m: torch.from_numpy(np.asarray(f.get(k, m))).float() for m in MODS_T}
         item.update({m: np.asarray(f.get(k, m)) for m in MODS_N})
         if self.with_index:
             item["index"] = torch.tensor(int(idx), dtype=torch.int64)
+        item.update(subject)
         return item
 
 
@@ -147,27 +165,45 @@ class VLBDatasets:
     val: VLB_Dataset | None = None
     test: VLB_Dataset | None = None
 
-    def __post_init__(self):
+    SUBJECT_SEED_STRIDE = 1009       # synthetic files of subject g: seeds random_state + k + 1009 g (subject 0: the single-subject run's)
+
+    def _split(self, lazyload_path, seed_offset=0):
+        """One subject's file list, split as the reference does -> (val files, train files, their names as ``dset_names``)"""
         c = self.config
-        if c.lazyload_path.startswith("synthetic:"):
-            n_files, n_samples = (int(x) for x in c.lazyload_path.split(":", 1)[1].split("x"))
-            f_list = [(c.random_state + k, n_samples) for k in range(n_files)]
+        if lazyload_path.startswith("synthetic:"):
+            n_files, n_samples = (int(x) for x in lazyload_path.split(":", 1)[1].split("x"))
+            f_list = [(c.random_state + k + seed_offset, n_samples) for k in range(n_files)]
             names = [f"synthetic_{k}" for k in range(n_files)]
         else:
             f_list = []
             for s in c.seasons:
                 f_list += sorted(glob.glob(
-                    c.lazyload_path.replace("$SCRATCH_PATH", os.environ.get("SCRATCH_PATH", ".")).replace("s*", f"{s}")))
+                    lazyload_path.replace("$SCRATCH_PATH", os.environ.get("SCRATCH_PATH", ".")).replace("s*", f"{s}")))
             names = [os.path.basename(x) for x in f_list]
         if not f_list:
-            raise FileNotFoundError(f"no lazy-load files match {c.lazyload_path!r}")
+            raise FileNotFoundError(f"no lazy-load files match {lazyload_path!r}")
         r = np.random.RandomState(c.random_state)
         vi = int(r.choice(len(f_list), 1)[0])
         val_file = [f_list[vi]]
         train_files = [x for x in f_list if x != f_list[vi]]
-        self.dset_names = {"val_set": [names[vi]], "train_set": [n for n, x in zip(names, f_list) if x != f_list[vi]]}
-        self.val = VLB_Dataset(val_file, c.geometry, c.num_target)
-        self.train = VLB_Dataset(train_files, c.geometry, c.num_target)
+        return val_file, train_files, {"val_set": [names[vi]], "train_set": [n for n, x in zip(names, f_list) if x != f_list[vi]]}
+
+    def __post_init__(self):
+        c = self.config
+        subjects = getattr(c, "subjects", None)
+        if subjects is None:
+            val_file, train_files, self.dset_names = self._split(c.lazyload_path)
+            self.val = VLB_Dataset(val_file, c.geometry, c.num_target)
+            self.train = VLB_Dataset(train_files, c.geometry, c.num_target)
+            return
+        # one list and one split (one validation file, drawn with RandomState(random_state)) per subject, concatenated in order
+        val, train, val_of, train_of, self.dset_names = [], [], [], [], {}
+        for g, name in enumerate(subjects):
+            v, t, self.dset_names[name] = self._split(c.lazyload_path.replace("{subject}", name), self.SUBJECT_SEED_STRIDE * g)
+            val, train = val + v, train + t
+            val_of, train_of = val_of + [g] * len(v), train_of + [g] * len(t)
+        self.val = VLB_Dataset(val, c.geometry, c.num_target, subject_of=val_of)
+        self.train = VLB_Dataset(train, c.geometry, c.num_target, subject_of=train_of)
 
 
 class VLBDataModule(_Base):
@@ -202,10 +238,11 @@ class DevicePrefetcher:
     pixels per clip) are copied host->device on a side stream while step i computes, and are
     handed over with an event, so the step never waits on PCIe.  The token ids and ``padvals`` stay on the
     host: the step sizes its unpadded row layout from them without a device sync (they are tiny and are
-    uploaded by the step itself).  Device tensors are tied to the consumer stream with ``record_stream`` so
+    uploaded by the step itself); so does a multi-subject batch's ``subject`` index, which the head checks on the
+    host.  Device tensors are tied to the consumer stream with ``record_stream`` so
     the caching allocator cannot recycle them while a kernel still reads them."""
 
-    def __init__(self, loader, device, keep_on_host=("language", "padvals"), on_staged=None, on_discard=None):
+    def __init__(self, loader, device, keep_on_host=("language", "padvals", "subject"), on_staged=None, on_discard=None):
         """``on_staged(batch, event)``: called for every batch right after its copies were enqueued (event = copies done),
         i.e. one step before the batch is handed over - VLBLitModule.prefetch_vision hooks in here.
         ``on_discard(batch)``: called for a batch that was staged but will never be handed over (the consumer stopped

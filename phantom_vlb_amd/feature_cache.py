@@ -81,6 +81,9 @@ def fingerprint(cfg, dataset, lib_path: str | None = None) -> str:
     taps = getattr(cfg, "readout_layers", None)
     if taps is not None:                  # only when set: fingerprints (and caches) from before the option stay valid
         doc["readout_layers"] = [int(k) for k in check_readout_layers(taps, g["layers"])]
+    subjects = getattr(cfg, "subjects", None)
+    if subjects is not None:              # likewise: which subject a dataset index belongs to depends on the list and its order
+        doc["subjects"] = [str(s) for s in subjects]
     return hashlib.sha256(json.dumps(doc, sort_keys=True).encode()).hexdigest()
 
 

@@ -7,6 +7,9 @@ src/utils.py:40-73) but runs as the fused vlb_head_fwd / vlb_head_bwd kernels.
 Opt-in, ``readout_layers``: the head reads K chosen decoder layers instead of the last one - each is pooled on its own
 (vlb_head_pool), the pooled vectors are mixed by softmax(``layer_mix.weight``) (vlb_head_mix_fwd / _bwd) and the rest of the
 head runs on the mix; see ``begin`` / ``tap`` / ``forward_tapped`` / ``backward_tapped`` / ``dhidden`` and DESIGN §5.3.3.
+Opt-in, ``subjects``: one ridge head per subject on the shared trunk (``ridge_layer.linear.weight`` [G,V,E]); each clip is
+regressed by its own subject's head, the penalty covers all heads (vlb_head_fwd_grouped / vlb_head_bwd_grouped in place of
+the tail; ``forward`` / ``forward_cached`` / ``forward_tapped`` take ``subject``); see DESIGN §5.3.4.
 Trainable parameters keep an fp32 master (what AdamW updates) and the bf16 copy the kernels read -
 the reference stores them in bf16 (``dtype=self.config.dtype``), i.e. the kernels see the same values.
 """
@@ -32,6 +35,22 @@ def check_loss(loss, num_target):
         raise ValueError(f"loss={loss!r}: expected one of {sorted(LOSS_KINDS)}")
     if loss == "pearson" and num_target < 2:
         raise ValueError(f"loss='pearson' needs num_target >= 2 (got {num_target}): one target has no spread to correlate")
+
+
+def check_subjects(subjects):
+    """``subjects`` as the head, the module and the datamodule take it: None (one head, keyed by the config's ``subject``), or
+    a list of two or more distinct subject names -> a tuple."""
+    if subjects is None:
+        return None
+    if isinstance(subjects, (str, bytes)) or not hasattr(subjects, "__iter__"):
+        raise ValueError(f"subjects={subjects!r}: a list of subject names is needed (one subject: leave it unset, use `subject`)")
+    out = tuple(str(s) for s in subjects)
+    if len(out) < 2:
+        raise ValueError(f"subjects={list(out)!r}: two or more subjects are needed; a single subject is `subject=...` with "
+                         "`subjects` unset")
+    if len(set(out)) != len(out):
+        raise ValueError(f"subjects={list(out)!r}: a subject is named twice")
+    return out
 
 
 LAYER_MIX = "layer_mix.weight"       # logits of the learned mix over the tapped layers (K > 1 only), fp32 master [K]
@@ -74,8 +93,11 @@ def check_readout_layers(layers, num_layers: int | None = None):
 
 class BrainHead:
     def __init__(self, dim: int, num_target: int, l2_lambda: float, eps: float, device, sd: dict | None = None,
-                 seed: int = 1234, loss: str = "mse", readout_layers=None):
+                 seed: int = 1234, loss: str = "mse", readout_layers=None, subjects=None):
         check_loss(loss, num_target)
+        # per-subject ridge heads on the shared trunk; G = 0: one head, the code path as ever
+        self.subjects = check_subjects(subjects)
+        self.G = 0 if self.subjects is None else len(self.subjects)
         self.loss, self.loss_kind = loss, LOSS_KINDS[loss]
         self.E, self.V, self.l2_lambda, self.eps, self.dev = dim, num_target, float(l2_lambda), float(eps), device
         # taps (normalised by the caller: check_readout_layers with L); K = 0: the fused path on one hidden tensor, as ever
@@ -95,6 +117,13 @@ class BrainHead:
                 "ridge_layer.linear.weight": (torch.rand(num_target, dim, generator=gen) * 2 - 1) * bound,
                 "ridge_layer.linear.bias": (torch.rand(num_target, generator=gen) * 2 - 1) * bound,
             }
+            if self.G:      # head 0 as a single head of this seed draws it, head g from seed + g; stacked [G,V,E] / [G,V]
+                ws_, bs_ = [sd["ridge_layer.linear.weight"]], [sd["ridge_layer.linear.bias"]]
+                for g in range(1, self.G):
+                    gg = torch.Generator(device="cpu").manual_seed(seed + g)
+                    ws_.append((torch.rand(num_target, dim, generator=gg) * 2 - 1) * bound)
+                    bs_.append((torch.rand(num_target, generator=gg) * 2 - 1) * bound)
+                sd["ridge_layer.linear.weight"], sd["ridge_layer.linear.bias"] = torch.stack(ws_), torch.stack(bs_)
             # the reference creates these modules in bf16 (dtype=self.config.dtype): start from bf16-representable values
             sd = {n: t.to(BF16).float() for n, t in sd.items()}
         for n in self.param_names:
@@ -107,6 +136,12 @@ class BrainHead:
         if self.K > 1 and tuple(self.master[LAYER_MIX].shape) != (self.K,):
             raise ValueError(f"{LAYER_MIX}: {tuple(self.master[LAYER_MIX].shape)} handed in, readout_layers="
                              f"{list(self.readout_layers)} needs ({self.K},)")
+        want = {"ridge_layer.linear.weight": (self.G, num_target, dim) if self.G else (num_target, dim),
+                "ridge_layer.linear.bias": (self.G, num_target) if self.G else (num_target,)}
+        for n, shape in want.items():
+            if tuple(self.master[n].shape) != shape:
+                raise ValueError(f"{n}: {tuple(self.master[n].shape)} handed in, "
+                                 f"subjects={None if self.subjects is None else list(self.subjects)!r} needs {shape}")
         self.compute = {n: t.to(BF16) for n, t in self.master.items()}
         self.grads = {n: torch.zeros_like(t) for n, t in self.master.items()}
         self._cap = None
@@ -130,12 +165,85 @@ class BrainHead:
             self.loss_aux = torch.zeros(2, dtype=f32, device=d)
             self.dz = torch.empty(B, E, dtype=f32, device=d)
             self.dpooled = torch.empty(B, E, dtype=f32, device=d)
+            if self.G:
+                self.gws = torch.empty(max(1, lib.vlb_head_grouped_ws_floats(B, E, V, self.G)), dtype=f32, device=d)
+                self.pool_src = torch.empty(B, E, dtype=f32, device=d)       # vlb_head_pool's output, the grouped tail's "cache"
+                self.pool_sumw = torch.empty(B, dtype=f32, device=d)
+                self.rows_id = torch.arange(B, dtype=torch.int32, device=d)
             self._cap = key
 
-    def forward(self, hidden, wmask, y, keep_scale=None, layout=None):
+    # ------------------------------------------------------------------ per-subject heads (subjects=[...]): the grouped tail
+    def _group(self, subject, B):
+        """``subject`` (host ints or a CPU tensor, one head index per clip) checked on the host -> device int32 [B];
+        None for a single head.  Nothing is launched before this has passed."""
+        if not self.G:
+            if subject is not None:
+                raise ValueError("head: `subject` given to a head built without `subjects` (one ridge head)")
+            return None
+        if subject is None:
+            raise ValueError(f"head: built with subjects={list(self.subjects)!r}: every call needs `subject`, one index per clip")
+        idx = torch.as_tensor(subject).detach().cpu().flatten()
+        if idx.numel() != B or idx.is_floating_point() or idx.dtype == torch.bool:
+            raise ValueError(f"head: subject has {idx.numel()} entries of {idx.dtype} for a batch of {B}: one integer index per clip")
+        idx = idx.to(torch.int64)
+        if int(idx.min()) < 0 or int(idx.max()) >= self.G:
+            raise ValueError(f"head: subject={idx.tolist()!r} has an index outside [0, {self.G}) (subjects={list(self.subjects)!r})")
+        return idx.to(torch.int32).to(self.dev)
+
+    def _fwd_grouped(self, src_pooled, src_sumw, rows, n_rows, y, keep_scale, group):
+        """vlb_head_fwd_grouped on (src rows -> pooled_raw, sumw): LN2, dropout, grouped ridge, the objective."""
+        B = y.shape[0]
+        self._saved_cached = (y, keep_scale)
+        self._saved_group = group
+        c = self.compute
+        check(lib.vlb_head_fwd_grouped(src_pooled.data_ptr(), src_sumw.data_ptr(), rows.data_ptr(),
+                                       c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
+                                       c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
+                                       c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
+                                       y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), group.data_ptr(),
+                                       self.gws.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
+                                       self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
+                                       self.rowstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, self.E,
+                                       self.V, self.G, n_rows, self.eps, self.l2_lambda, self.loss_kind, _stream()),
+              "vlb_head_fwd_grouped")
+        return self.pred, self.loss_terms
+
+    def _bwd_grouped(self, loss_scale, l2_scale):
+        y, keep_scale = self._saved_cached
+        B = y.shape[0]
+        c, gr = self.compute, self.grads
+        check(lib.vlb_head_bwd_grouped(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                                       c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(),
+                                       None if keep_scale is None else keep_scale.data_ptr(), self._saved_group.data_ptr(),
+                                       self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
+                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
+                                       gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
+                                       gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
+                                       gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(),
+                                       self.gws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(), self.rowstat.data_ptr(),
+                                       B, self.E, self.V, self.G, self.eps, self.l2_lambda, float(loss_scale), float(l2_scale),
+                                       self.loss_kind, _stream()), "vlb_head_bwd_grouped")
+
+    def subject_state_dict(self, name_or_index):
+        """One subject's head in the reference's shapes ([V,E], [V], the shared LN tensors; fp32 masters): what a
+        per-subject reference module loads."""
+        if not self.G:
+            raise ValueError("head: subject_state_dict() needs a head built with `subjects`")
+        g = name_or_index
+        if isinstance(g, str):
+            if g not in self.subjects:
+                raise ValueError(f"head: subject {g!r} is not one of {list(self.subjects)!r}")
+            g = self.subjects.index(g)
+        if isinstance(g, bool) or not isinstance(g, int) or not 0 <= g < self.G:
+            raise ValueError(f"head: subject index {name_or_index!r} outside [0, {self.G})")
+        return {n: (t[g] if n.startswith("ridge_layer.") else t).detach().clone() for n, t in self.master.items()}
+
+    def forward(self, hidden, wmask, y, keep_scale=None, layout=None, subject=None):
         """hidden bf16 [B*S,E] (or [B,S,E]; packed rows with a packed ``layout``), wmask f32 [B,S] (always
-        dense), y f32 [B,V] -> (pred f32 [B,V], loss_terms f32[3])."""
+        dense), y f32 [B,V] -> (pred f32 [B,V], loss_terms f32[3]).  ``subject``: the head index of every clip, for a head
+        built with ``subjects`` (then: vlb_head_pool, the grouped tail on identity rows; backward adds vlb_head_dhidden)."""
         B, S = wmask.shape
+        group = self._group(subject, B)
         packed = layout is not None and layout.packed
         rows = layout.rows if packed else B * S
         if hidden.numel() != rows * self.E or (packed and (layout.B, layout.S) != (B, S)):
@@ -144,6 +252,11 @@ class BrainHead:
         self._buffers(B, S)
         self._saved = (hidden, wmask, y, keep_scale, cu, rows)
         c = self.compute
+        if group is not None:
+            check(lib.vlb_head_pool(hidden.data_ptr(), wmask.data_ptr(), self.ws.data_ptr(), self.stats.data_ptr(),
+                                    self.pool_src.data_ptr(), self.pool_sumw.data_ptr(), B, S, self.E, self.eps,
+                                    None if cu is None else cu.data_ptr(), _stream()), "vlb_head_pool")
+            return self._fwd_grouped(self.pool_src, self.pool_sumw, self.rows_id, B, y, keep_scale, group)
         check(lib.vlb_head_fwd(hidden.data_ptr(), wmask.data_ptr(), c["layer_norm1.weight"].data_ptr(),
                                c["layer_norm1.bias"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
                                c["layer_norm2.bias"].data_ptr(), c["ridge_layer.linear.weight"].data_ptr(),
@@ -170,6 +283,13 @@ class BrainHead:
         B, S = wmask.shape
         c, gr = self.compute, self.grads
         dh = torch.empty(rows, self.E, dtype=BF16, device=self.dev) if need_dhidden else None
+        if self.G:
+            self._bwd_grouped(loss_scale, l2_scale)
+            if need_dhidden:
+                check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), self.stats.data_ptr(), self.dpooled.data_ptr(),
+                                           dh.data_ptr(), B, S, self.E, None if cu is None else cu.data_ptr(), rows, 0,
+                                           _stream()), "vlb_head_dhidden")
+            return dh
         fn, tail, what = lib.vlb_head_bwd, (), "vlb_head_bwd"
         if self.loss_kind:
             fn, tail, what = lib.vlb_head_bwd_loss, (self.loss_kind, self.rowstat.data_ptr()), "vlb_head_bwd_loss"
@@ -188,10 +308,11 @@ class BrainHead:
         return dh
 
     # ------------------------------------------------------------------ frozen-backbone feature cache (feature_cache.py)
-    def forward_cached(self, cache, indices, y, keep_scale=None):
+    def forward_cached(self, cache, indices, y, keep_scale=None, subject=None):
         """The head forward of a batch whose (pooled_raw, sumw) sit in ``cache`` rows ``indices`` (host int64 [B]):
         -> (pred f32 [B,V], loss_terms f32[3]), the same bits vlb_head_fwd gives for the same (pooled_raw, sumw)."""
         B = y.shape[0]
+        group = self._group(subject, B)
         rows = cache.rows(indices)
         if rows.numel() != B:
             raise ValueError(f"head: {rows.numel()} cache rows for a batch of {B}")
@@ -203,9 +324,11 @@ class BrainHead:
                 check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
                                                    self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
                                                    _stream()), "vlb_feature_cache_gather")
-            return self.forward_tapped(y, keep_scale)
+            return self.forward_tapped(y, keep_scale, subject)
         if self._cap is None or self._cap[0] != B:
             self._buffers(B, 1)           # no pooling workspace needed; buffers of an uncached step of this B serve as they are
+        if group is not None:
+            return self._fwd_grouped(cache.pooled, cache.sumw, rows, cache.n, y, keep_scale, group)
         self._saved_cached = (y, keep_scale)
         c = self.compute
         check(lib.vlb_head_fwd_cached(cache.pooled.data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
@@ -260,14 +383,17 @@ class BrainHead:
                                 self.p_stack[i].data_ptr(), self.tap_sumw.data_ptr(), B, S, self.E, self.eps,
                                 None if cu is None else cu.data_ptr(), _stream()), "vlb_head_pool")
 
-    def forward_tapped(self, y, keep_scale=None):
+    def forward_tapped(self, y, keep_scale=None, subject=None):
         """alpha = softmax(layer_mix.weight), pooled_raw = sum_k alpha_k P_k, then the tail of the head as
         vlb_head_fwd_cached runs it on (pooled_raw, sumw) -> (pred f32 [B,V], loss_terms f32[3])."""
         B = y.shape[0]
+        group = self._group(subject, B)
         c = self.compute
         check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), c[LAYER_MIX].data_ptr() if self.K > 1 else None,
                                    self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
               "vlb_head_mix_fwd")
+        if group is not None:
+            return self._fwd_grouped(self.mixed, self.tap_sumw, self.identity_rows, B, y, keep_scale, group)
         self._saved_cached = (y, keep_scale)
         check(lib.vlb_head_fwd_cached(self.mixed.data_ptr(), self.tap_sumw.data_ptr(), self.identity_rows.data_ptr(),
                                       c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
@@ -309,6 +435,8 @@ class BrainHead:
 
     def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
         """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""
+        if self.G:
+            return self._bwd_grouped(loss_scale, l2_scale)
         y, keep_scale = self._saved_cached
         B = y.shape[0]
         c, gr = self.compute, self.grads

@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
-from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers
+from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers, check_subjects
 from .optim import VlbAdamW
 
 
@@ -171,6 +171,9 @@ class VLBLitModuleConfig:
     # decoder layers the head reads (HF hidden_states[k], k in [1, L] or [-L, -1]; more than one: a learned softmax mix of their
     # pooled features, ``layer_mix.weight``); the decoder stops at the highest.  None: hidden_states[-1], as the reference
     readout_layers: list[int] | None = None
+    # two or more subject names: one backbone (and adapter set), one ridge head per subject (``ridge_layer.linear.weight``
+    # [G,V,E]); every batch then carries "subject" (datamodule.config.subjects, the same list).  None: one head, as the reference
+    subjects: list[str] | None = None
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -181,6 +184,8 @@ class VLBLitModuleConfig:
         if self.merge_lora_for_eval and not self.use_lora:
             raise ValueError("merge_lora_for_eval=True needs use_lora=True: without adapters there is nothing to merge")
         check_loss(self.loss, self.num_target)
+        if self.subjects is not None:
+            self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
             if not self.freeze_backbone and not self.use_lora:
                 raise ValueError("readout_layers with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported: "
@@ -188,6 +193,28 @@ class VLBLitModuleConfig:
                                  "freeze_backbone=True or use_lora=True")
             # the geometry name fixes L here already; configure_model checks again against the geometry it builds
             self.readout_layers = check_readout_layers(self.readout_layers, resolve_geometry(self).layers)
+
+
+def check_batch_subjects(batch, subjects, B: int | None = None):
+    """The per-clip head index of a batch, checked on the host: -> None for a single-subject module, else an int64 CPU tensor
+    [B] with values in [0, len(subjects)).  A batch with "subject" reaching a module without ``subjects``, or the reverse, is a
+    configuration error (the module's and the datamodule's ``subjects`` must be the same list)."""
+    has = "subject" in batch
+    if has != (subjects is not None):
+        raise ValueError(f"the batch {'carries' if has else 'has no'} \"subject\" but litmodule.config.subjects is "
+                         f"{None if subjects is None else list(subjects)!r}: set litmodule.config.subjects and "
+                         "datamodule.config.subjects to the same list (or leave both unset for one subject)")
+    if subjects is None:
+        return None
+    idx = torch.as_tensor(batch["subject"]).detach().cpu().flatten()
+    if idx.is_floating_point() or idx.dtype == torch.bool:
+        raise ValueError(f"batch[\"subject\"] is {idx.dtype}: integer indices into subjects={list(subjects)!r} are needed")
+    idx = idx.to(torch.int64)
+    if B is not None and idx.numel() != B:
+        raise ValueError(f"batch[\"subject\"] has {idx.numel()} entries for a batch of {B} clips")
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= len(subjects)):
+        raise ValueError(f"batch[\"subject\"]={idx.tolist()!r}: an index outside [0, {len(subjects)}) (subjects={list(subjects)!r})")
+    return idx
 
 
 def resolve_geometry(cfg: VLBLitModuleConfig) -> Geometry:
@@ -284,7 +311,7 @@ class VLBLitModule(_Base):
         self.nnmodule = _Attr(config=_Attr(hidden_size=g.dim, tokenizer_model_max_length=g.max_len,
                                            num_frames=g.num_frames, use_cache=False), backbone=self.backbone)
         self.head = BrainHead(g.dim, cfg.num_target, cfg.l2_lambda, g.ln_eps, dev, sd=head_state, seed=cfg.init_seed,
-                              loss=getattr(cfg, "loss", "mse"), readout_layers=taps)
+                              loss=getattr(cfg, "loss", "mse"), readout_layers=taps, subjects=getattr(cfg, "subjects", None))
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -402,10 +429,14 @@ class VLBLitModule(_Base):
             x_video = torch.stack([v[0] if isinstance(v, (list, tuple)) else v for v in x_video])
         return x_video.to(self.device, torch.float32).contiguous()
 
-    def forward(self, x_video, x_lang, weight_mask, attention_mask=None, y=None, keep_scale=None, layout=None, ids_host=None):
+    def forward(self, x_video, x_lang, weight_mask, attention_mask=None, y=None, keep_scale=None, layout=None, ids_host=None,
+                subject=None):
         """reference :229-256 -> (regression_output fp32 [B,V], l2_reg).  attention_mask is re-derived
         on the device from the ids (ids != 0), exactly what the reference passes in (:271).
-        ``layout``: packed RowLayout from ``backbone.row_layout`` (rows without padded tails)."""
+        ``layout``: packed RowLayout from ``backbone.row_layout`` (rows without padded tails).  ``subject``: with
+        ``config.subjects``, the head index of every clip (host ints or a CPU tensor [B]); checked before anything is launched."""
+        if (subject is None) != (self.head.G == 0):
+            self.head._group(subject, x_lang.shape[0])          # raises: a multi-subject head needs `subject`, a single one takes none
         vis = self._vision_tensor(x_video)
         ids = x_lang.to(self.device, torch.int64).contiguous()
         B = ids.shape[0]
@@ -426,9 +457,9 @@ class VLBLitModule(_Base):
         if y is None:
             y = torch.zeros(B, self.config.num_target, dtype=torch.float32, device=self.device)
         if taps is not None:
-            pred, terms = self.head.forward_tapped(y, keep_scale)
+            pred, terms = self.head.forward_tapped(y, keep_scale, subject)
         else:
-            pred, terms = self.head.forward(hidden, weight_mask, y, keep_scale, layout)
+            pred, terms = self.head.forward(hidden, weight_mask, y, keep_scale, layout, subject)
         self._loss_terms = terms
         return pred, terms[1]
 
@@ -475,6 +506,7 @@ class VLBLitModule(_Base):
         cfg, g = self.config, self.geometry
         dev = self.device
         self._cached_step = False
+        subject = check_batch_subjects(batch, getattr(cfg, "subjects", None), len(batch["timeseries"]))
         cache = self.feature_caches.get("train" if train else "val") if cfg.cache_features and "index" in batch else None
         if cache is not None and cache.lookup(batch["index"]):
             # every clip's features are cached: no backbone, no weight mask; the same head kernels on the same fp32 inputs
@@ -484,7 +516,7 @@ class VLBLitModule(_Base):
                 keep = ops.dropout_keep_scale(y.shape[0], g.dim, cfg.dropout_rate, self._dropout_seed(), dev)
             if torch.is_tensor(batch.get("vision")):
                 self.discard_prefetched_vision(batch)       # its frozen vision side is not needed
-            pred, terms = self.head.forward_cached(cache, batch["index"], y, keep)
+            pred, terms = self.head.forward_cached(cache, batch["index"], y, keep, subject)
             self._loss_terms = terms
             self._cached_step = True
             return pred, y, terms
@@ -501,7 +533,7 @@ class VLBLitModule(_Base):
         if train and cfg.dropout_rate > 0:          # nn.Dropout(p) in training mode (reference :226,251)
             keep = ops.dropout_keep_scale(x_lang.shape[0], g.dim, cfg.dropout_rate, self._dropout_seed(), dev)
         ids_host = batch["language"] if batch["language"].device.type == "cpu" else None
-        pred, _ = self.forward(batch["vision"], x_lang, wm, y=y, keep_scale=keep, layout=layout, ids_host=ids_host)
+        pred, _ = self.forward(batch["vision"], x_lang, wm, y=y, keep_scale=keep, layout=layout, ids_host=ids_host, subject=subject)
         if cache is not None and cache.store(batch["index"], self.head) and cache.complete() and cfg.feature_cache_dir:
             cache.save(cfg.feature_cache_dir, self._feature_cache_fp[cache.split])
         return pred, y, self._loss_terms
@@ -671,7 +703,10 @@ class VLBLitModule(_Base):
         self.log("val/brain_loss", loss)
         if self.head.loss_kind:
             self.log("val/brain_mse", self.head.loss_aux[0].clone())
-        return {"loss": loss, "brain_preds": pred.clone(), "brain_vals": y}
+        out = {"loss": loss, "brain_preds": pred.clone(), "brain_vals": y}
+        if "subject" in batch:            # per-subject validation correlations (LogValAccuracyCallback)
+            out["subject"] = torch.as_tensor(batch["subject"]).detach().cpu().to(torch.int64)
+        return out
 
     # ------------------------------------------------------------------ hooks Lightning's fit loop calls (reference train.py:41-56)
     def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):
@@ -684,8 +719,9 @@ class VLBLitModule(_Base):
 
     def transfer_batch_to_device(self, batch, device, dataloader_idx=0):
         """Pixels / targets / weights go to the GPU; the token ids and ``padvals`` (20 KB) stay on the host so the step can size
-        its unpadded row layout without a device sync (the step uploads them itself); so does a feature-cache ``index``."""
-        keep = ("language", "padvals", "index")
+        its unpadded row layout without a device sync (the step uploads them itself); so do a feature-cache ``index`` and the
+        per-clip ``subject`` index (checked on the host, uploaded by the head)."""
+        keep = ("language", "padvals", "index", "subject")
         return {k: (v.to(device, non_blocking=True) if torch.is_tensor(v) and k not in keep else v) for k, v in batch.items()}
 
     def on_fit_start(self):

@@ -289,7 +289,7 @@ class Trainer:
         except TypeError:
             train_loader = datamodule.train_dataloader()
         val_loader = datamodule.val_dataloader()
-        keep_on_host = ("language", "padvals")
+        keep_on_host = ("language", "padvals", "subject")    # "subject" (multi-subject runs): the head checks it on the host
         if self._feature_cache:
             model.setup_feature_cache(train_loader.dataset, val_loader.dataset)
             keep_on_host += ("index",)        # the cache decides hit / miss on the host

@@ -95,16 +95,30 @@ class RidgeRegressionLayer:
 class LogValAccuracyCallback(_Callback):
     """Per-target Pearson r over the validation set (src/utils.py:85-110), streamed: five running sums
     per target on the device instead of concatenating every prediction, and ONE tensor of per-target
-    correlations (kept available as `correlations`) copied to the host once before the per-ROI log() calls."""
+    correlations (kept available as `correlations`) copied to the host once before the per-ROI log() calls.
+
+    Multi-subject runs (``outputs["subject"]``: the index of every clip into ``pl_module.config.subjects``): the five sums are
+    kept per subject, [G,5,V] with clip counts [G]; logged are ``val_corr_avg/<subject>`` and ``val_corr_ROI_xxxxxx/<subject>``
+    for every subject that had validation clips, and ``val_corr_avg`` = the mean of the former over those subjects
+    (`correlations` is then [G,V], NaN rows for subjects without clips).  Without the key nothing changes."""
 
     def on_validation_epoch_start(self, trainer, pl_module):
         self.n = 0
         self.s = None
+        self.count = None               # multi-subject only: clips per subject, fp64 [G] on the device
 
     def on_validation_batch_end(self, trainer, pl_module, outputs, batch, batch_idx, dataloader_idx=0):
         y = torch.nan_to_num(outputs["brain_vals"].double())
         p = torch.nan_to_num(outputs["brain_preds"].double())
-        cur = torch.stack([p.sum(0), y.sum(0), (p * p).sum(0), (y * y).sum(0), (p * y).sum(0)])
+        subject = outputs.get("subject") if isinstance(outputs, dict) else None
+        if subject is not None:
+            G = len(pl_module.config.subjects)
+            onehot = torch.nn.functional.one_hot(torch.as_tensor(subject).to(p.device, torch.int64), G).double()     # [B,G]
+            cur = torch.einsum("bg,kbv->gkv", onehot, torch.stack([p, y, p * p, y * y, p * y]))
+            cnt = onehot.sum(0)
+            self.count = cnt if self.count is None else self.count + cnt
+        else:
+            cur = torch.stack([p.sum(0), y.sum(0), (p * p).sum(0), (y * y).sum(0), (p * y).sum(0)])
         self.s = cur if self.s is None else self.s + cur
         self.n += p.shape[0]
 
@@ -113,21 +127,56 @@ class LogValAccuracyCallback(_Callback):
         issues the same two collectives - a rank that drew no batch (fewer validation batches than ranks,
         ``limit_val_batches`` < world) contributes zeros instead of skipping them."""
         import torch.distributed as dist
+        subjects = getattr(getattr(pl_module, "config", None), "subjects", None)
+        stacked = self.count is not None or (self.s is None and subjects is not None)
         if self.s is None:
             if pl_module is None:
                 raise RuntimeError("all_reduce_sums() on a rank without validation batches needs the module "
                                    "(device and num_target of the zero contribution)")
-            self.s = torch.zeros(5, pl_module.config.num_target, dtype=torch.float64, device=pl_module.device)
+            shape = (len(subjects), 5, pl_module.config.num_target) if stacked else (5, pl_module.config.num_target)
+            self.s = torch.zeros(*shape, dtype=torch.float64, device=pl_module.device)
         n = torch.tensor([float(self.n)], dtype=torch.float64, device=self.s.device)
         dist.all_reduce(self.s)
         dist.all_reduce(n)
+        if stacked:                           # the stacked sums [G,5,V] went through above; their clip counts [G] follow
+            if self.count is None:
+                self.count = torch.zeros(self.s.shape[0], dtype=torch.float64, device=self.s.device)
+            dist.all_reduce(self.count)
         self.n = int(n.item())
         if self.n == 0:
-            self.s = None                     # nobody validated anything: nothing to report
+            self.s = self.count = None        # nobody validated anything: nothing to report
+
+    @staticmethod
+    def _corr(s, n):
+        sp, sy, spp, syy, spy = s
+        cov = spy - sp * sy / n
+        var = (spp - sp * sp / n) * (syy - sy * sy / n)
+        return (cov / var.clamp_min(1e-30).sqrt()).float()
+
+    def _per_subject_epoch_end(self, pl_module):
+        names = list(pl_module.config.subjects)
+        counts = self.count.cpu().tolist()                   # one small copy: which subjects had clips
+        V = self.s.shape[-1]
+        self.correlations = torch.full((len(names), V), float("nan"), dtype=torch.float32, device=self.s.device)
+        limit = getattr(self, "max_roi_logs", None)
+        avgs = []
+        for g, name in enumerate(names):
+            if counts[g] <= 0:
+                continue
+            self.correlations[g] = self._corr(self.s[g], float(counts[g]))
+            host = self.correlations[g].cpu().tolist()
+            for i in range(V if limit is None else min(V, limit)):
+                pl_module.log(f"val_corr_ROI_{i:0{6}}/{name}", host[i])
+            avgs.append(self.correlations[g].mean())
+            pl_module.log(f"val_corr_avg/{name}", avgs[-1])
+        if avgs:
+            pl_module.log("val_corr_avg", torch.stack(avgs).mean())
 
     def on_validation_epoch_end(self, trainer, pl_module):
         if self.s is None:
             return
+        if self.count is not None:
+            return self._per_subject_epoch_end(pl_module)
         n = float(self.n)
         sp, sy, spp, syy, spy = self.s
         cov = spy - sp * sy / n
