@@ -593,6 +593,39 @@ int64_t vlb_ridge_ws_floats(int V);
 int vlb_ridge_fwd(const void* x, const void* ridge_w, const void* ridge_b, float* pred, float* l2_out, float* ws, int B, int E, int V,
                   float l2_lambda, void* stream);
 
+/* Closed-form fit of the ridge head from the frozen-feature cache (opt-in, ridge_fit="closed_form"; every
+ * entry point above keeps its bits).  With loss = mse, fixed LN parameters and dropout off the head's objective over N clips,
+ *   J(W, b) = 1/(N V) sum_n ||W z_n + b - y_n||^2 + l2_lambda ||W||_F^2,
+ * is a ridge regression in the RidgeRegressionLayer's (src/utils.py:59-73) weight and bias; its minimiser is
+ *   (Zc^T Zc + l2_lambda N V I) W^T = Zc^T Yc,  b = ybar - W zbar   (Zc, Yc: column-centred; the bias is not penalised).
+ * All sums, the factorisation and the solves are fp64; no atomics, fixed summation order: the same input gives the same bits.
+ * vlb_head_features_cached (src/utils.py:59-73: the layer's input): the gather vlb_head_fwd_cached starts with and its
+ *   LN1-affine + LN2 launch with keep_scale = NULL, nothing else -> z bf16 [B,E] (the bits vlb_head_fwd_cached leaves in z
+ *   for the same rows and keep_scale = NULL) and the pooled_raw / sumw / zhat / ln2_rstd it writes.
+ * vlb_ridge_gram_accumulate (src/utils.py:59-73): G [E,E] += z^T z (the full square, both triangles), C [V,E] += y^T z (the
+ *   layout of W), sz [E] += colsum(z), sy [V] += colsum(y) for a chunk of n >= 1 rows; z bf16 [n,E], y fp32 [n,V] with
+ *   pitch ldy.  The caller zeroes the four fp64 buffers before the first chunk.
+ * vlb_chol_f64 (src/utils.py:59-73: the system's factor): in-place lower Cholesky of the n x n fp64 matrix A (pitch lda),
+ *   blocked by 64; any n >= 1.  Only the lower triangle is read and written; bytes above the diagonal are untouched.
+ *   *info (device int) is cleared first; a pivot that is not > 0 (NaN included) stores its 1-based index there, and the
+ *   rest of the factorisation - and a vlb_chol_solve_f64 handed the same info - does nothing.
+ * vlb_chol_solve_f64 (src/utils.py:59-73: the weights): every row v of X [nrhs,n] (pitch ldx) <- the solution of
+ *   L L^T x = X[v,:], in place: blocked forward, then back substitution.  info: the factorisation's (read only).
+ * vlb_ridge_solve (src/utils.py:59-73): A_ws [E,E] <- G - sz sz^T / N + l2_lambda N V I, X_ws [V,E] <- C - sy sz^T / N,
+ *   factor, solve (X_ws keeps the fp64 solution), W_out fp32 [V,E] <- X_ws, b_out fp32 [V] <- sy / N - X_ws sz / N.
+ *   G, C, sz, sy are read only: another l2_lambda re-solves from the same sums.  *info: the factorisation's pivot index,
+ *   or -(v + 1) for the first target column v whose sum sy[v] is not finite (a NaN / Inf target never reaches the matrix);
+ *   on *info != 0 W_out / b_out are not written. */
+int vlb_head_features_cached(const float* cache_pooled, const float* cache_sumw, const int32_t* rows, const void* ln1_w,
+                             const void* ln1_b, const void* ln2_w, const void* ln2_b, float* pooled_raw, float* sumw,
+                             float* zhat, float* ln2_rstd, void* z, int B, int E, int n_rows, float eps, void* stream);
+int vlb_ridge_gram_accumulate(const void* z, const float* y, int ldy, double* G, double* C, double* sz, double* sy, int n, int E,
+                              int V, void* stream);
+int vlb_chol_f64(double* A, int n, int lda, int* info, void* stream);
+int vlb_chol_solve_f64(const double* L, int ldl, double* X, int n, int nrhs, int ldx, const int* info, void* stream);
+int vlb_ridge_solve(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
+                    double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, void* stream);
+
 /* head dropout mask (litmodule :226,251 nn.Dropout(p) in training): out[i] = keep_i / (1-p), keep_i from a
  * counter-based hash of (seed, i) with 16 random bits per element (same mixer as the LoRA masks).  The result is
  * what vlb_head_fwd / vlb_head_bwd take as `keep_scale`. */

@@ -20,7 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VLB_LIB") or os.path.join(_HERE, "libvlb.so")
 IS_PRODUCT_LIB = os.path.abspath(LIB_PATH) == os.path.join(_HERE, "libvlb.so")
 
-P, I, F, L = c_void_p, c_int, c_float, c_int64
+P, I, F, L, D = c_void_p, c_int, c_float, c_int64, c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/vlb.h one to one
 SIGNATURES = {
@@ -129,6 +129,11 @@ SIGNATURES = {
     "vlb_hrf_pool": [P, I, P, P, P, I, I, I, P],
     "vlb_ridge_ws_floats": [I],
     "vlb_ridge_fwd": [P, P, P, P, P, P, I, I, I, F, P],
+    "vlb_head_features_cached": [P] * 12 + [I, I, I, F, P],
+    "vlb_ridge_gram_accumulate": [P, P, I, P, P, P, P, I, I, I, P],
+    "vlb_chol_f64": [P, I, I, P, P],
+    "vlb_chol_solve_f64": [P, I, P, I, I, I, P, P],
+    "vlb_ridge_solve": [P, P, P, P, L, D, P, P, P, P, P, I, I, P],
     "vlb_allreduce_scalar": [P, P, I, P],
     "vlb_cast_f32_to_bf16": [P, P, L, P],
     "vlb_cast_bf16_to_f32": [P, P, L, P],

@@ -956,15 +956,23 @@ int ridge_fwd_parts(int B, int E, int V) {
   return mfma ? (ntiles < 2048 ? ntiles : 2048) : (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
 }
 
+// The LN1-affine + LN2 (+ dropout) launch on its own: head_fwd_tail's first launch, and all of vlb_head_features_cached.
+int head_ln2_launch(const float* pooled_raw, const float* sumw, const void* ln1_w, const void* ln1_b, const void* ln2_w,
+                    const void* ln2_b, const float* keep_scale, float* zhat, float* ln2_rstd, void* z, int B, int E, float eps,
+                    hipStream_t st) {
+  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
+                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
 // LN1 affine + LN2 + dropout -> z, ridge GEMV, loss: everything of the forward that reads only (pooled_raw, sumw).
 // vlb_head_fwd and vlb_head_fwd_cached both end here, so the two give the same bits for the same (pooled_raw, sumw).
 int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w, const void* ln1_b, const void* ln2_w,
                   const void* ln2_b, const void* ridge_w, const void* ridge_b, const float* y, const float* keep_scale,
                   float* lpart, float* zhat, float* ln2_rstd, void* z, float* pred, float* loss_terms, int B, int E, int V,
                   float eps, float l2_lambda, hipStream_t st) {
-  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
-                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
-  VLB_LAUNCH_CHECK();
+  if (int rc = head_ln2_launch(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, keep_scale, zhat, ln2_rstd, z, B, E, eps, st)) return rc;
   int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
   if (B <= 16 && E % 128 == 0 && E <= 4096) {
     const int ntiles = (V + 15) / 16;
@@ -1436,6 +1444,22 @@ extern "C" int vlb_head_fwd_cached(const float* cache_pooled, const float* cache
   VLB_LAUNCH_CHECK();
   return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, ws, zhat, ln2_rstd, z,
                        pred, loss_terms, B, E, V, eps, l2_lambda, st);
+}
+
+// The features the ridge layer reads, for the closed-form fit (ridge_solve.hip): the same gather, the same LN2 launch with
+// keep_scale = NULL, and nothing after it - no ridge, no loss.
+extern "C" int vlb_head_features_cached(const float* cache_pooled, const float* cache_sumw, const int* rows, const void* ln1_w,
+                                        const void* ln1_b, const void* ln2_w, const void* ln2_b, float* pooled_raw, float* sumw,
+                                        float* zhat, float* ln2_rstd, void* z, int B, int E, int n_rows, float eps, void* stream) {
+  VLB_REQUIRE(cache_pooled && cache_sumw && rows && ln1_w && ln1_b && ln2_w && ln2_b && pooled_raw && sumw && zhat && ln2_rstd && z,
+              "head_features_cached: null argument");
+  VLB_REQUIRE(B > 0 && n_rows > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_features_cached: bad shape B=%d E=%d n_rows=%d", B, E,
+              n_rows);
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
+                     pooled_raw, sumw, E, n_rows);
+  VLB_LAUNCH_CHECK();
+  return head_ln2_launch(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, nullptr, zhat, ln2_rstd, z, B, E, eps, st);
 }
 
 extern "C" int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,

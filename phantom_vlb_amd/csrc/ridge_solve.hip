@@ -1,0 +1,450 @@
+// Closed-form fit of the ridge head (RidgeRegressionLayer, src/utils.py:59-73) from the frozen-feature cache, DESIGN §5.3.5.
+//
+//   J(W, b) = 1/(N V) sum_n || W z_n + b - y_n ||^2 + l2_lambda ||W||_F^2         (z bf16 [E], y fp32 [V])
+//   (Zc^T Zc + l2_lambda N V I) W^T = Zc^T Yc,   b = ybar - W zbar
+//
+// Everything here is fp64: the sums G = Z^T Z [E,E], C = Y^T Z [V,E], sz = colsum(Z), sy = colsum(Y) (products of a bf16
+// and a bf16 / fp32 value are exact in fp64), the centring, the lower Cholesky factor and the two triangular solves.
+// Plain fp64 FMAs (v_fma_f64), no MFMA: fp64 time is not what these epochs wait for (§5.3.5 has the figures).
+// No atomics anywhere: every output element is owned by one thread and summed in one fixed order, so two runs give the same
+// bits.  All stores are vector stores.
+#include "common.hpp"
+
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+
+namespace {
+
+constexpr int TS = 64;        // output tile edge of the tile kernels (256 threads, 4 x 4 results each)
+constexpr int GK = 32;        // rows of z / y staged per step of the Gram kernel
+constexpr int FK = 16;        // k-slice of the fp64 tile kernel
+constexpr int NB = 64;        // Cholesky / substitution block
+constexpr int LP = NB + 1;    // LDS row pitch (doubles) of a 64 x 64 block: column walks hit 64 different banks
+
+// ---------------------------------------------------------------- Gram pass: D[M,N] += A^T B over n rows
+// A is [n, M] (bf16 for G: the same z; fp32 for C: y, pitch lda), B = z bf16 [n, N], D fp64 [M, N] row-major, pitch ldd.
+// grid (ceil(N/64), ceil(M/64)), 256 threads.  A 32-row slab of each operand is staged in LDS in its own narrow type (one
+// 16-byte global load and one 16-byte LDS store per lane where the pitch allows, contiguous over the lanes: no bank
+// conflict) and widened when read: per k a thread reads its 4 A and 4 B values as one 8- or 16-byte LDS read (16 lanes
+// contiguous, the 4 lane rows broadcast).  The rows are summed in ascending order into 16 fp64 accumulators per thread.
+__device__ __forceinline__ double widen(bf16 x) { return (double)(float)x; }
+__device__ __forceinline__ double widen(float x) { return (double)x; }
+
+template <typename T>
+__device__ __forceinline__ void stage_slab(const T* __restrict__ src, int64_t ld, int r0, int n, int c0, int ncols, T* lds) {
+  constexpr int PER = 16 / (int)sizeof(T);                 // elements of one 16-byte access
+  constexpr int CHUNKS = GK * TS / PER;                    // 256 (bf16) or 512 (fp32)
+  const bool vec = ld % PER == 0 && ((uintptr_t)src & 15) == 0 && c0 + TS <= ncols;      // block-uniform
+#pragma unroll
+  for (int c = threadIdx.x; c < CHUNKS; c += 256) {
+    const int r = c / (TS / PER), col = (c % (TS / PER)) * PER;
+    T* dst = lds + r * TS + col;
+    if (vec) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (r0 + r < n) v = *reinterpret_cast<const u32x4*>(src + (int64_t)(r0 + r) * ld + c0 + col);
+      *reinterpret_cast<u32x4*>(dst) = v;
+    } else {
+#pragma unroll
+      for (int i = 0; i < PER; ++i)
+        dst[i] = (r0 + r < n && c0 + col + i < ncols) ? src[(int64_t)(r0 + r) * ld + c0 + col + i] : (T)0.f;
+    }
+  }
+}
+
+template <typename TA>
+__global__ __launch_bounds__(256) void gram_tile_kernel(const TA* __restrict__ A, int64_t lda, const bf16* __restrict__ Bz,
+                                                        int64_t ldb, double* __restrict__ D, int64_t ldd, int n, int M, int N) {
+  __shared__ __attribute__((aligned(16))) TA As[GK * TS];
+  __shared__ __attribute__((aligned(16))) bf16 Bs[GK * TS];
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  const int i0 = blockIdx.y * TS, j0 = blockIdx.x * TS;
+  double acc[4][4] = {};
+  for (int r0 = 0; r0 < n; r0 += GK) {
+    __syncthreads();
+    stage_slab<TA>(A, lda, r0, n, i0, M, As);
+    stage_slab<bf16>(Bz, ldb, r0, n, j0, N, Bs);
+    __syncthreads();
+#pragma unroll 8
+    for (int k = 0; k < GK; ++k) {
+      double a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = widen(As[k * TS + ty * 4 + i]);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = widen(Bs[k * TS + tx * 4 + j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+    }
+  }
+  const int col = j0 + tx * 4;
+  const bool vec = ldd % 2 == 0 && ((uintptr_t)D & 15) == 0 && col + 4 <= N;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = i0 + ty * 4 + i;
+    if (row >= M) continue;
+    double* d = D + (int64_t)row * ldd + col;
+    if (vec) {
+      f64x2* d2 = reinterpret_cast<f64x2*>(d);
+      f64x2 lo = d2[0], hi = d2[1];
+      lo.x += acc[i][0]; lo.y += acc[i][1]; hi.x += acc[i][2]; hi.y += acc[i][3];
+      d2[0] = lo; d2[1] = hi;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (col + j < N) d[j] += acc[i][j];
+    }
+  }
+}
+
+// s[c] += sum over the n rows (ascending) of x[r, c]: one thread per column, lanes on consecutive columns
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_f64_kernel(const T* __restrict__ x, int64_t ld, double* __restrict__ s, int n,
+                                                         int ncols) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  double t = 0.0;
+  for (int r = 0; r < n; ++r) t += widen(x[(int64_t)r * ld + c]);
+  s[c] += t;
+}
+
+// ---------------------------------------------------------------- fp64 tile kernel: D[M,N] -= P Q^T  (or P Q, QT)
+//   D[i,j] -= sum_{k<K} P[i*ldp + k] * (QT ? Q[k*ldq + j] : Q[j*ldq + k])
+// The Cholesky trailing update (P = Q = the panel below the diagonal block, lower = 1: only tiles that touch the lower
+// triangle run and only elements with j <= i are stored, D's (0,0) being a diagonal element) and the block updates of the
+// forward (P = solved block of X, Q = rows of L) and back (QT: Q = columns of L) substitution.
+// grid (ceil(N/64), ceil(M/64)), 256 threads.  Both operands are staged k-major in LDS with a 65-double pitch: the fill's
+// 8-byte stores (4 rows x 4 k-quads per 16 lanes; QT: 16 consecutive columns) and the reads (16 consecutive doubles per
+// lane row, the other lane rows broadcast) touch every bank at most once per lane group.  A thread owns rows ty + 16 i and
+// columns tx + 16 j, so its global accesses to D are 128 contiguous bytes per 16 lanes.
+// A non-zero *info (a failed factorisation) turns the kernel into a no-op.
+template <bool QT>
+__global__ __launch_bounds__(256) void tile_sub_f64_kernel(double* __restrict__ D, int64_t ldd, const double* P, int64_t ldp,
+                                                           const double* Q, int64_t ldq, int M, int N, int K, int lower,
+                                                           const int* __restrict__ info) {
+  __shared__ double Ps[FK * LP];
+  __shared__ double Qs[FK * LP];
+  if (info && *info != 0) return;
+  const int i0 = blockIdx.y * TS, j0 = blockIdx.x * TS;
+  if (lower && j0 > i0 + TS - 1) return;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  double acc[4][4] = {};
+  const bool pvec = ldp % 2 == 0 && ((uintptr_t)P & 15) == 0, qvec = ldq % 2 == 0 && ((uintptr_t)Q & 15) == 0;
+  for (int kc = 0; kc < K; kc += FK) {
+    __syncthreads();
+    {   // rows of P (and of Q): lane t -> row t / 4, k-quad t % 4; two 16-byte loads where aligned
+      const int r = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4, k = kc + kq;
+      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      if (i0 + r < M) {
+        const double* p = P + (int64_t)(i0 + r) * ldp + k;
+        if (pvec && k + 4 <= K) {
+          const f64x2 lo = reinterpret_cast<const f64x2*>(p)[0], hi = reinterpret_cast<const f64x2*>(p)[1];
+          v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (k + i < K) v[i] = p[i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) Ps[(kq + i) * LP + r] = v[i];
+      if (!QT) {
+        double w[4] = {0.0, 0.0, 0.0, 0.0};
+        if (j0 + r < N) {
+          const double* q = Q + (int64_t)(j0 + r) * ldq + k;
+          if (qvec && k + 4 <= K) {
+            const f64x2 lo = reinterpret_cast<const f64x2*>(q)[0], hi = reinterpret_cast<const f64x2*>(q)[1];
+            w[0] = lo.x; w[1] = lo.y; w[2] = hi.x; w[3] = hi.y;
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (k + i < K) w[i] = q[i];
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Qs[(kq + i) * LP + r] = w[i];
+      } else {   // Q is k-major already: lane t -> k t / 16, columns t % 16 + 16 i (128 contiguous bytes per 16 lanes)
+        const int kk = threadIdx.x >> 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int j = tx + 16 * i;
+          Qs[kk * LP + j] = (kc + kk < K && j0 + j < N) ? Q[(int64_t)(kc + kk) * ldq + j0 + j] : 0.0;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FK; ++k) {
+      double a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = Ps[k * LP + ty + 16 * i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = Qs[k * LP + tx + 16 * j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = i0 + ty + 16 * i;
+    if (row >= M) continue;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = j0 + tx + 16 * j;
+      if (col < N && (!lower || col <= row)) D[(int64_t)row * ldd + col] -= acc[i][j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------- Cholesky: the nb x nb diagonal block, in LDS
+// One block of 256 threads, right-looking.  Only the lower triangle is read and written.  A pivot that is not > 0 (a NaN
+// fails the comparison too) puts its 1-based index into *info (first failure wins) and ends the kernel before anything of
+// this block is written back; every later kernel of the factorisation and of a solve returns at once on *info != 0.
+__global__ __launch_bounds__(256) void chol_block_kernel(double* __restrict__ A, int64_t lda, int k0, int nb, int* __restrict__ info) {
+  __shared__ double Ls[NB * LP];
+  if (*info != 0) return;
+  double* blk = A + (int64_t)k0 * lda + k0;
+  for (int e = threadIdx.x; e < nb * nb; e += 256) {
+    const int i = e / nb, j = e % nb;
+    if (j <= i) Ls[i * LP + j] = blk[(int64_t)i * lda + j];
+  }
+  __syncthreads();
+  for (int j = 0; j < nb; ++j) {
+    const double d = Ls[j * LP + j];
+    if (!(d > 0.0)) {                       // uniform: every thread reads the same value
+      if (threadIdx.x == 0) *info = k0 + j + 1;
+      return;
+    }
+    const double s = sqrt(d);
+    __syncthreads();
+    if (threadIdx.x == 0) Ls[j * LP + j] = s;
+    for (int i = j + 1 + threadIdx.x; i < nb; i += 256) Ls[i * LP + j] /= s;
+    __syncthreads();
+    const int m = nb - j - 1;               // trailing square (rows, columns j+1 .. nb-1), lower part
+    for (int e = threadIdx.x; e < m * m; e += 256) {
+      const int i = j + 1 + e / m, c = j + 1 + e % m;
+      if (c <= i) Ls[i * LP + c] = fma(-Ls[i * LP + j], Ls[c * LP + j], Ls[i * LP + c]);
+    }
+    __syncthreads();
+  }
+  for (int e = threadIdx.x; e < nb * nb; e += 256) {
+    const int i = e / nb, j = e % nb;
+    if (j <= i) blk[(int64_t)i * lda + j] = Ls[i * LP + j];
+  }
+}
+
+// ---------------------------------------------------------------- substitution with one diagonal block, a row per thread
+// X[r, k0 .. k0+nb) <- that row solved against L11 = L[k0.., k0..) (nb x nb, lower):
+//   !BACK: x L11^T = a, i.e. x_j = (a_j - sum_{k<j} x_k L11[j,k]) / L11[j,j]    (Cholesky panel below the block; forward solve)
+//    BACK: x L11   = a, i.e. x_j = (a_j - sum_{k>j} x_k L11[k,j]) / L11[j,j]    (back solve)
+// L11 sits in LDS (T[j][k] = the coefficient of x_k in equation j; every lane reads the same word: a broadcast), padded to
+// 64 x 64 with the identity so the loops have constant bounds and the row lives in registers.  grid ceil(rows/256).
+template <bool BACK>
+__global__ __launch_bounds__(256) void tri_rows_kernel(double* __restrict__ X, int64_t ldx, int nrows, const double* L, int64_t ldl,
+                                                       int k0, int nb, const int* __restrict__ info) {
+  __shared__ double T[NB * LP];
+  if (*info != 0) return;
+  const double* blk = L + (int64_t)k0 * ldl + k0;
+  for (int e = threadIdx.x; e < NB * NB; e += 256) {
+    const int j = e / NB, k = e % NB;          // consecutive lanes: consecutive k
+    double v = j == k ? 1.0 : 0.0;
+    if (j < nb && k < nb) {
+      if (!BACK && k <= j) v = blk[(int64_t)j * ldl + k];
+      if (BACK && k >= j) v = blk[(int64_t)k * ldl + j];
+    }
+    T[j * LP + k] = v;
+  }
+  __syncthreads();
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= nrows) return;
+  double* row = X + (int64_t)r * ldx + k0;
+  double x[NB];
+  const bool vec = nb == NB && ldx % 2 == 0 && ((uintptr_t)(X + k0) & 15) == 0;
+  if (vec) {
+#pragma unroll
+    for (int k = 0; k < NB; k += 2) {
+      const f64x2 v = *reinterpret_cast<const f64x2*>(row + k);
+      x[k] = v.x; x[k + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) x[k] = k < nb ? row[k] : 0.0;
+  }
+  if (!BACK) {
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      double t = x[j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) t = fma(-x[k], T[j * LP + k], t);
+      x[j] = t / T[j * LP + j];
+    }
+  } else {
+#pragma unroll
+    for (int j = NB - 1; j >= 0; --j) {
+      double t = x[j];
+#pragma unroll
+      for (int k = NB - 1; k > j; --k) t = fma(-x[k], T[j * LP + k], t);
+      x[j] = t / T[j * LP + j];
+    }
+  }
+  if (vec) {
+#pragma unroll
+    for (int k = 0; k < NB; k += 2) {
+      f64x2 v = {x[k], x[k + 1]};
+      *reinterpret_cast<f64x2*>(row + k) = v;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) if (k < nb) row[k] = x[k];
+  }
+}
+
+// ---------------------------------------------------------------- the ridge system and what is read off its solution
+// A[i,j] = G[i,j] - sz[i] sz[j] / N + (i == j) ridge   (ridge = l2_lambda N V, formed on the host in fp64), full square
+__global__ __launch_bounds__(256) void ridge_form_a_kernel(const double* __restrict__ G, const double* __restrict__ sz,
+                                                           double* __restrict__ A, int E, double inv_n, double ridge) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+  if (j >= E) return;
+  double v = G[(int64_t)i * E + j] - sz[i] * sz[j] * inv_n;
+  if (i == j) v += ridge;
+  A[(int64_t)i * E + j] = v;
+}
+// R[v,e] = C[v,e] - sy[v] sz[e] / N
+__global__ __launch_bounds__(256) void ridge_form_r_kernel(const double* __restrict__ C, const double* __restrict__ sz,
+                                                           const double* __restrict__ sy, double* __restrict__ R, int E,
+                                                           double inv_n) {
+  const int e = blockIdx.x * 256 + threadIdx.x, v = blockIdx.y;
+  if (e >= E) return;
+  R[(int64_t)v * E + e] = C[(int64_t)v * E + e] - sy[v] * sz[e] * inv_n;
+}
+// The factorisation sees only the features.  A NaN / Inf target reaches C and sy alone (sy[v] is not finite exactly when
+// column v of y holds one), so it is looked for here: the first such column v is reported as *info = -(v + 1), unless the
+// factorisation has failed already.  One thread, ascending v: the answer does not depend on scheduling.
+__global__ void ridge_check_targets_kernel(const double* __restrict__ sy, int V, int* __restrict__ info) {
+  if (threadIdx.x != 0 || blockIdx.x != 0 || *info != 0) return;
+  for (int v = 0; v < V; ++v)
+    if (!isfinite(sy[v])) {
+      *info = -(v + 1);
+      return;
+    }
+}
+// W[v,:] = fp32(X[v,:]),  b[v] = fp32(sy[v] / N - (X[v,:] . sz) / N): one block per v; the dot product is summed per thread
+// over e = t, t + 256, ... and then over the 256 threads in ascending order (fixed, no atomics).  No-op on *info != 0.
+__global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restrict__ X, const double* __restrict__ sz,
+                                                           const double* __restrict__ sy, float* __restrict__ W,
+                                                           float* __restrict__ b, int E, double inv_n,
+                                                           const int* __restrict__ info) {
+  __shared__ double part[256];
+  if (*info != 0) return;
+  const int v = blockIdx.x;
+  double t = 0.0;
+  for (int e = threadIdx.x; e < E; e += 256) {
+    const double x = X[(int64_t)v * E + e];
+    W[(int64_t)v * E + e] = (float)x;
+    t = fma(x, sz[e], t);
+  }
+  part[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int i = 0; i < 256; ++i) s += part[i];
+    b[v] = (float)(sy[v] * inv_n - s * inv_n);
+  }
+}
+
+inline dim3 tiles(int M, int N) { return dim3((N + TS - 1) / TS, (M + TS - 1) / TS); }
+
+}  // namespace
+
+// ---------------------------------------------------------------- C-ABI
+extern "C" int vlb_ridge_gram_accumulate(const void* z, const float* y, int ldy, double* G, double* C, double* sz, double* sy,
+                                         int n, int E, int V, void* stream) {
+  VLB_REQUIRE(z && y && G && C && sz && sy, "ridge_gram_accumulate: null argument");
+  VLB_REQUIRE(n >= 1 && E >= 1 && V >= 1 && ldy >= V, "ridge_gram_accumulate: bad shape n=%d E=%d V=%d ldy=%d", n, E, V, ldy);
+  hipStream_t st = as_stream(stream);
+  const bf16* zz = (const bf16*)z;
+  hipLaunchKernelGGL(gram_tile_kernel<bf16>, tiles(E, E), dim3(256), 0, st, zz, (int64_t)E, zz, (int64_t)E, G, (int64_t)E, n, E, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gram_tile_kernel<float>, tiles(V, E), dim3(256), 0, st, y, (int64_t)ldy, zz, (int64_t)E, C, (int64_t)E, n, V, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(colsum_f64_kernel<bf16>, dim3((E + 255) / 256), dim3(256), 0, st, zz, (int64_t)E, sz, n, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(colsum_f64_kernel<float>, dim3((V + 255) / 256), dim3(256), 0, st, y, (int64_t)ldy, sy, n, V);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+static int chol_launch(double* A, int n, int64_t lda, int* info, hipStream_t st) {
+  for (int k0 = 0; k0 < n; k0 += NB) {
+    const int nb = n - k0 < NB ? n - k0 : NB, m = n - k0 - nb;          // m > 0 only below a full block
+    hipLaunchKernelGGL(chol_block_kernel, dim3(1), dim3(256), 0, st, A, lda, k0, nb, info);
+    VLB_LAUNCH_CHECK();
+    if (m <= 0) break;
+    double* below = A + (int64_t)(k0 + nb) * lda + k0;                   // A21 -> L21 = A21 L11^-T
+    hipLaunchKernelGGL(tri_rows_kernel<false>, dim3((m + 255) / 256), dim3(256), 0, st, A + (int64_t)(k0 + nb) * lda, lda, m, A, lda,
+                       k0, nb, info);
+    VLB_LAUNCH_CHECK();
+    double* trail = A + (int64_t)(k0 + nb) * lda + (k0 + nb);            // A22 -= L21 L21^T (lower)
+    hipLaunchKernelGGL(tile_sub_f64_kernel<false>, tiles(m, m), dim3(256), 0, st, trail, lda, below, lda, below, lda, m, m, nb, 1, info);
+    VLB_LAUNCH_CHECK();
+  }
+  return VLB_OK;
+}
+
+extern "C" int vlb_chol_f64(double* A, int n, int lda, int* info, void* stream) {
+  VLB_REQUIRE(A && info, "chol_f64: null argument");
+  VLB_REQUIRE(n >= 1 && lda >= n, "chol_f64: bad shape n=%d lda=%d", n, lda);
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(info, 0, sizeof(int), st) != hipSuccess) {
+    vlb_set_error("chol_f64: clearing info failed");
+    return VLB_ERR_LAUNCH;
+  }
+  return chol_launch(A, n, lda, info, st);
+}
+
+extern "C" int vlb_chol_solve_f64(const double* L, int ldl, double* X, int n, int nrhs, int ldx, const int* info, void* stream) {
+  VLB_REQUIRE(L && X && info, "chol_solve_f64: null argument");
+  VLB_REQUIRE(n >= 1 && nrhs >= 1 && ldl >= n && ldx >= n, "chol_solve_f64: bad shape n=%d nrhs=%d ldl=%d ldx=%d", n, nrhs, ldl, ldx);
+  hipStream_t st = as_stream(stream);
+  const dim3 rows((nrhs + 255) / 256);
+  for (int k0 = 0; k0 < n; k0 += NB) {          // L y = r, block column by block column
+    const int nb = n - k0 < NB ? n - k0 : NB, m = n - k0 - nb;
+    hipLaunchKernelGGL(tri_rows_kernel<false>, rows, dim3(256), 0, st, X, (int64_t)ldx, nrhs, L, (int64_t)ldl, k0, nb, info);
+    VLB_LAUNCH_CHECK();
+    if (m > 0) {                                 // X[:, rest] -= X[:, blk] L[rest, blk]^T
+      hipLaunchKernelGGL(tile_sub_f64_kernel<false>, tiles(nrhs, m), dim3(256), 0, st, X + k0 + nb, (int64_t)ldx, X + k0,
+                         (int64_t)ldx, L + (int64_t)(k0 + nb) * ldl + k0, (int64_t)ldl, nrhs, m, nb, 0, info);
+      VLB_LAUNCH_CHECK();
+    }
+  }
+  for (int k0 = (n - 1) / NB * NB; k0 >= 0; k0 -= NB) {   // L^T x = y, from the last block up
+    const int nb = n - k0 < NB ? n - k0 : NB;
+    hipLaunchKernelGGL(tri_rows_kernel<true>, rows, dim3(256), 0, st, X, (int64_t)ldx, nrhs, L, (int64_t)ldl, k0, nb, info);
+    VLB_LAUNCH_CHECK();
+    if (k0 > 0) {                                // X[:, 0..k0) -= X[:, blk] L[blk, 0..k0)
+      hipLaunchKernelGGL(tile_sub_f64_kernel<true>, tiles(nrhs, k0), dim3(256), 0, st, X, (int64_t)ldx, X + k0, (int64_t)ldx,
+                         L + (int64_t)k0 * ldl, (int64_t)ldl, nrhs, k0, nb, 0, info);
+      VLB_LAUNCH_CHECK();
+    }
+  }
+  return VLB_OK;
+}
+
+extern "C" int vlb_ridge_solve(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
+                               double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, void* stream) {
+  VLB_REQUIRE(G && C && sz && sy && A_ws && X_ws && W_out && b_out && info, "ridge_solve: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1 && N >= 1, "ridge_solve: bad shape E=%d V=%d N=%lld", E, V, (long long)N);
+  VLB_REQUIRE(l2_lambda >= 0.0, "ridge_solve: l2_lambda=%g is negative", l2_lambda);
+  const double inv_n = 1.0 / (double)N, ridge = l2_lambda * (double)N * (double)V;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(ridge_form_a_kernel, dim3((E + 255) / 256, E), dim3(256), 0, st, G, sz, A_ws, E, inv_n, ridge);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ridge_form_r_kernel, dim3((E + 255) / 256, V), dim3(256), 0, st, C, sz, sy, X_ws, E, inv_n);
+  VLB_LAUNCH_CHECK();
+  if (int rc = vlb_chol_f64(A_ws, E, E, info, stream)) return rc;
+  hipLaunchKernelGGL(ridge_check_targets_kernel, dim3(1), dim3(64), 0, st, sy, V, info);
+  VLB_LAUNCH_CHECK();
+  if (int rc = vlb_chol_solve_f64(A_ws, E, X_ws, E, V, E, info, stream)) return rc;
+  hipLaunchKernelGGL(ridge_finish_kernel, dim3(V), dim3(256), 0, st, X_ws, sz, sy, W_out, b_out, E, inv_n, info);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}

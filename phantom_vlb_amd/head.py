@@ -453,3 +453,126 @@ class BrainHead:
                  gr["layer_norm1.bias"].data_ptr(), self.ws.data_ptr(), self.dz.data_ptr(),
                  self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self.l2_lambda, float(loss_scale),
                  float(l2_scale), _stream(), *tail), what)
+
+    # ------------------------------------------------------------------ closed-form ridge fit (ridge_fit="closed_form")
+    # With loss="mse", the LN parameters (and the mix) held fixed and dropout off, the objective over N clips is a ridge
+    # regression in (ridge_layer.linear.weight, .bias); DESIGN §5.3.5.  ridge_stats_begin(); ridge_stats_add(...) per chunk of
+    # cached clips; ridge_solve() -> the minimiser, written into the fp32 masters and their bf16 copies.  All fp64 on the device.
+    def ridge_stats_begin(self):
+        """Allocate and zero the fp64 sums (G [E,E], C [V,E], sz [E], sy [V]), one set per head."""
+        if self.loss != "mse":
+            raise ValueError(f"head: the closed-form ridge fit minimises the mse objective; this head has loss={self.loss!r}")
+        H, E, V, d, f64 = max(1, self.G), self.E, self.V, self.dev, torch.float64
+        self._ridge = {"G": torch.zeros(H, E, E, dtype=f64, device=d), "C": torch.zeros(H, V, E, dtype=f64, device=d),
+                       "sz": torch.zeros(H, E, dtype=f64, device=d), "sy": torch.zeros(H, V, dtype=f64, device=d), "n": [0] * H}
+
+    def ridge_stats_end(self):
+        """Free the sums (and the last solve's workspaces)."""
+        self._ridge = None
+
+    def features_cached(self, cache, indices):
+        """z bf16 [n,E] of the cached clips ``indices``: what the ridge layer reads in ``forward_cached`` with
+        ``keep_scale=None`` (same gather, same mix, same LN2 launch: the same bits), and nothing after it.  The tensor is the
+        head's own ``z`` buffer: the next call overwrites it."""
+        rows = cache.rows(indices)
+        B = rows.numel()
+        c = self.compute
+        if self.K:
+            if cache.layers != self.K:
+                raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for {self.K} tapped layer(s)")
+            self.begin(B, self._cap[1] if self._cap is not None and self._cap[0] == B else 1)
+            for k in range(self.K):
+                check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
+                                                   self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
+                                                   _stream()), "vlb_feature_cache_gather")
+            check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), c[LAYER_MIX].data_ptr() if self.K > 1 else None,
+                                       self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
+                  "vlb_head_mix_fwd")
+            src, sw, rows, n_rows = self.mixed, self.tap_sumw, self.identity_rows, B
+        else:
+            if cache.layers is not None:
+                raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for a head without readout_layers")
+            if self._cap is None or self._cap[0] != B:
+                self._buffers(B, 1)
+            src, sw, n_rows = cache.pooled, cache.sumw, cache.n
+        check(lib.vlb_head_features_cached(src.data_ptr(), sw.data_ptr(), rows.data_ptr(), c["layer_norm1.weight"].data_ptr(),
+                                           c["layer_norm1.bias"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                                           c["layer_norm2.bias"].data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
+                                           self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), B, self.E, n_rows,
+                                           self.eps, _stream()), "vlb_head_features_cached")
+        return self.z
+
+    def ridge_stats_add(self, cache, indices, y, subject=None):
+        """Add a chunk of cached clips (``indices``: host int64 [n]; ``y`` fp32 [n,V] on the device; ``subject``: one head
+        index per clip for a head built with ``subjects``) to the sums.  Checked on the host like ``forward_cached``; with
+        ``subjects`` the chunk is partitioned on the host and each part goes to its own head's sums, in index order."""
+        st = getattr(self, "_ridge", None)
+        if st is None:
+            raise RuntimeError("head: ridge_stats_add() before ridge_stats_begin()")
+        idx = torch.as_tensor(indices).detach().cpu().flatten().to(torch.int64)
+        n = idx.numel()
+        if y.dim() != 2 or tuple(y.shape) != (n, self.V) or y.dtype != torch.float32 or y.device.type != torch.device(self.dev).type:
+            raise ValueError(f"head: ridge_stats_add needs y fp32 [{n},{self.V}] on {self.dev}, got {y.dtype} {tuple(y.shape)} on {y.device}")
+        group = self._group(subject, n)
+        if group is None:
+            parts = [(0, idx, y.contiguous())]
+        else:
+            g_host = torch.as_tensor(subject).detach().cpu().flatten().to(torch.int64)
+            parts = []
+            for g in range(self.G):
+                sel = torch.nonzero(g_host == g).flatten()
+                if sel.numel():
+                    parts.append((g, idx[sel], y.index_select(0, sel.to(y.device)).contiguous()))
+        for g, ids, yy in parts:
+            z = self.features_cached(cache, ids)
+            m = ids.numel()
+            check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), yy.data_ptr(), self.V, st["G"][g].data_ptr(), st["C"][g].data_ptr(),
+                                                st["sz"][g].data_ptr(), st["sy"][g].data_ptr(), m, self.E, self.V, _stream()),
+                  "vlb_ridge_gram_accumulate")
+            st["n"][g] += m
+
+    def ridge_solve(self, l2_lambda=None):
+        """Minimise the mse objective over the accumulated clips in (weight, bias), per head: one fp64 Cholesky factorisation
+        and solve each.  -> a list (one entry per head) of {"subject", "n", "info", "l2_lambda"}.  Everything is solved
+        first; a head without clips, a singular system (``l2_lambda`` 0 with n <= E) or a failed pivot (``info`` != 0) raises
+        with the head and the pivot named and leaves every parameter as it was.  Otherwise the fp32 masters and their bf16
+        copies are written.  The sums are only read: another ``l2_lambda`` solves again from them."""
+        st = getattr(self, "_ridge", None)
+        if st is None:
+            raise RuntimeError("head: ridge_solve() before ridge_stats_begin()")
+        lam = self.l2_lambda if l2_lambda is None else float(l2_lambda)
+        H, E, V, d = max(1, self.G), self.E, self.V, self.dev
+        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        if lam < 0:
+            raise ValueError(f"head: ridge_solve: l2_lambda = {lam} is negative")
+        for g in range(H):
+            if st["n"][g] == 0:
+                raise ValueError(f"head: ridge_solve: {name(g)} has no clips (N = 0): nothing to fit it to")
+            if not lam > 0 and st["n"][g] <= E:
+                raise ValueError(f"head: ridge_solve: {name(g)} has N = {st['n'][g]} <= E = {E} clips and l2_lambda = {lam}: the "
+                                 "centred Gram matrix is singular; set l2_lambda > 0")
+        A = torch.empty(E, E, dtype=torch.float64, device=d)
+        X = torch.empty(H, V, E, dtype=torch.float64, device=d)
+        W = torch.empty(H, V, E, dtype=torch.float32, device=d)
+        b = torch.empty(H, V, dtype=torch.float32, device=d)
+        info = torch.zeros(H, dtype=torch.int32, device=d)
+        for g in range(H):
+            check(lib.vlb_ridge_solve(st["G"][g].data_ptr(), st["C"][g].data_ptr(), st["sz"][g].data_ptr(), st["sy"][g].data_ptr(),
+                                      st["n"][g], lam, A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(), b[g].data_ptr(),
+                                      info[g:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
+        infos = info.tolist()                           # the one device read of the solve
+        st["X"] = X                                     # the fp64 solutions, for inspection
+        for g in range(H):
+            if infos[g] < 0:
+                raise ValueError(f"head: ridge_solve: {name(g)}: target column {-infos[g] - 1} holds a NaN or Inf (info = "
+                                 f"{infos[g]}, N = {st['n'][g]}); the parameters are unchanged")
+            if infos[g]:
+                raise ValueError(f"head: ridge_solve: {name(g)}: pivot {infos[g]} of {E} is not positive (info = {infos[g]}, "
+                                 f"N = {st['n'][g]}, l2_lambda = {lam}): a larger l2_lambda, or NaN in the targets")
+        wn, bn = "ridge_layer.linear.weight", "ridge_layer.linear.bias"
+        self.master[wn].copy_(W.view(self.master[wn].shape))
+        self.master[bn].copy_(b.view(self.master[bn].shape))
+        self.compute[wn].copy_(self.master[wn])         # fp32 -> bf16, round to nearest even: what AdamW's rewrite gives too
+        self.compute[bn].copy_(self.master[bn])
+        return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": infos[g], "l2_lambda": lam}
+                for g in range(H)]

@@ -174,6 +174,10 @@ class VLBLitModuleConfig:
     # two or more subject names: one backbone (and adapter set), one ridge head per subject (``ridge_layer.linear.weight``
     # [G,V,E]); every batch then carries "subject" (datamodule.config.subjects, the same list).  None: one head, as the reference
     subjects: list[str] | None = None
+    # "closed_form": once the train split's feature cache is complete, ridge_layer.linear.{weight,bias} are set to the exact
+    # minimiser of the mse objective for the current LN parameters (dropout not included), fp64 on the device;
+    # training then goes on as configured.  None: AdamW finds them, as the reference
+    ridge_fit: str | None = None
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -184,6 +188,18 @@ class VLBLitModuleConfig:
         if self.merge_lora_for_eval and not self.use_lora:
             raise ValueError("merge_lora_for_eval=True needs use_lora=True: without adapters there is nothing to merge")
         check_loss(self.loss, self.num_target)
+        if self.ridge_fit is not None:
+            if self.ridge_fit != "closed_form":
+                raise ValueError(f"ridge_fit={self.ridge_fit!r}: expected None or 'closed_form'")
+            if not self.cache_features:
+                raise ValueError("ridge_fit='closed_form' reads the train split's frozen-feature cache: set cache_features=True "
+                                 "(with freeze_backbone=True, use_lora=False)")
+            if self.loss != "mse":
+                raise ValueError(f"ridge_fit='closed_form' minimises the mse objective, loss={self.loss!r} has no closed form: "
+                                 "set loss='mse' (or ridge_fit=None)")
+            if not self.l2_lambda > 0:
+                raise ValueError(f"ridge_fit='closed_form' needs l2_lambda > 0 (got {self.l2_lambda}): with fewer clips than "
+                                 "features the system is singular without the penalty; set l2_lambda to a positive value")
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
@@ -562,6 +578,70 @@ class VLBLitModule(_Base):
             fps[split] = fingerprint(cfg, ds)
             if cfg.feature_cache_dir and not c.complete():
                 c.load(cfg.feature_cache_dir, fps[split])
+        if cfg.ridge_fit is not None and train_dataset is not None:
+            self._ridge_fit_dataset, self._ridge_fit_done = train_dataset, False
+            self._maybe_fit_ridge()            # a persisted cache is complete already: the fit precedes the first step
+
+    def _maybe_fit_ridge(self) -> None:
+        """ridge_fit="closed_form": run the fit once per fit, the first time the train split's cache is complete."""
+        if self.config.ridge_fit is None or self.__dict__.get("_ridge_fit_done", True):
+            return
+        c = self.feature_caches.get("train")
+        if c is None or not c.complete():
+            return
+        self._ridge_fit_done = True
+        self.fit_ridge_closed_form(self._ridge_fit_dataset)
+
+    def fit_ridge_closed_form(self, dataset=None, l2_lambda=None, chunk: int = 512) -> list:
+        """Set ``ridge_layer.linear.{weight,bias}`` to the minimiser of the mse objective over the train split, for the LN
+        parameters (and the layer mix) as they are now and without dropout: walk ``dataset`` (default: the
+        train dataset) in ``features_only`` mode in index order, ``chunk`` clips at a time, accumulate the fp64 sums from the
+        cached features, solve per head, write the fp32 masters (wherever they live) and their bf16 copies, and zero AdamW's
+        moments of exactly these two tensors.  Logs ``ridge_fit/n``, ``ridge_fit/l2_lambda`` and the first chunk's
+        ``ridge_fit/train_mse_before`` / ``_after`` (the existing cached forward).  -> ``BrainHead.ridge_solve``'s list."""
+        cfg = self.config
+        if not cfg.cache_features or cfg.loss != "mse":
+            raise ValueError("fit_ridge_closed_form needs cache_features=True and loss='mse'")
+        cache = self.feature_caches.get("train")
+        if cache is None or not cache.complete():
+            raise RuntimeError("fit_ridge_closed_form: the train split's feature cache is not complete yet (it fills during "
+                               "the first epoch, or loads from feature_cache_dir)")
+        ds = dataset if dataset is not None else self.__dict__.get("_ridge_fit_dataset") or self._datamodule_dataset("train")
+        if ds is None or len(ds) != cache.n:
+            raise ValueError(f"fit_ridge_closed_form: a dataset of {None if ds is None else len(ds)} clips for a cache of {cache.n}")
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"fit_ridge_closed_form: chunk={chunk}")
+        subjects = getattr(cfg, "subjects", None)
+        was = ds.features_only
+        ds.features_only = True            # an item is {"index", "timeseries"[, "subject"]}: nothing else is read
+        first = mse = None
+        try:
+            self.head.ridge_stats_begin()
+            for lo in range(0, len(ds), chunk):
+                items = [ds[i] for i in range(lo, min(lo + chunk, len(ds)))]
+                batch = {k: torch.stack([torch.as_tensor(it[k]) for it in items]) for k in items[0]}
+                subject = check_batch_subjects(batch, subjects, len(items))
+                # the targets as every step sees them (reference :288: through bf16)
+                y = batch["timeseries"].to(self.device, torch.float32).to(torch.bfloat16).float().contiguous()
+                if first is None:
+                    first = (batch["index"], y, subject)
+                    mse = [float(self.head.forward_cached(cache, *first[:2], None, subject)[1][0])]
+                self.head.ridge_stats_add(cache, batch["index"], y, subject)
+            out = self.head.ridge_solve(cfg.l2_lambda if l2_lambda is None else l2_lambda)
+        finally:
+            ds.features_only = was
+            self.head.ridge_stats_end()
+        opt = getattr(self, "optimizer", None)
+        if opt is not None:
+            opt.reset_moments(["ridge_layer.linear.weight", "ridge_layer.linear.bias"])
+        mse.append(float(self.head.forward_cached(cache, first[0], first[1], None, first[2])[1][0]))
+        self.log("ridge_fit/n", float(sum(o["n"] for o in out)))
+        self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]))
+        self.log("ridge_fit/train_mse_before", mse[0])
+        self.log("ridge_fit/train_mse_after", mse[1])
+        self.ridge_fit_result = out
+        return out
 
     def feature_cache_begin(self, split: str, dataset=None) -> None:
         """Start of a training epoch / validation pass: a split whose cache is complete stops loading anything but the
@@ -580,6 +660,8 @@ class VLBLitModule(_Base):
         rate = None if c is None else c.hit_rate()
         if rate is not None:
             self.log(f"feature_cache/{split}_hit_rate", rate)
+        if split == "train" and self.config.ridge_fit is not None:
+            self._maybe_fit_ridge()            # the epoch that completed the train cache ends with the closed-form fit
         return rate
 
     def _datamodule_dataset(self, split):

@@ -88,6 +88,20 @@ class VlbAdamW(torch.optim.Optimizer):
             for a in range(0, f.numel, chunk):
                 f.compute[a:a + chunk].copy_(f.master[a:a + chunk])
 
+    def reset_moments(self, names):
+        """Zero both Adam moments of the named tensors of the head (+ LoRA) store - after their masters were set by something
+        other than an AdamW step (the closed-form ridge fit): the history of the values they replaced says
+        nothing about the new ones.  The bias-correction step count is left alone.  Single process only."""
+        f = self.flats[0]
+        if self.shardeds[0] is not None and self.shardeds[0].active:
+            raise RuntimeError("VlbAdamW.reset_moments: the moments are sharded over ranks (data parallelism); not supported")
+        for n in names:
+            if n not in f.offsets:
+                raise KeyError(f"VlbAdamW.reset_moments: {n!r} is not a tensor of the flat store ({sorted(f.offsets)[:6]} ...)")
+            o, k, _ = f.offsets[n]
+            f.m[o:o + k].zero_()
+            f.v[o:o + k].zero_()
+
     # ------------------------------------------------------------------ checkpoint surface (torch.optim.Optimizer)
     def state_dict(self):
         """``torch.optim`` layout (``state`` / ``param_groups``) plus ``vlb``: the bias-correction step count and, per flat
