@@ -626,6 +626,29 @@ int vlb_chol_solve_f64(const double* L, int ldl, double* X, int n, int nrhs, int
 int vlb_ridge_solve(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
                     double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, void* stream);
 
+/* Choosing l2_lambda for the closed-form fit by blocked K-fold cross-validation (opt-in, ridge_lambda_grid; DESIGN 5.3.6;
+ * every entry point above keeps its bits).  The fp64 sums are kept per fold k: S_k = (G_k, C_k, sz_k, sy_k, n_k) and
+ * syy_k [V] = sum y^2.  Fold k's training sums are T_k = sum_{j != k} S_j and go through vlb_ridge_solve unchanged (N = N - n_k);
+ * the held-out Pearson correlation of target v follows from S_k and the solution X [V,E] alone:
+ *   Gc = G_k - sz_k sz_k^T / n_k,  Rc = C_k - sy_k sz_k^T / n_k,  vy[v] = syy_k[v] - sy_k[v]^2 / n_k,
+ *   cov = X[v,:] . Rc[v,:],  vp = X[v,:] Gc X[v,:]^T,  r[v] = cov / sqrt(vp vy) clipped to [-1, 1], 0 unless vp > 0 and vy > 0.
+ * fp64, no atomics, one owner and one summation order per output element; a non-zero *info makes the scoring a no-op.
+ * vlb_ridge_sumsq_accumulate (src/utils.py:59-73: the layer's targets): syy [V] += sum over the n rows of (double)y[r,v]^2;
+ *   y fp32 [n,V] with pitch ldy.  The caller zeroes syy before the first chunk.
+ * vlb_f64_sum_except (src/utils.py:59-73: the folds' training sums): out[i] = sum over j != skip, ascending, of
+ *   parts[j * stride + i] for i < numel; count parts, skip in [-1, count) (-1: all of them).
+ * vlb_ridge_cv_center (src/utils.py:59-73: the held-out moments): Gc [E,E], Rc [V,E], vy [V] as above, once per fold.
+ * vlb_ridge_cv_score (src/utils.py:59-73: the layer's prediction, never formed): r_out [V] as above from the solution X that
+ *   vlb_ridge_solve left in X_ws.  The tile T = X Gc stays in registers: one partial of vp per (target, 64-column tile) goes to
+ *   ws (vlb_ridge_cv_ws_doubles(E, V) doubles) and is summed in ascending order.  info: the solve's (read only). */
+int vlb_ridge_sumsq_accumulate(const float* y, int ldy, double* syy, int n, int V, void* stream);
+int vlb_f64_sum_except(const double* parts, int64_t stride, int count, int skip, double* out, int64_t numel, void* stream);
+int vlb_ridge_cv_center(const double* G_k, const double* C_k, const double* sz_k, const double* sy_k, const double* syy_k,
+                        int64_t n_k, double* Gc, double* Rc, double* vy, int E, int V, void* stream);
+int64_t vlb_ridge_cv_ws_doubles(int E, int V);
+int vlb_ridge_cv_score(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws, double* r_out,
+                       const int* info, int E, int V, void* stream);
+
 /* head dropout mask (litmodule :226,251 nn.Dropout(p) in training): out[i] = keep_i / (1-p), keep_i from a
  * counter-based hash of (seed, i) with 16 random bits per element (same mixer as the LoRA masks).  The result is
  * what vlb_head_fwd / vlb_head_bwd take as `keep_scale`. */

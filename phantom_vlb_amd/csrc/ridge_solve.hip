@@ -351,6 +351,138 @@ __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restr
   }
 }
 
+// ---------------------------------------------------------------- blocked K-fold CV of l2_lambda
+// s[c] += sum over the n rows (ascending) of y[r, c]^2: colsum_f64_kernel's twin (an fp32 square is exact in fp64)
+__global__ __launch_bounds__(256) void colsumsq_f64_kernel(const float* __restrict__ y, int64_t ld, double* __restrict__ s, int n,
+                                                           int ncols) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  double t = 0.0;
+  for (int r = 0; r < n; ++r) {
+    const double w = widen(y[(int64_t)r * ld + c]);
+    t = fma(w, w, t);
+  }
+  s[c] += t;
+}
+// out[i] = sum over j != skip (ascending) of parts[j * stride + i]: one thread per element, lanes on consecutive elements
+__global__ __launch_bounds__(256) void sum_except_f64_kernel(const double* __restrict__ parts, int64_t stride, int count, int skip,
+                                                             double* __restrict__ out, int64_t numel) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= numel) return;
+  double t = 0.0;
+  for (int j = 0; j < count; ++j)
+    if (j != skip) t += parts[(int64_t)j * stride + i];
+  out[i] = t;
+}
+// vy[v] = syy[v] - sy[v]^2 / n
+__global__ __launch_bounds__(256) void cv_vy_kernel(const double* __restrict__ syy, const double* __restrict__ sy,
+                                                    double* __restrict__ vy, int V, double inv_n) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v < V) vy[v] = syy[v] - sy[v] * sy[v] * inv_n;
+}
+// The quadratic form vp[v] = X[v,:] Gc X[v,:]^T, one partial per (target, 64-column tile):
+//   ws[v * nct + c] = sum_{j in tile c} (sum_k X[v,k] Gc[k,j]) X[v,j],   nct = ceil(E / 64)
+// tile_sub_f64_kernel<QT>'s loop (P = X rows, Q = Gc k-major; the same staging, the same 65-double pitch, the same 16-lane
+// reads), but the 64 x 64 tile of T = X Gc stays in the accumulators: each is multiplied by X[v,j], a thread adds its four
+// columns tx, tx + 16, tx + 32, tx + 48 in that order, and one thread per target adds the 16 lanes' sums in ascending tx
+// (LDS, pitch 17: 32 lanes on 32 different bank pairs).  grid (nct, ceil(V/64)), 256 threads.  No-op on *info != 0.
+__global__ __launch_bounds__(256) void cv_quad_tile_kernel(const double* __restrict__ X, const double* __restrict__ Gc,
+                                                           double* __restrict__ ws, int E, int V, const int* __restrict__ info) {
+  __shared__ double Ps[FK * LP];
+  __shared__ double Qs[FK * LP];
+  __shared__ double red[TS * 17];
+  if (*info != 0) return;
+  const int i0 = blockIdx.y * TS, j0 = blockIdx.x * TS;
+  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+  double acc[4][4] = {};
+  const bool pvec = E % 2 == 0 && ((uintptr_t)X & 15) == 0;
+  for (int kc = 0; kc < E; kc += FK) {
+    __syncthreads();
+    {   // rows of X: lane t -> row t / 4, k-quad t % 4
+      const int r = threadIdx.x >> 2, kq = (threadIdx.x & 3) * 4, k = kc + kq;
+      double v[4] = {0.0, 0.0, 0.0, 0.0};
+      if (i0 + r < V) {
+        const double* p = X + (int64_t)(i0 + r) * E + k;
+        if (pvec && k + 4 <= E) {
+          const f64x2 lo = reinterpret_cast<const f64x2*>(p)[0], hi = reinterpret_cast<const f64x2*>(p)[1];
+          v[0] = lo.x; v[1] = lo.y; v[2] = hi.x; v[3] = hi.y;
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) if (k + i < E) v[i] = p[i];
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) Ps[(kq + i) * LP + r] = v[i];
+      // Gc is k-major already: lane t -> k t / 16, columns t % 16 + 16 i (128 contiguous bytes per 16 lanes)
+      const int kk = threadIdx.x >> 4;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = tx + 16 * i;
+        Qs[kk * LP + j] = (kc + kk < E && j0 + j < E) ? Gc[(int64_t)(kc + kk) * E + j0 + j] : 0.0;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < FK; ++k) {
+      double a[4], b[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = Ps[k * LP + ty + 16 * i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) b[j] = Qs[k * LP + tx + 16 * j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = fma(a[i], b[j], acc[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = i0 + ty + 16 * i;
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int col = j0 + tx + 16 * j;
+      const double x = (row < V && col < E) ? X[(int64_t)row * E + col] : 0.0;
+      t = fma(acc[i][j], x, t);
+    }
+    red[(ty + 16 * i) * 17 + tx] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < TS && i0 + threadIdx.x < V) {
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) s += red[threadIdx.x * 17 + t];
+    ws[(int64_t)(i0 + threadIdx.x) * gridDim.x + blockIdx.x] = s;
+  }
+}
+// r[v] = cov / sqrt(vp vy) clipped to [-1, 1], 0 unless vp > 0 and vy > 0:  vp = the nct partials of ws in ascending order,
+// cov = X[v,:] . Rc[v,:] summed as ridge_finish_kernel sums (per thread over e = t, t + 256, ..., then the 256 threads in
+// ascending order).  One block per v.  No-op on *info != 0.
+__global__ __launch_bounds__(256) void cv_finish_kernel(const double* __restrict__ X, const double* __restrict__ Rc,
+                                                        const double* __restrict__ vy, const double* __restrict__ ws,
+                                                        double* __restrict__ r_out, int E, int nct,
+                                                        const int* __restrict__ info) {
+  __shared__ double part[256];
+  if (*info != 0) return;
+  const int v = blockIdx.x;
+  double t = 0.0;
+  for (int e = threadIdx.x; e < E; e += 256) t = fma(X[(int64_t)v * E + e], Rc[(int64_t)v * E + e], t);
+  part[threadIdx.x] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double cov = 0.0, vp = 0.0;
+    for (int i = 0; i < 256; ++i) cov += part[i];
+    for (int c = 0; c < nct; ++c) vp += ws[(int64_t)v * nct + c];
+    const double y2 = vy[v];
+    double r = 0.0;
+    if (vp > 0.0 && y2 > 0.0) {
+      r = cov / sqrt(vp * y2);
+      r = r > 1.0 ? 1.0 : r < -1.0 ? -1.0 : r;
+    }
+    r_out[v] = r;
+  }
+}
+
 inline dim3 tiles(int M, int N) { return dim3((N + TS - 1) / TS, (M + TS - 1) / TS); }
 
 }  // namespace
@@ -445,6 +577,60 @@ extern "C" int vlb_ridge_solve(const double* G, const double* C, const double* s
   VLB_LAUNCH_CHECK();
   if (int rc = vlb_chol_solve_f64(A_ws, E, X_ws, E, V, E, info, stream)) return rc;
   hipLaunchKernelGGL(ridge_finish_kernel, dim3(V), dim3(256), 0, st, X_ws, sz, sy, W_out, b_out, E, inv_n, info);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// ---------------------------------------------------------------- C-ABI: blocked K-fold CV of l2_lambda
+extern "C" int vlb_ridge_sumsq_accumulate(const float* y, int ldy, double* syy, int n, int V, void* stream) {
+  VLB_REQUIRE(y && syy, "ridge_sumsq_accumulate: null argument");
+  VLB_REQUIRE(n >= 1 && V >= 1 && ldy >= V, "ridge_sumsq_accumulate: bad shape n=%d V=%d ldy=%d", n, V, ldy);
+  hipLaunchKernelGGL(colsumsq_f64_kernel, dim3((V + 255) / 256), dim3(256), 0, as_stream(stream), y, (int64_t)ldy, syy, n, V);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_f64_sum_except(const double* parts, int64_t stride, int count, int skip, double* out, int64_t numel,
+                                  void* stream) {
+  VLB_REQUIRE(parts && out, "f64_sum_except: null argument");
+  VLB_REQUIRE(count >= 1 && skip >= -1 && skip < count && numel >= 1 && stride >= numel && numel <= ((int64_t)1 << 38),
+              "f64_sum_except: bad shape count=%d skip=%d numel=%lld stride=%lld", count, skip, (long long)numel, (long long)stride);
+  hipLaunchKernelGGL(sum_except_f64_kernel, dim3((unsigned)((numel + 255) / 256)), dim3(256), 0, as_stream(stream), parts, stride,
+                     count, skip, out, numel);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_ridge_cv_center(const double* G_k, const double* C_k, const double* sz_k, const double* sy_k,
+                                   const double* syy_k, int64_t n_k, double* Gc, double* Rc, double* vy, int E, int V,
+                                   void* stream) {
+  VLB_REQUIRE(G_k && C_k && sz_k && sy_k && syy_k && Gc && Rc && vy, "ridge_cv_center: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1 && n_k >= 1, "ridge_cv_center: bad shape E=%d V=%d n_k=%lld", E, V, (long long)n_k);
+  const double inv_n = 1.0 / (double)n_k;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(ridge_form_a_kernel, dim3((E + 255) / 256, E), dim3(256), 0, st, G_k, sz_k, Gc, E, inv_n, 0.0);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ridge_form_r_kernel, dim3((E + 255) / 256, V), dim3(256), 0, st, C_k, sz_k, sy_k, Rc, E, inv_n);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cv_vy_kernel, dim3((V + 255) / 256), dim3(256), 0, st, syy_k, sy_k, vy, V, inv_n);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int64_t vlb_ridge_cv_ws_doubles(int E, int V) {
+  if (E < 1 || V < 1) return 0;
+  return (int64_t)V * ((E + TS - 1) / TS);
+}
+
+extern "C" int vlb_ridge_cv_score(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws, double* r_out,
+                                  const int* info, int E, int V, void* stream) {
+  VLB_REQUIRE(X && Gc && Rc && vy && ws && r_out && info, "ridge_cv_score: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1, "ridge_cv_score: bad shape E=%d V=%d", E, V);
+  hipStream_t st = as_stream(stream);
+  const int nct = (E + TS - 1) / TS;
+  hipLaunchKernelGGL(cv_quad_tile_kernel, tiles(V, E), dim3(256), 0, st, X, Gc, ws, E, V, info);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cv_finish_kernel, dim3(V), dim3(256), 0, st, X, Rc, vy, ws, r_out, E, nct, info);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }

@@ -458,11 +458,22 @@ class BrainHead:
     # With loss="mse", the LN parameters (and the mix) held fixed and dropout off, the objective over N clips is a ridge
     # regression in (ridge_layer.linear.weight, .bias); DESIGN §5.3.5.  ridge_stats_begin(); ridge_stats_add(...) per chunk of
     # cached clips; ridge_solve() -> the minimiser, written into the fp32 masters and their bf16 copies.  All fp64 on the device.
-    def ridge_stats_begin(self):
-        """Allocate and zero the fp64 sums (G [E,E], C [V,E], sz [E], sy [V]), one set per head."""
+    def ridge_stats_begin(self, folds=None, block=None):
+        """Allocate and zero the fp64 sums (G [E,E], C [V,E], sz [E], sy [V]), one set per head.  ``folds=K`` (with
+        ``block``): one set per (head, fold) plus syy [V] = sum y^2, for ``ridge_cv``; a head's m-th clip
+        (its rank among the clips that head has received so far) goes to fold ``(m // block) % K``."""
         if self.loss != "mse":
             raise ValueError(f"head: the closed-form ridge fit minimises the mse objective; this head has loss={self.loss!r}")
         H, E, V, d, f64 = max(1, self.G), self.E, self.V, self.dev, torch.float64
+        if folds is not None:
+            K, blk = int(folds), 1 if block is None else int(block)
+            if K < 2 or blk < 1:
+                raise ValueError(f"head: ridge_stats_begin: folds={folds}, block={block}: folds >= 2 and block >= 1 are needed")
+            self._ridge = {"G": torch.zeros(H, K, E, E, dtype=f64, device=d), "C": torch.zeros(H, K, V, E, dtype=f64, device=d),
+                           "sz": torch.zeros(H, K, E, dtype=f64, device=d), "sy": torch.zeros(H, K, V, dtype=f64, device=d),
+                           "syy": torch.zeros(H, K, V, dtype=f64, device=d), "n": [0] * H, "n_fold": [[0] * K for _ in range(H)],
+                           "folds": K, "block": blk}
+            return
         self._ridge = {"G": torch.zeros(H, E, E, dtype=f64, device=d), "C": torch.zeros(H, V, E, dtype=f64, device=d),
                        "sz": torch.zeros(H, E, dtype=f64, device=d), "sy": torch.zeros(H, V, dtype=f64, device=d), "n": [0] * H}
 
@@ -523,6 +534,8 @@ class BrainHead:
                 sel = torch.nonzero(g_host == g).flatten()
                 if sel.numel():
                     parts.append((g, idx[sel], y.index_select(0, sel.to(y.device)).contiguous()))
+        if "folds" in st:
+            return self._ridge_stats_add_folds(st, cache, parts)
         for g, ids, yy in parts:
             z = self.features_cached(cache, ids)
             m = ids.numel()
@@ -536,7 +549,8 @@ class BrainHead:
         and solve each.  -> a list (one entry per head) of {"subject", "n", "info", "l2_lambda"}.  Everything is solved
         first; a head without clips, a singular system (``l2_lambda`` 0 with n <= E) or a failed pivot (``info`` != 0) raises
         with the head and the pivot named and leaves every parameter as it was.  Otherwise the fp32 masters and their bf16
-        copies are written.  The sums are only read: another ``l2_lambda`` solves again from them."""
+        copies are written.  The sums are only read: another ``l2_lambda`` solves again from them.  With folds active the
+        head's sums are its folds' added in ascending order."""
         st = getattr(self, "_ridge", None)
         if st is None:
             raise RuntimeError("head: ridge_solve() before ridge_stats_begin()")
@@ -557,7 +571,9 @@ class BrainHead:
         b = torch.empty(H, V, dtype=torch.float32, device=d)
         info = torch.zeros(H, dtype=torch.int32, device=d)
         for g in range(H):
-            check(lib.vlb_ridge_solve(st["G"][g].data_ptr(), st["C"][g].data_ptr(), st["sz"][g].data_ptr(), st["sy"][g].data_ptr(),
+            # with folds the head's totals are the folds' sums added in ascending order (skip = -1)
+            Gs, Cs, szs, sys_ = self._ridge_fold_sums(st, g, -1) if "folds" in st else (st["G"][g], st["C"][g], st["sz"][g], st["sy"][g])
+            check(lib.vlb_ridge_solve(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(),
                                       st["n"][g], lam, A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(), b[g].data_ptr(),
                                       info[g:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
         infos = info.tolist()                           # the one device read of the solve
@@ -576,3 +592,108 @@ class BrainHead:
         self.compute[bn].copy_(self.master[bn])
         return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": infos[g], "l2_lambda": lam}
                 for g in range(H)]
+
+    # ------------------------------------------------------------------ l2_lambda by blocked K-fold CV (ridge_lambda_grid)
+    # DESIGN §5.3.6.  ridge_stats_begin(folds=K, block=b) keeps the sums per (head, fold); ridge_cv(grid) solves every fold's
+    # training sums T_k = sum_{j != k} S_j for every lambda and scores the held-out fold from S_k's moments alone.
+    def _ridge_stats_add_folds(self, st, cache, parts):
+        """``ridge_stats_add`` with folds: each head's part of the chunk is partitioned on the host once more, by fold."""
+        K, blk = st["folds"], st["block"]
+        for g, ids, yy in parts:
+            m = ids.numel()
+            fold = (torch.arange(st["n"][g], st["n"][g] + m, dtype=torch.int64) // blk) % K
+            for k in range(K):
+                sel = torch.nonzero(fold == k).flatten()
+                mk = sel.numel()
+                if not mk:
+                    continue
+                yk = yy if mk == m else yy.index_select(0, sel.to(yy.device)).contiguous()
+                z = self.features_cached(cache, ids[sel])
+                check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), yk.data_ptr(), self.V, st["G"][g, k].data_ptr(),
+                                                    st["C"][g, k].data_ptr(), st["sz"][g, k].data_ptr(), st["sy"][g, k].data_ptr(),
+                                                    mk, self.E, self.V, _stream()), "vlb_ridge_gram_accumulate")
+                check(lib.vlb_ridge_sumsq_accumulate(yk.data_ptr(), self.V, st["syy"][g, k].data_ptr(), mk, self.V, _stream()),
+                      "vlb_ridge_sumsq_accumulate")
+                st["n_fold"][g][k] += mk
+            st["n"][g] += m
+
+    def _ridge_fold_sums(self, st, g, skip):
+        """(G, C, sz, sy) of head g summed over its folds but ``skip`` (-1: none), in ascending fold order, into the shared
+        buffers st["T"] (the next call overwrites them; everything runs on one stream)."""
+        K, E, V = st["folds"], self.E, self.V
+        T = st.get("T")
+        if T is None:
+            f64, d = torch.float64, self.dev
+            T = st["T"] = (torch.empty(E, E, dtype=f64, device=d), torch.empty(V, E, dtype=f64, device=d),
+                           torch.empty(E, dtype=f64, device=d), torch.empty(V, dtype=f64, device=d))
+        for name, out in zip(("G", "C", "sz", "sy"), T):
+            check(lib.vlb_f64_sum_except(st[name][g].data_ptr(), out.numel(), K, int(skip), out.data_ptr(), out.numel(), _stream()),
+                  "vlb_f64_sum_except")
+        return T
+
+    def ridge_cv(self, grid):
+        """Blocked K-fold cross-validation of ``l2_lambda`` over ``grid`` from the per-fold sums: for every head g, fold k and
+        grid point i the training sums T_k are solved (vlb_ridge_solve, N = N_g - n_gk) and the held-out fold is scored
+        (vlb_ridge_cv_score) into an fp64 table [H,K,L,V] pre-filled with NaN.  Everything is queued without a host sync; the
+        [H,K,L] infos and the table's target means are read once at the end.  The score of a grid point is the mean over heads
+        and folds of the mean over targets of r; a grid point with any failed solve is excluded (a warning names it); the
+        largest score wins and an exact tie goes to the larger lambda.  A (head, fold) with fewer than 2 clips, or every grid
+        point excluded, raises.  The parameters are never written.  -> {"grid", "score" [L], "score_per_head" [H,L],
+        "best_index", "best_lambda", "r" [H,L,V] (fold mean, on the device), "infos" [H][K][L]}."""
+        import warnings
+        st = getattr(self, "_ridge", None)
+        if st is None or "folds" not in st:
+            raise RuntimeError("head: ridge_cv() needs ridge_stats_begin(folds=K) and the clips added")
+        grid = [float(x) for x in grid]
+        if not grid or not all(math.isfinite(x) and x > 0 for x in grid):
+            raise ValueError(f"head: ridge_cv: grid={grid!r}: one or more positive values are needed")
+        H, K, L, E, V, d = max(1, self.G), st["folds"], len(grid), self.E, self.V, self.dev
+        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        for g in range(H):
+            for k in range(K):
+                if st["n_fold"][g][k] < 2:
+                    raise ValueError(f"head: ridge_cv: {name(g)}: fold {k} of {K} holds {st['n_fold'][g][k]} clip(s) (block = "
+                                     f"{st['block']}, N = {st['n'][g]}): a held-out correlation needs 2 or more; use fewer folds or "
+                                     "a smaller block")
+        f64 = torch.float64
+        A = torch.empty(E, E, dtype=f64, device=d)
+        X = torch.empty(V, E, dtype=f64, device=d)
+        W = torch.empty(V, E, dtype=torch.float32, device=d)        # vlb_ridge_solve's fp32 outputs: scratch here
+        b = torch.empty(V, dtype=torch.float32, device=d)
+        Gc = torch.empty(E, E, dtype=f64, device=d)
+        Rc = torch.empty(V, E, dtype=f64, device=d)
+        vy = torch.empty(V, dtype=f64, device=d)
+        ws = torch.empty(lib.vlb_ridge_cv_ws_doubles(E, V), dtype=f64, device=d)
+        table = torch.full((H, K, L, V), float("nan"), dtype=f64, device=d)
+        info = torch.zeros(H, K, L, dtype=torch.int32, device=d)
+        for g in range(H):
+            for k in range(K):
+                nk = st["n_fold"][g][k]
+                Tg, Tc, Tsz, Tsy = self._ridge_fold_sums(st, g, k)
+                check(lib.vlb_ridge_cv_center(st["G"][g, k].data_ptr(), st["C"][g, k].data_ptr(), st["sz"][g, k].data_ptr(),
+                                              st["sy"][g, k].data_ptr(), st["syy"][g, k].data_ptr(), nk, Gc.data_ptr(), Rc.data_ptr(),
+                                              vy.data_ptr(), E, V, _stream()), "vlb_ridge_cv_center")
+                for i, lam in enumerate(grid):
+                    check(lib.vlb_ridge_solve(Tg.data_ptr(), Tc.data_ptr(), Tsz.data_ptr(), Tsy.data_ptr(), st["n"][g] - nk, lam,
+                                              A.data_ptr(), X.data_ptr(), W.data_ptr(), b.data_ptr(), info[g, k, i:].data_ptr(), E, V,
+                                              _stream()), "vlb_ridge_solve")
+                    check(lib.vlb_ridge_cv_score(X.data_ptr(), Gc.data_ptr(), Rc.data_ptr(), vy.data_ptr(), ws.data_ptr(),
+                                                 table[g, k, i].data_ptr(), info[g, k, i:].data_ptr(), E, V, _stream()),
+                          "vlb_ridge_cv_score")
+        infos = info.cpu()                              # the two device reads of the sweep
+        means = table.mean(-1).cpu()                    # [H,K,L]; NaN where the solve failed
+        ok = [not bool(infos[:, :, i].any()) for i in range(L)]
+        for i in range(L):
+            if not ok[i]:
+                bad = [(g, k, int(infos[g, k, i])) for g in range(H) for k in range(K) if int(infos[g, k, i])]
+                warnings.warn(f"head: ridge_cv: l2_lambda = {grid[i]!r} (grid point {i}) is excluded: "
+                              + ", ".join(f"{name(g)} fold {k} info = {v}" for g, k, v in bad[:4])
+                              + (" ..." if len(bad) > 4 else "") + " (a pivot that is not positive, or NaN / Inf in the targets)")
+        if not any(ok):
+            raise ValueError(f"head: ridge_cv: every grid point of {grid!r} had a failed solve; the parameters are unchanged")
+        per_head = means.mean(1)                        # [H,L]
+        score = per_head.mean(0)                        # [L]
+        best = max((i for i in range(L) if ok[i]), key=lambda i: (float(score[i]), grid[i]))
+        st["cv_table"] = table                          # [H,K,L,V], for inspection
+        return {"grid": grid, "score": [float(s) for s in score], "score_per_head": [[float(s) for s in row] for row in per_head],
+                "best_index": best, "best_lambda": grid[best], "r": table.mean(1), "infos": infos.tolist()}

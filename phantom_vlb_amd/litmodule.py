@@ -14,6 +14,7 @@ loss), because there is no autograd graph through hand-written kernels.
 """
 from __future__ import annotations
 
+import math
 import os
 import warnings
 from dataclasses import dataclass
@@ -178,6 +179,13 @@ class VLBLitModuleConfig:
     # minimiser of the mse objective for the current LN parameters (dropout not included), fp64 on the device;
     # training then goes on as configured.  None: AdamW finds them, as the reference
     ridge_fit: str | None = None
+    # ridge_fit="closed_form" only.  A list of two or more distinct positive values: the fit chooses l2_lambda among them by
+    # blocked K-fold cross-validation on the train split (held-out Pearson r, from the same one pass over the cache; DESIGN
+    # §5.3.6), solves with it and keeps it for every later step (the configured l2_lambda holds until then and need not be
+    # in the list).  A clip's fold is (its rank in its head's clips // ridge_cv_block) % ridge_cv_folds.  None: l2_lambda as given
+    ridge_lambda_grid: list[float] | None = None
+    ridge_cv_folds: int = 5
+    ridge_cv_block: int = 128           # contiguous clips per block, about three minutes of TRs: a choice, not a measurement
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -200,6 +208,24 @@ class VLBLitModuleConfig:
             if not self.l2_lambda > 0:
                 raise ValueError(f"ridge_fit='closed_form' needs l2_lambda > 0 (got {self.l2_lambda}): with fewer clips than "
                                  "features the system is singular without the penalty; set l2_lambda to a positive value")
+        if isinstance(self.ridge_cv_folds, bool) or not isinstance(self.ridge_cv_folds, int) or self.ridge_cv_folds < 2:
+            raise ValueError(f"ridge_cv_folds={self.ridge_cv_folds!r}: an integer >= 2 is needed")
+        if isinstance(self.ridge_cv_block, bool) or not isinstance(self.ridge_cv_block, int) or self.ridge_cv_block < 1:
+            raise ValueError(f"ridge_cv_block={self.ridge_cv_block!r}: an integer >= 1 is needed")
+        if self.ridge_lambda_grid is not None:
+            if self.ridge_fit != "closed_form":
+                raise ValueError("ridge_lambda_grid is the closed-form fit's choice of l2_lambda: set ridge_fit='closed_form' "
+                                 "(or leave ridge_lambda_grid unset)")
+            if isinstance(self.ridge_lambda_grid, (str, bytes)) or not hasattr(self.ridge_lambda_grid, "__iter__"):
+                raise ValueError(f"ridge_lambda_grid={self.ridge_lambda_grid!r}: a list of l2_lambda values is needed")
+            grid = list(self.ridge_lambda_grid)
+            for x in grid:
+                if isinstance(x, bool) or not isinstance(x, (int, float)) or not (math.isfinite(x) and x > 0):
+                    raise ValueError(f"ridge_lambda_grid={grid!r}: {x!r} is not a positive number; every value must be > 0")
+            grid = [float(x) for x in grid]
+            if len(set(grid)) < 2 or len(set(grid)) != len(grid):
+                raise ValueError(f"ridge_lambda_grid={grid!r}: two or more distinct values are needed")
+            self.ridge_lambda_grid = grid
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
@@ -328,6 +354,8 @@ class VLBLitModule(_Base):
                                            num_frames=g.num_frames, use_cache=False), backbone=self.backbone)
         self.head = BrainHead(g.dim, cfg.num_target, cfg.l2_lambda, g.ln_eps, dev, sd=head_state, seed=cfg.init_seed,
                               loss=getattr(cfg, "loss", "mse"), readout_layers=taps, subjects=getattr(cfg, "subjects", None))
+        if "_ridge_cv_lambda" in self.__dict__:      # a checkpoint loaded before the head existed: the l2_lambda its fit chose
+            self.head.l2_lambda = float(self.__dict__["_ridge_cv_lambda"])
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -598,7 +626,10 @@ class VLBLitModule(_Base):
         train dataset) in ``features_only`` mode in index order, ``chunk`` clips at a time, accumulate the fp64 sums from the
         cached features, solve per head, write the fp32 masters (wherever they live) and their bf16 copies, and zero AdamW's
         moments of exactly these two tensors.  Logs ``ridge_fit/n``, ``ridge_fit/l2_lambda`` and the first chunk's
-        ``ridge_fit/train_mse_before`` / ``_after`` (the existing cached forward).  -> ``BrainHead.ridge_solve``'s list."""
+        ``ridge_fit/train_mse_before`` / ``_after`` (the existing cached forward).  -> ``BrainHead.ridge_solve``'s list.
+        With ``ridge_lambda_grid`` set and no explicit ``l2_lambda`` the same walk keeps the sums per fold, ``ridge_cv``
+        chooses ``l2_lambda``, the solve uses it and ``head.l2_lambda`` keeps it; ``ridge_fit/cv_score``,
+        ``/cv_score_<i>`` and ``/cv_best_index`` are logged too and ``ridge_fit_result`` is ``ridge_cv``'s dict."""
         cfg = self.config
         if not cfg.cache_features or cfg.loss != "mse":
             raise ValueError("fit_ridge_closed_form needs cache_features=True and loss='mse'")
@@ -615,9 +646,14 @@ class VLBLitModule(_Base):
         subjects = getattr(cfg, "subjects", None)
         was = ds.features_only
         ds.features_only = True            # an item is {"index", "timeseries"[, "subject"]}: nothing else is read
-        first = mse = None
+        first = mse = cv = None
+        # ridge_lambda_grid (and no explicit l2_lambda): the same one walk keeps the sums per fold, ridge_cv chooses (§5.3.6)
+        grid = cfg.ridge_lambda_grid if l2_lambda is None else None
         try:
-            self.head.ridge_stats_begin()
+            if grid is not None:
+                self.head.ridge_stats_begin(folds=cfg.ridge_cv_folds, block=cfg.ridge_cv_block)
+            else:
+                self.head.ridge_stats_begin()
             for lo in range(0, len(ds), chunk):
                 items = [ds[i] for i in range(lo, min(lo + chunk, len(ds)))]
                 batch = {k: torch.stack([torch.as_tensor(it[k]) for it in items]) for k in items[0]}
@@ -628,7 +664,13 @@ class VLBLitModule(_Base):
                     first = (batch["index"], y, subject)
                     mse = [float(self.head.forward_cached(cache, *first[:2], None, subject)[1][0])]
                 self.head.ridge_stats_add(cache, batch["index"], y, subject)
-            out = self.head.ridge_solve(cfg.l2_lambda if l2_lambda is None else l2_lambda)
+            if grid is not None:
+                cv = self.head.ridge_cv(grid)
+                out = self.head.ridge_solve(cv["best_lambda"])
+                # every later step and validation loss uses the objective these weights minimise
+                self.head.l2_lambda = self._ridge_cv_lambda = float(cv["best_lambda"])
+            else:
+                out = self.head.ridge_solve(cfg.l2_lambda if l2_lambda is None else l2_lambda)
         finally:
             ds.features_only = was
             self.head.ridge_stats_end()
@@ -640,6 +682,13 @@ class VLBLitModule(_Base):
         self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]))
         self.log("ridge_fit/train_mse_before", mse[0])
         self.log("ridge_fit/train_mse_after", mse[1])
+        if cv is not None:
+            self.log("ridge_fit/cv_score", float(cv["score"][cv["best_index"]]))
+            for i, s in enumerate(cv["score"]):
+                self.log(f"ridge_fit/cv_score_{i}", float(s))
+            self.log("ridge_fit/cv_best_index", float(cv["best_index"]))
+            self.ridge_fit_result = dict(cv, solve=out)     # ridge_cv's dict, and ridge_solve's list under "solve"
+            return out
         self.ridge_fit_result = out
         return out
 
@@ -828,10 +877,16 @@ class VLBLitModule(_Base):
         """Lightning hook: the counter-based dropout state (head step, LoRA step) next to ``state_dict`` /
         ``optimizer_states`` (VlbAdamW.state_dict carries moments, step count and the full fine-tune's backbone masters)."""
         checkpoint["vlb_rng"] = self.rng_state()
+        if "_ridge_cv_lambda" in self.__dict__:      # ridge_lambda_grid: the l2_lambda the closed-form fit chose (§5.3.6)
+            checkpoint["vlb_ridge_l2_lambda"] = float(self.__dict__["_ridge_cv_lambda"])
 
     def on_load_checkpoint(self, checkpoint: dict) -> None:
         if "vlb_rng" in checkpoint:
             self.set_rng_state(checkpoint["vlb_rng"])
+        if "vlb_ridge_l2_lambda" in checkpoint:
+            self._ridge_cv_lambda = float(checkpoint["vlb_ridge_l2_lambda"])
+            if getattr(self, "head", None) is not None:
+                self.head.l2_lambda = self._ridge_cv_lambda
 
     def state_dict(self, *args, **kwargs):
         """Trainables only, upstream / peft names (what a Lightning ModelCheckpoint stores for this module; the reference saves

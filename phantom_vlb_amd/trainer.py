@@ -91,6 +91,8 @@ def trainable_state(module, step: int, to_host: bool = True) -> dict | None:
     if sch is not None:
         state["lr_scheduler"] = sch.state_dict()
     state["rng"] = module.rng_state()
+    if "_ridge_cv_lambda" in module.__dict__:      # ridge_lambda_grid: the l2_lambda the closed-form fit chose
+        state["ridge_l2_lambda"] = float(module.__dict__["_ridge_cv_lambda"])
     return state
 
 
@@ -159,6 +161,8 @@ def load_trainable_checkpoint(module, path):
             opt.param_groups[0]["lr"] = st["lr"]
     if "rng" in st:
         module.set_rng_state(st["rng"])
+    if "ridge_l2_lambda" in st:
+        module._ridge_cv_lambda = module.head.l2_lambda = float(st["ridge_l2_lambda"])
     return st.get("global_step", 0)
 
 
@@ -219,6 +223,14 @@ class Trainer:
         if self.rank == 0:
             for lg in self.loggers:
                 lg.log_metrics(metrics, self.global_step)
+
+    def _log_ridge_cv(self, model):
+        """ridge_lambda_grid: the ``ridge_fit/*`` values of the cross-validated closed-form fit (the chosen l2_lambda, the
+        scores) go to the loggers once, right after the fit."""
+        res = getattr(model, "ridge_fit_result", None)
+        if isinstance(res, dict) and getattr(self, "_ridge_cv_logged", None) is not res:
+            self._ridge_cv_logged = res
+            self._log({k: v for k, v in model.logged.items() if k.startswith("ridge_fit/")})
 
     def validate(self, model, loader):
         """Validation epoch.  Data parallel: ranks take rank-strided batches (the frozen weights are replicated, so
@@ -292,6 +304,7 @@ class Trainer:
         keep_on_host = ("language", "padvals", "subject")    # "subject" (multi-subject runs): the head checks it on the host
         if self._feature_cache:
             model.setup_feature_cache(train_loader.dataset, val_loader.dataset)
+            self._log_ridge_cv(model)         # a persisted cache: the cross-validated fit has run already
             keep_on_host += ("index",)        # the cache decides hit / miss on the host
         if torch.cuda.is_available():        # overlap the next batch's host->device copy with the current step
             from .datamodule import DevicePrefetcher
@@ -346,6 +359,7 @@ class Trainer:
                 batches.close()              # a batch staged ahead but never consumed is dropped (DevicePrefetcher.on_discard)
             if self._feature_cache and (rate := model.feature_cache_end("train")) is not None:
                 self._log({"feature_cache/train_hit_rate": rate, "epoch": epoch})
+            self._log_ridge_cv(model)
         return
 
     def save_checkpoint(self, filepath, weights_only: bool = False):
