@@ -649,6 +649,32 @@ int64_t vlb_ridge_cv_ws_doubles(int E, int V);
 int vlb_ridge_cv_score(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws, double* r_out,
                        const int* info, int E, int V, void* stream);
 
+/* One l2_lambda per target for the closed-form fit (opt-in, ridge_lambda_per_target; every entry point above
+ * keeps its bits).  J(W, b) = 1/(N V) sum_n ||W z_n + b - y_n||^2 + sum_v lambda_v ||W_v||^2 decouples per target: row v of
+ * the minimiser is row v of vlb_ridge_solve's with the scalar lambda_v.
+ * vlb_ridge_cv_select (src/utils.py:59-73: the layer's targets, one by one): table fp64 [K,L,V] (one head's held-out r) ->
+ *   rmean [L,V] = (sum over k ascending) / K;  choice int32 [V] = the grid point with the largest rmean among those with
+ *   ok[i] != 0 (an excluded point is skipped through the mask, whatever it holds), an exact tie going to the larger grid[i]
+ *   (grid fp64 [L], any order);  rbest [V] = the winning rmean.  No point allowed: choice -1, rbest NaN.
+ * vlb_ridge_solve_rows (src/utils.py:59-73: the weights, row by row): vlb_ridge_solve's launches through the same host code;
+ *   W_out[v,:] and b_out[v] are written only where choice[v] == want (want >= 0), every other row's bytes stay as they are;
+ *   a non-zero *info writes nothing.  Row v has the bits vlb_ridge_solve gives it for the same l2_lambda.
+ * vlb_head_l2_rows_fwd (src/utils.py:59-73: the layer's l2 term, one lambda per row): ridge_w bf16 [R,E] (R = max(1,G) V),
+ *   lam fp32 [R]; loss_terms[1] <- sum_r lam[r] sum_e (float)W[r,e]^2 (fp64 sums in a fixed order through ws,
+ *   vlb_head_l2_rows_ws_doubles(R) doubles, rounded once), loss_terms[2] <- loss_terms[0] + loss_terms[1] (fp32).  Run after
+ *   a forward entry that was handed l2_lambda = 0, on the same stream.  E % 8 == 0, E <= 8192, ridge_w 16-byte aligned.
+ * vlb_head_l2_rows_bwd (src/utils.py:59-73: the l2 term's gradient): d_ridge_w[r,e] += (coef lam[r]) (float)W[r,e] with
+ *   coef = l2_scale * 2; a row with lam[r] == 0 keeps its bits.  Run after a backward entry that was handed l2_lambda = 0.
+ * vlb_head_l2_rows_ws_doubles (src/utils.py:59-73): the doubles vlb_head_l2_rows_fwd's ws needs; 0 for R < 1. */
+int vlb_ridge_cv_select(const double* table, const double* grid, const int* ok, double* rmean, int* choice, double* rbest,
+                        int K, int L, int V, void* stream);
+int vlb_ridge_solve_rows(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
+                         double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, const int* choice,
+                         int want, void* stream);
+int64_t vlb_head_l2_rows_ws_doubles(int R);
+int vlb_head_l2_rows_fwd(const void* ridge_w, const float* lam, double* ws, float* loss_terms, int R, int E, void* stream);
+int vlb_head_l2_rows_bwd(const void* ridge_w, const float* lam, float* d_ridge_w, int R, int E, float coef, void* stream);
+
 /* head dropout mask (litmodule :226,251 nn.Dropout(p) in training): out[i] = keep_i / (1-p), keep_i from a
  * counter-based hash of (seed, i) with 16 random bits per element (same mixer as the LoRA masks).  The result is
  * what vlb_head_fwd / vlb_head_bwd take as `keep_scale`. */

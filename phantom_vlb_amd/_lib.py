@@ -139,11 +139,16 @@ SIGNATURES = {
     "vlb_ridge_cv_center": [P, P, P, P, P, L, P, P, P, I, I, P],
     "vlb_ridge_cv_ws_doubles": [I, I],
     "vlb_ridge_cv_score": [P, P, P, P, P, P, P, I, I, P],
+    "vlb_ridge_cv_select": [P, P, P, P, P, P, I, I, I, P],
+    "vlb_ridge_solve_rows": [P, P, P, P, L, D, P, P, P, P, P, I, I, P, I, P],
+    "vlb_head_l2_rows_ws_doubles": [I],
+    "vlb_head_l2_rows_fwd": [P, P, P, P, I, I, P],
+    "vlb_head_l2_rows_bwd": [P, P, P, I, I, F, P],
     "vlb_allreduce_scalar": [P, P, I, P],
     "vlb_cast_f32_to_bf16": [P, P, L, P],
     "vlb_cast_bf16_to_f32": [P, P, L, P],
 }
-_RESTYPES = {"vlb_last_error": c_char_p, "vlb_hrf_pool_ws_floats": c_int64, "vlb_ridge_ws_floats": c_int64, "vlb_ridge_cv_ws_doubles": c_int64, "vlb_head_ws_floats": c_int64, "vlb_head_mix_ws_floats": c_int64, "vlb_head_grouped_ws_floats": c_int64,"vlb_wgrad_u_ws_floats": c_int64,
+_RESTYPES = {"vlb_last_error": c_char_p, "vlb_hrf_pool_ws_floats": c_int64, "vlb_ridge_ws_floats": c_int64, "vlb_ridge_cv_ws_doubles": c_int64, "vlb_head_l2_rows_ws_doubles": c_int64, "vlb_head_ws_floats": c_int64, "vlb_head_mix_ws_floats": c_int64, "vlb_head_grouped_ws_floats": c_int64,"vlb_wgrad_u_ws_floats": c_int64,
              "vlb_gemm_workspace_bytes": c_int64, "vlb_reducescatter_stage_floats": c_int64, "vlb_comm_loopback_stage_bytes": c_int64,
              "vlb_norm_bwd_ws_floats": c_int64, "vlb_rmsnorm_bwd_full_ws_floats": c_int64, "vlb_colsum_ws_floats": c_int64, "vlb_dwconv3x3_bwd_w_ws_floats": c_int64}
 

@@ -1793,3 +1793,125 @@ extern "C" int vlb_ridge_fwd(const void* x, const void* ridge_w, const void* rid
   if (e != hipSuccess) { vlb_set_error("ridge_fwd: copy failed: %s", hipGetErrorString(e)); return VLB_ERR_LAUNCH; }
   return VLB_OK;
 }
+
+// ---------------------------------------------------------------- per-row ridge penalty
+// With one l2_lambda per row of ridge_layer.linear.weight (R = max(1,G) V rows) the penalty is sum_r lam[r] ||W_r||^2.  The
+// existing entries are handed l2_lambda = 0 (their l2 term and l2 gradient are exactly zero) and these two run after them on
+// the same stream.  Both stream W once: a lane reads 8 bf16 as one 16-byte load, the 64 lanes of a wave 1 KiB contiguous.
+namespace {
+
+constexpr int L2R_MAX_BLOCKS = 2048;      // memory-bound grid cap: 256 CUs x 8 blocks; the rest is grid-strided
+
+// forward, stage 1: a wave owns rows gw, gw + nw, ... (gw = its index in the grid, nw = waves in the grid) in ascending order.
+// Per row: each lane adds the fp32 squares (exact: a bf16 square has 16 significant bits) of its chunks lane, lane + 64, ...
+// into one fp64 accumulator, the 64 lanes are summed by a fixed xor butterfly, the row sum is multiplied by (double)lam[r] and
+// added to the wave's fp64 total.  part[block] = the 4 waves' totals in ascending order.  No atomics.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(256) void l2_rows_partial_kernel(const bf16* __restrict__ W, const float* __restrict__ lam,
+                                                              double* __restrict__ part, int R, int E) {
+  __shared__ double wtot[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nw = gridDim.x * 4, chunks = E >> 3;
+  double total = 0.0;
+  for (int r = blockIdx.x * 4 + wave; r < R; r += nw) {
+    const bf16* row = W + (int64_t)r * E;
+    double s = 0.0;
+#pragma unroll 4
+    for (int c = lane; c < chunks; c += 64) {
+      const bf16x8 w = *reinterpret_cast<const bf16x8*>(row + 8 * c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float f = (float)w[j];
+        s += (double)(f * f);
+      }
+    }
+    s = wave_sum_f64(s);
+    total += (double)lam[r] * s;
+  }
+  if (lane == 0) wtot[wave] = total;
+  __syncthreads();
+  if (threadIdx.x == 0) part[blockIdx.x] = ((wtot[0] + wtot[1]) + wtot[2]) + wtot[3];
+}
+
+// forward, stage 2 (one block, in the mould of loss_finalize_kernel): thread i sums partials i, i + 256, ... in order, the 256
+// sums are tree-summed in LDS; loss_terms[1] <- the total rounded once to fp32, loss_terms[2] <- loss_terms[0] + loss_terms[1]
+__global__ __launch_bounds__(256) void l2_rows_finish_kernel(const double* __restrict__ part, int nblk, float* __restrict__ out) {
+  __shared__ double sm[256];
+  double t = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) t += part[i];
+  sm[threadIdx.x] = t;
+  __syncthreads();
+  for (int s2 = 128; s2 > 0; s2 >>= 1) {
+    if ((int)threadIdx.x < s2) sm[threadIdx.x] += sm[threadIdx.x + s2];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l2 = (float)sm[0];
+    out[1] = l2;
+    out[2] = out[0] + l2;
+  }
+}
+
+// backward: d[r,e] += (coef lam[r]) (float)W[r,e], one owner per element: a thread takes 8 consecutive elements of one row
+// (one 16-byte load of W, two 16-byte loads and stores of d).  A row with lam[r] == 0 is neither read nor written.
+__global__ __launch_bounds__(256) void l2_rows_bwd_kernel(const bf16* __restrict__ W, const float* __restrict__ lam,
+                                                          float* __restrict__ d, int64_t nchunks, int chunks_per_row, float coef) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < nchunks; c += stride) {
+    const float l = lam[c / chunks_per_row];
+    if (l == 0.f) continue;
+    const float k = coef * l;
+    const bf16x8 w = *reinterpret_cast<const bf16x8*>(W + 8 * c);
+    f32x4* dp = reinterpret_cast<f32x4*>(d + 8 * c);
+    f32x4 lo = dp[0], hi = dp[1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      lo[j] = fmaf(k, (float)w[j], lo[j]);
+      hi[j] = fmaf(k, (float)w[4 + j], hi[j]);
+    }
+    dp[0] = lo;
+    dp[1] = hi;
+  }
+}
+
+inline int l2_rows_blocks(int R) {
+  const int b = (R + 3) / 4;
+  return b < L2R_MAX_BLOCKS ? b : L2R_MAX_BLOCKS;
+}
+
+}  // namespace
+
+extern "C" int64_t vlb_head_l2_rows_ws_doubles(int R) { return R < 1 ? 0 : (int64_t)l2_rows_blocks(R); }
+
+extern "C" int vlb_head_l2_rows_fwd(const void* ridge_w, const float* lam, double* ws, float* loss_terms, int R, int E,
+                                    void* stream) {
+  VLB_REQUIRE(ridge_w && lam && ws && loss_terms, "head_l2_rows_fwd: null argument");
+  VLB_REQUIRE(R >= 1 && E >= 8 && E % 8 == 0 && E <= 8192, "head_l2_rows_fwd: bad shape R=%d E=%d (E %% 8 == 0, E <= 8192)", R, E);
+  VLB_REQUIRE(((uintptr_t)ridge_w & 15) == 0, "head_l2_rows_fwd: ridge_w is not 16-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const int nblk = l2_rows_blocks(R);
+  hipLaunchKernelGGL(l2_rows_partial_kernel, dim3(nblk), dim3(256), 0, st, (const bf16*)ridge_w, lam, ws, R, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(l2_rows_finish_kernel, dim3(1), dim3(256), 0, st, ws, nblk, loss_terms);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_head_l2_rows_bwd(const void* ridge_w, const float* lam, float* d_ridge_w, int R, int E, float coef,
+                                    void* stream) {
+  VLB_REQUIRE(ridge_w && lam && d_ridge_w, "head_l2_rows_bwd: null argument");
+  VLB_REQUIRE(R >= 1 && E >= 8 && E % 8 == 0 && E <= 8192, "head_l2_rows_bwd: bad shape R=%d E=%d (E %% 8 == 0, E <= 8192)", R, E);
+  VLB_REQUIRE(((uintptr_t)ridge_w & 15) == 0 && ((uintptr_t)d_ridge_w & 15) == 0, "head_l2_rows_bwd: a tensor is not 16-byte aligned");
+  const int64_t nchunks = (int64_t)R * (E >> 3);
+  const int64_t want = (nchunks + 255) / 256;
+  const int nblk = (int)(want < L2R_MAX_BLOCKS ? want : L2R_MAX_BLOCKS);
+  hipLaunchKernelGGL(l2_rows_bwd_kernel, dim3(nblk), dim3(256), 0, as_stream(stream), (const bf16*)ridge_w, lam, d_ridge_w, nchunks,
+                     E >> 3, coef);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}

@@ -329,13 +329,17 @@ __global__ void ridge_check_targets_kernel(const double* __restrict__ sy, int V,
 }
 // W[v,:] = fp32(X[v,:]),  b[v] = fp32(sy[v] / N - (X[v,:] . sz) / N): one block per v; the dot product is summed per thread
 // over e = t, t + 256, ... and then over the 256 threads in ascending order (fixed, no atomics).  No-op on *info != 0.
+// With ``choice`` (vlb_ridge_solve_rows) only the rows with choice[v] == want are written, by the same
+// arithmetic; the other rows' blocks return at once and their bytes in W and b stay as they are.
 __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restrict__ X, const double* __restrict__ sz,
                                                            const double* __restrict__ sy, float* __restrict__ W,
                                                            float* __restrict__ b, int E, double inv_n,
-                                                           const int* __restrict__ info) {
+                                                           const int* __restrict__ info, const int* __restrict__ choice,
+                                                           int want) {
   __shared__ double part[256];
   if (*info != 0) return;
   const int v = blockIdx.x;
+  if (choice && choice[v] != want) return;              // block-uniform
   double t = 0.0;
   for (int e = threadIdx.x; e < E; e += 256) {
     const double x = X[(int64_t)v * E + e];
@@ -483,6 +487,32 @@ __global__ __launch_bounds__(256) void cv_finish_kernel(const double* __restrict
   }
 }
 
+// ---------------------------------------------------------------- l2_lambda per target
+// One head's slice of the held-out table, [K,L,V]: rmean[i,v] = (sum_k table[k,i,v], ascending k, from 0) / K for every grid
+// point; choice[v] = the grid point with the largest rmean among those with ok[i] != 0 (an excluded point is never compared,
+// whatever it holds), an exact tie going to the larger grid[i]; rbest[v] = its rmean.  No point allowed: choice -1, rbest NaN.
+// One thread per target, lanes on consecutive targets: every load and store is contiguous over the lanes.
+__global__ __launch_bounds__(256) void cv_select_kernel(const double* __restrict__ table, const double* __restrict__ grid,
+                                                        const int* __restrict__ ok, double* __restrict__ rmean,
+                                                        int* __restrict__ choice, double* __restrict__ rbest, int K, int L, int V) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= V) return;
+  const double k_d = (double)K;
+  int best = -1;
+  double rb = __builtin_nan(""), gb = 0.0;
+  for (int i = 0; i < L; ++i) {
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) s += table[((int64_t)k * L + i) * V + v];
+    const double m = s / k_d;
+    rmean[(int64_t)i * V + v] = m;
+    if (ok[i] == 0) continue;
+    const double g = grid[i];
+    if (best < 0 || m > rb || (m == rb && g > gb)) { best = i; rb = m; gb = g; }
+  }
+  choice[v] = best;
+  rbest[v] = rb;
+}
+
 inline dim3 tiles(int M, int N) { return dim3((N + TS - 1) / TS, (M + TS - 1) / TS); }
 
 }  // namespace
@@ -561,11 +591,11 @@ extern "C" int vlb_chol_solve_f64(const double* L, int ldl, double* X, int n, in
   return VLB_OK;
 }
 
-extern "C" int vlb_ridge_solve(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
-                               double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, void* stream) {
-  VLB_REQUIRE(G && C && sz && sy && A_ws && X_ws && W_out && b_out && info, "ridge_solve: null argument");
-  VLB_REQUIRE(E >= 1 && V >= 1 && N >= 1, "ridge_solve: bad shape E=%d V=%d N=%lld", E, V, (long long)N);
-  VLB_REQUIRE(l2_lambda >= 0.0, "ridge_solve: l2_lambda=%g is negative", l2_lambda);
+// form, factor, solve, finish: vlb_ridge_solve (choice = nullptr: every row is written) and vlb_ridge_solve_rows (rows with
+// choice[v] == want) run this one sequence of launches
+static int ridge_solve_launch(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
+                              double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, const int* choice,
+                              int want, void* stream) {
   const double inv_n = 1.0 / (double)N, ridge = l2_lambda * (double)N * (double)V;
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(ridge_form_a_kernel, dim3((E + 255) / 256, E), dim3(256), 0, st, G, sz, A_ws, E, inv_n, ridge);
@@ -576,7 +606,36 @@ extern "C" int vlb_ridge_solve(const double* G, const double* C, const double* s
   hipLaunchKernelGGL(ridge_check_targets_kernel, dim3(1), dim3(64), 0, st, sy, V, info);
   VLB_LAUNCH_CHECK();
   if (int rc = vlb_chol_solve_f64(A_ws, E, X_ws, E, V, E, info, stream)) return rc;
-  hipLaunchKernelGGL(ridge_finish_kernel, dim3(V), dim3(256), 0, st, X_ws, sz, sy, W_out, b_out, E, inv_n, info);
+  hipLaunchKernelGGL(ridge_finish_kernel, dim3(V), dim3(256), 0, st, X_ws, sz, sy, W_out, b_out, E, inv_n, info, choice, want);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+extern "C" int vlb_ridge_solve(const double* G, const double* C, const double* sz, const double* sy, int64_t N, double l2_lambda,
+                               double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E, int V, void* stream) {
+  VLB_REQUIRE(G && C && sz && sy && A_ws && X_ws && W_out && b_out && info, "ridge_solve: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1 && N >= 1, "ridge_solve: bad shape E=%d V=%d N=%lld", E, V, (long long)N);
+  VLB_REQUIRE(l2_lambda >= 0.0, "ridge_solve: l2_lambda=%g is negative", l2_lambda);
+  return ridge_solve_launch(G, C, sz, sy, N, l2_lambda, A_ws, X_ws, W_out, b_out, info, E, V, nullptr, 0, stream);
+}
+
+// ---------------------------------------------------------------- C-ABI: l2_lambda per target
+extern "C" int vlb_ridge_solve_rows(const double* G, const double* C, const double* sz, const double* sy, int64_t N,
+                                    double l2_lambda, double* A_ws, double* X_ws, float* W_out, float* b_out, int* info, int E,
+                                    int V, const int* choice, int want, void* stream) {
+  VLB_REQUIRE(G && C && sz && sy && A_ws && X_ws && W_out && b_out && info && choice, "ridge_solve_rows: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1 && N >= 1, "ridge_solve_rows: bad shape E=%d V=%d N=%lld", E, V, (long long)N);
+  VLB_REQUIRE(l2_lambda >= 0.0, "ridge_solve_rows: l2_lambda=%g is negative", l2_lambda);
+  VLB_REQUIRE(want >= 0, "ridge_solve_rows: want=%d is negative", want);
+  return ridge_solve_launch(G, C, sz, sy, N, l2_lambda, A_ws, X_ws, W_out, b_out, info, E, V, choice, want, stream);
+}
+
+extern "C" int vlb_ridge_cv_select(const double* table, const double* grid, const int* ok, double* rmean, int* choice,
+                                   double* rbest, int K, int L, int V, void* stream) {
+  VLB_REQUIRE(table && grid && ok && rmean && choice && rbest, "ridge_cv_select: null argument");
+  VLB_REQUIRE(K >= 1 && L >= 1 && V >= 1, "ridge_cv_select: bad shape K=%d L=%d V=%d", K, L, V);
+  hipLaunchKernelGGL(cv_select_kernel, dim3((V + 255) / 256), dim3(256), 0, as_stream(stream), table, grid, ok, rmean, choice, rbest,
+                     K, L, V);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }

@@ -145,6 +145,44 @@ class BrainHead:
         self.compute = {n: t.to(BF16) for n, t in self.master.items()}
         self.grads = {n: torch.zeros_like(t) for n, t in self.master.items()}
         self._cap = None
+        self.l2_lambda_rows = None        # set_l2_lambda_rows: one penalty per row of the ridge weight
+
+    # ------------------------------------------------------------------ one l2_lambda per row (set_l2_lambda_rows)
+    def set_l2_lambda_rows(self, rows):
+        """``rows`` fp32 [R] on the device, R = max(1,G) * V (the rows of ``ridge_layer.linear.weight``), every value finite
+        and >= 0: the penalty becomes sum_r rows[r] ||W_r||^2.  Every forward / backward entry is then handed l2_lambda = 0
+        and followed by vlb_head_l2_rows_fwd / _bwd on the same stream.  None: back to the scalar ``l2_lambda``."""
+        if rows is None:
+            self.l2_lambda_rows = None
+            return
+        if self.loss != "mse":
+            raise ValueError(f"head: a penalty per row is defined for the mse objective; this head has loss={self.loss!r}")
+        R = max(1, self.G) * self.V
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float32 or rows.numel() != R or \
+                rows.device.type != torch.device(self.dev).type:
+            raise ValueError(f"head: set_l2_lambda_rows needs an fp32 tensor of {R} values on {self.dev}, got "
+                             f"{getattr(rows, 'dtype', type(rows))} {tuple(getattr(rows, 'shape', ()))}")
+        rows = rows.detach().reshape(R).contiguous().clone()
+        if not bool((torch.isfinite(rows) & (rows >= 0)).all()):
+            raise ValueError("head: set_l2_lambda_rows: every value must be finite and >= 0")
+        self.l2_lambda_rows = rows
+        self._l2_rows_ws = torch.empty(max(1, lib.vlb_head_l2_rows_ws_doubles(R)), dtype=torch.float64, device=self.dev)
+
+    def _lam(self):
+        """the l2_lambda the existing entries are handed: 0 while a penalty per row is in force"""
+        return self.l2_lambda if self.l2_lambda_rows is None else 0.0
+
+    def _l2_rows_fwd(self):
+        if self.l2_lambda_rows is not None:
+            check(lib.vlb_head_l2_rows_fwd(self.compute["ridge_layer.linear.weight"].data_ptr(), self.l2_lambda_rows.data_ptr(),
+                                           self._l2_rows_ws.data_ptr(), self.loss_terms.data_ptr(), self.l2_lambda_rows.numel(),
+                                           self.E, _stream()), "vlb_head_l2_rows_fwd")
+
+    def _l2_rows_bwd(self, l2_scale):
+        if self.l2_lambda_rows is not None:
+            check(lib.vlb_head_l2_rows_bwd(self.compute["ridge_layer.linear.weight"].data_ptr(), self.l2_lambda_rows.data_ptr(),
+                                           self.grads["ridge_layer.linear.weight"].data_ptr(), self.l2_lambda_rows.numel(), self.E,
+                                           float(l2_scale) * 2.0, _stream()), "vlb_head_l2_rows_bwd")
 
     def _buffers(self, B, S):
         key = (B, S)
@@ -204,8 +242,9 @@ class BrainHead:
                                        self.gws.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
                                        self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
                                        self.rowstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, self.E,
-                                       self.V, self.G, n_rows, self.eps, self.l2_lambda, self.loss_kind, _stream()),
+                                       self.V, self.G, n_rows, self.eps, self._lam(), self.loss_kind, _stream()),
               "vlb_head_fwd_grouped")
+        self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
     def _bwd_grouped(self, loss_scale, l2_scale):
@@ -221,8 +260,9 @@ class BrainHead:
                                        gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
                                        gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(),
                                        self.gws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(), self.rowstat.data_ptr(),
-                                       B, self.E, self.V, self.G, self.eps, self.l2_lambda, float(loss_scale), float(l2_scale),
+                                       B, self.E, self.V, self.G, self.eps, self._lam(), float(loss_scale), float(l2_scale),
                                        self.loss_kind, _stream()), "vlb_head_bwd_grouped")
+        self._l2_rows_bwd(l2_scale)
 
     def subject_state_dict(self, name_or_index):
         """One subject's head in the reference's shapes ([V,E], [V], the shared LN tensors; fp32 masters): what a
@@ -264,18 +304,19 @@ class BrainHead:
                                None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
                                self.stats.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
                                self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                               self.loss_terms.data_ptr(), B, S, self.E, self.V, self.eps, self.l2_lambda,
+                               self.loss_terms.data_ptr(), B, S, self.E, self.V, self.eps, self._lam(),
                                None if cu is None else cu.data_ptr(), _stream()),
               "vlb_head_fwd")
         if self.loss_kind:
             self._loss_fwd(y, B, S)
+        self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
     def _loss_fwd(self, y, B, S):
         """loss_terms[0], [2] <- the chosen objective (S: where the forward left its ridge partials in ws; 0 = cached)"""
         check(lib.vlb_head_loss_fwd(self.pred.data_ptr(), y.data_ptr(), self.ws.data_ptr(), self.rowstat.data_ptr(),
                                     self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, S, self.E, self.V,
-                                    self.loss_kind, self.l2_lambda, _stream()), "vlb_head_loss_fwd")
+                                    self.loss_kind, self._lam(), _stream()), "vlb_head_loss_fwd")
 
     def backward(self, need_dhidden: bool, loss_scale: float = 1.0, l2_scale: float = 1.0):
         """Fills self.grads (fp32, overwritten) and returns d loss / d hidden (bf16) or None."""
@@ -302,9 +343,10 @@ class BrainHead:
                  gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
                  gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(),
                  self.ws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(),
-                 None if dh is None else dh.data_ptr(), B, S, self.E, self.V, self.eps, self.l2_lambda,
+                 None if dh is None else dh.data_ptr(), B, S, self.E, self.V, self.eps, self._lam(),
                  float(loss_scale), float(l2_scale), None if cu is None else cu.data_ptr(), rows,
                  _stream(), *tail), what)
+        self._l2_rows_bwd(l2_scale)
         return dh
 
     # ------------------------------------------------------------------ frozen-backbone feature cache (feature_cache.py)
@@ -338,10 +380,11 @@ class BrainHead:
                                       y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
                                       self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                      self.loss_terms.data_ptr(), B, self.E, self.V, cache.n, self.eps, self.l2_lambda,
+                                      self.loss_terms.data_ptr(), B, self.E, self.V, cache.n, self.eps, self._lam(),
                                       _stream()), "vlb_head_fwd_cached")
         if self.loss_kind:
             self._loss_fwd(y, B, 0)
+        self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
     # ------------------------------------------------------------------ readout from chosen decoder layers (readout_layers)
@@ -402,10 +445,11 @@ class BrainHead:
                                       y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
                                       self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                      self.loss_terms.data_ptr(), B, self.E, self.V, B, self.eps, self.l2_lambda,
+                                      self.loss_terms.data_ptr(), B, self.E, self.V, B, self.eps, self._lam(),
                                       _stream()), "vlb_head_fwd_cached")
         if self.loss_kind:
             self._loss_fwd(y, B, 0)
+        self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
     def backward_tapped(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
@@ -451,8 +495,9 @@ class BrainHead:
                  gr["ridge_layer.linear.bias"].data_ptr(), gr["layer_norm2.weight"].data_ptr(),
                  gr["layer_norm2.bias"].data_ptr(), gr["layer_norm1.weight"].data_ptr(),
                  gr["layer_norm1.bias"].data_ptr(), self.ws.data_ptr(), self.dz.data_ptr(),
-                 self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self.l2_lambda, float(loss_scale),
+                 self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self._lam(), float(loss_scale),
                  float(l2_scale), _stream(), *tail), what)
+        self._l2_rows_bwd(l2_scale)
 
     # ------------------------------------------------------------------ closed-form ridge fit (ridge_fit="closed_form")
     # With loss="mse", the LN parameters (and the mix) held fixed and dropout off, the objective over N clips is a ridge
@@ -631,7 +676,7 @@ class BrainHead:
                   "vlb_f64_sum_except")
         return T
 
-    def ridge_cv(self, grid):
+    def ridge_cv(self, grid, per_target=False):
         """Blocked K-fold cross-validation of ``l2_lambda`` over ``grid`` from the per-fold sums: for every head g, fold k and
         grid point i the training sums T_k are solved (vlb_ridge_solve, N = N_g - n_gk) and the held-out fold is scored
         (vlb_ridge_cv_score) into an fp64 table [H,K,L,V] pre-filled with NaN.  Everything is queued without a host sync; the
@@ -639,7 +684,12 @@ class BrainHead:
         and folds of the mean over targets of r; a grid point with any failed solve is excluded (a warning names it); the
         largest score wins and an exact tie goes to the larger lambda.  A (head, fold) with fewer than 2 clips, or every grid
         point excluded, raises.  The parameters are never written.  -> {"grid", "score" [L], "score_per_head" [H,L],
-        "best_index", "best_lambda", "r" [H,L,V] (fold mean, on the device), "infos" [H][K][L]}."""
+        "best_index", "best_lambda", "r" [H,L,V] (fold mean, on the device), "infos" [H][K][L]}.
+        ``per_target=True`` also chooses one grid point per (head, target) on the device (vlb_ridge_cv_select,
+        the same exclusions, a tie to the larger lambda) and adds "choice" [H,V] (device int32), "lambda_rows" [H,V] (device
+        fp32, grid[choice]), "lambda_counts" [H][L] (one more device read) and "score_per_target", the mean over heads and
+        targets of the winning fold-mean r - selected on the same folds it is scored on, so optimistic; everything else,
+        "best_index" and "best_lambda" included, is what the call returns without it."""
         import warnings
         st = getattr(self, "_ridge", None)
         if st is None or "folds" not in st:
@@ -695,5 +745,76 @@ class BrainHead:
         score = per_head.mean(0)                        # [L]
         best = max((i for i in range(L) if ok[i]), key=lambda i: (float(score[i]), grid[i]))
         st["cv_table"] = table                          # [H,K,L,V], for inspection
-        return {"grid": grid, "score": [float(s) for s in score], "score_per_head": [[float(s) for s in row] for row in per_head],
-                "best_index": best, "best_lambda": grid[best], "r": table.mean(1), "infos": infos.tolist()}
+        out = {"grid": grid, "score": [float(s) for s in score], "score_per_head": [[float(s) for s in row] for row in per_head],
+               "best_index": best, "best_lambda": grid[best], "r": table.mean(1), "infos": infos.tolist()}
+        if per_target:
+            grid_d = torch.tensor(grid, dtype=f64, device=d)
+            ok_d = torch.tensor([int(o) for o in ok], dtype=torch.int32, device=d)
+            rmean = torch.empty(H, L, V, dtype=f64, device=d)
+            choice = torch.empty(H, V, dtype=torch.int32, device=d)
+            rbest = torch.empty(H, V, dtype=f64, device=d)
+            for g in range(H):
+                check(lib.vlb_ridge_cv_select(table[g].data_ptr(), grid_d.data_ptr(), ok_d.data_ptr(), rmean[g].data_ptr(),
+                                              choice[g].data_ptr(), rbest[g].data_ptr(), K, L, V, _stream()), "vlb_ridge_cv_select")
+            idx = choice.to(torch.int64)
+            counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx))
+            packed = torch.cat([counts.to(f64).flatten(), rbest.mean().reshape(1)]).cpu()       # the one device read
+            st["cv_rmean"] = rmean                      # [H,L,V], for inspection
+            out.update(choice=choice, lambda_rows=grid_d.to(torch.float32)[idx], score_per_target=float(packed[-1]),
+                       lambda_counts=[[int(c) for c in row] for row in packed[:-1].reshape(H, L)])
+        return out
+
+    def ridge_solve_rows(self, choice, grid):
+        """The minimiser of the mse objective with one l2_lambda per target: ``choice`` int32 [H,V] on the
+        device (``ridge_cv(per_target=True)``'s), ``grid`` its grid.  For every head and every grid point some target of that
+        head chose, the head's totals are solved once with that lambda (vlb_ridge_solve_rows) and the rows that chose it are
+        written into scratch; the infos are read once; a failed solve raises with the head, the grid point and the pivot named
+        and leaves every parameter as it was.  Otherwise the fp32 masters and their bf16 copies are written as ``ridge_solve``
+        writes them.  -> ``ridge_solve``'s list with "lambda_counts" [L] in place of "l2_lambda"."""
+        st = getattr(self, "_ridge", None)
+        if st is None:
+            raise RuntimeError("head: ridge_solve_rows() before ridge_stats_begin()")
+        grid = [float(x) for x in grid]
+        H, E, V, L, d = max(1, self.G), self.E, self.V, len(grid), self.dev
+        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        if not grid or not all(math.isfinite(x) and x > 0 for x in grid):
+            raise ValueError(f"head: ridge_solve_rows: grid={grid!r}: one or more positive values are needed")
+        if not isinstance(choice, torch.Tensor) or choice.dtype != torch.int32 or choice.numel() != H * V or \
+                choice.device.type != torch.device(d).type:
+            raise ValueError(f"head: ridge_solve_rows needs choice int32 [{H},{V}] on {d}")
+        choice = choice.reshape(H, V).contiguous()
+        for g in range(H):
+            if st["n"][g] == 0:
+                raise ValueError(f"head: ridge_solve_rows: {name(g)} has no clips (N = 0): nothing to fit it to")
+        idx = choice.to(torch.int64)
+        if bool(((idx < 0) | (idx >= L)).any()):
+            raise ValueError(f"head: ridge_solve_rows: choice holds an index outside [0, {L})")
+        counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx)).tolist()
+        A = torch.empty(E, E, dtype=torch.float64, device=d)
+        X = torch.empty(V, E, dtype=torch.float64, device=d)
+        W = torch.empty(H, V, E, dtype=torch.float32, device=d)
+        b = torch.empty(H, V, dtype=torch.float32, device=d)
+        used = [(g, i) for g in range(H) for i in range(L) if counts[g][i]]
+        info = torch.zeros(len(used), dtype=torch.int32, device=d)
+        for j, (g, i) in enumerate(used):
+            # with folds the head's totals are the folds' sums added in ascending order (skip = -1)
+            Gs, Cs, szs, sys_ = self._ridge_fold_sums(st, g, -1) if "folds" in st else (st["G"][g], st["C"][g], st["sz"][g], st["sy"][g])
+            check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g], grid[i],
+                                           A.data_ptr(), X.data_ptr(), W[g].data_ptr(), b[g].data_ptr(), info[j:].data_ptr(), E, V,
+                                           choice[g].data_ptr(), i, _stream()), "vlb_ridge_solve_rows")
+        infos = info.tolist()                           # the one device read of the solves
+        for j, (g, i) in enumerate(used):
+            if infos[j] < 0:
+                raise ValueError(f"head: ridge_solve_rows: {name(g)}, l2_lambda = {grid[i]!r} (grid point {i}): target column "
+                                 f"{-infos[j] - 1} holds a NaN or Inf (info = {infos[j]}, N = {st['n'][g]}); the parameters are "
+                                 "unchanged")
+            if infos[j]:
+                raise ValueError(f"head: ridge_solve_rows: {name(g)}, l2_lambda = {grid[i]!r} (grid point {i}): pivot {infos[j]} "
+                                 f"of {E} is not positive (info = {infos[j]}, N = {st['n'][g]}); the parameters are unchanged")
+        wn, bn = "ridge_layer.linear.weight", "ridge_layer.linear.bias"
+        self.master[wn].copy_(W.view(self.master[wn].shape))
+        self.master[bn].copy_(b.view(self.master[bn].shape))
+        self.compute[wn].copy_(self.master[wn])         # fp32 -> bf16, round to nearest even, as ridge_solve
+        self.compute[bn].copy_(self.master[bn])
+        return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": 0, "lambda_counts": counts[g]}
+                for g in range(H)]

@@ -186,6 +186,10 @@ class VLBLitModuleConfig:
     ridge_lambda_grid: list[float] | None = None
     ridge_cv_folds: int = 5
     ridge_cv_block: int = 128           # contiguous clips per block, about three minutes of TRs: a choice, not a measurement
+    # ridge_lambda_grid only.  True: the same cross-validation chooses one grid point per (head, target), each row of the ridge
+    # weight is solved with its own l2_lambda and every later step's penalty is sum_v lambda_v ||W_v||^2;
+    # head.l2_lambda keeps the one global choice, for reporting.  False: one l2_lambda for the whole head
+    ridge_lambda_per_target: bool = False
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -226,6 +230,11 @@ class VLBLitModuleConfig:
             if len(set(grid)) < 2 or len(set(grid)) != len(grid):
                 raise ValueError(f"ridge_lambda_grid={grid!r}: two or more distinct values are needed")
             self.ridge_lambda_grid = grid
+        if not isinstance(self.ridge_lambda_per_target, bool):
+            raise ValueError(f"ridge_lambda_per_target={self.ridge_lambda_per_target!r}: true or false is needed")
+        if self.ridge_lambda_per_target and self.ridge_lambda_grid is None:
+            raise ValueError("ridge_lambda_per_target=True chooses each target's l2_lambda from ridge_lambda_grid: set "
+                             "ridge_lambda_grid (or leave ridge_lambda_per_target unset)")
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
@@ -356,6 +365,8 @@ class VLBLitModule(_Base):
                               loss=getattr(cfg, "loss", "mse"), readout_layers=taps, subjects=getattr(cfg, "subjects", None))
         if "_ridge_cv_lambda" in self.__dict__:      # a checkpoint loaded before the head existed: the l2_lambda its fit chose
             self.head.l2_lambda = float(self.__dict__["_ridge_cv_lambda"])
+        if "_ridge_lambda_rows" in self.__dict__:    # likewise the per-target penalties (ridge_lambda_per_target, §5.3.7)
+            self.head.set_l2_lambda_rows(self.__dict__["_ridge_lambda_rows"].to(dev, torch.float32))
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -629,7 +640,11 @@ class VLBLitModule(_Base):
         ``ridge_fit/train_mse_before`` / ``_after`` (the existing cached forward).  -> ``BrainHead.ridge_solve``'s list.
         With ``ridge_lambda_grid`` set and no explicit ``l2_lambda`` the same walk keeps the sums per fold, ``ridge_cv``
         chooses ``l2_lambda``, the solve uses it and ``head.l2_lambda`` keeps it; ``ridge_fit/cv_score``,
-        ``/cv_score_<i>`` and ``/cv_best_index`` are logged too and ``ridge_fit_result`` is ``ridge_cv``'s dict."""
+        ``/cv_score_<i>`` and ``/cv_best_index`` are logged too and ``ridge_fit_result`` is ``ridge_cv``'s dict.
+        With ``ridge_lambda_per_target`` as well, ``ridge_cv(grid, per_target=True)`` chooses per (head, target),
+        ``ridge_solve_rows`` solves each row with its own l2_lambda and ``head.set_l2_lambda_rows`` puts the vector in force
+        (DESIGN §5.3.7); ``ridge_fit/cv_score_per_target`` and ``/lambda_count_<i>`` are logged too.  An explicit
+        ``l2_lambda`` skips the grid and clears the vector."""
         cfg = self.config
         if not cfg.cache_features or cfg.loss != "mse":
             raise ValueError("fit_ridge_closed_form needs cache_features=True and loss='mse'")
@@ -664,13 +679,22 @@ class VLBLitModule(_Base):
                     first = (batch["index"], y, subject)
                     mse = [float(self.head.forward_cached(cache, *first[:2], None, subject)[1][0])]
                 self.head.ridge_stats_add(cache, batch["index"], y, subject)
-            if grid is not None:
+            if grid is not None and cfg.ridge_lambda_per_target:
+                cv = self.head.ridge_cv(grid, per_target=True)
+                out = self.head.ridge_solve_rows(cv["choice"], grid)
+                self.head.set_l2_lambda_rows(cv["lambda_rows"].flatten())
+                self._ridge_lambda_rows = self.head.l2_lambda_rows.detach().cpu()
+                self.head.l2_lambda = self._ridge_cv_lambda = float(cv["best_lambda"])       # the global choice, for reporting
+            elif grid is not None:
                 cv = self.head.ridge_cv(grid)
                 out = self.head.ridge_solve(cv["best_lambda"])
                 # every later step and validation loss uses the objective these weights minimise
                 self.head.l2_lambda = self._ridge_cv_lambda = float(cv["best_lambda"])
             else:
                 out = self.head.ridge_solve(cfg.l2_lambda if l2_lambda is None else l2_lambda)
+            if not (grid is not None and cfg.ridge_lambda_per_target) and self.head.l2_lambda_rows is not None:
+                self.head.set_l2_lambda_rows(None)               # a fit with one l2_lambda: one scalar penalty again
+                self.__dict__.pop("_ridge_lambda_rows", None)
         finally:
             ds.features_only = was
             self.head.ridge_stats_end()
@@ -679,7 +703,7 @@ class VLBLitModule(_Base):
             opt.reset_moments(["ridge_layer.linear.weight", "ridge_layer.linear.bias"])
         mse.append(float(self.head.forward_cached(cache, first[0], first[1], None, first[2])[1][0]))
         self.log("ridge_fit/n", float(sum(o["n"] for o in out)))
-        self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]))
+        self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]) if "l2_lambda" in out[0] else float(cv["best_lambda"]))
         self.log("ridge_fit/train_mse_before", mse[0])
         self.log("ridge_fit/train_mse_after", mse[1])
         if cv is not None:
@@ -687,6 +711,10 @@ class VLBLitModule(_Base):
             for i, s in enumerate(cv["score"]):
                 self.log(f"ridge_fit/cv_score_{i}", float(s))
             self.log("ridge_fit/cv_best_index", float(cv["best_index"]))
+            if "lambda_counts" in cv:
+                self.log("ridge_fit/cv_score_per_target", float(cv["score_per_target"]))
+                for i in range(len(cv["grid"])):
+                    self.log(f"ridge_fit/lambda_count_{i}", float(sum(row[i] for row in cv["lambda_counts"])))
             self.ridge_fit_result = dict(cv, solve=out)     # ridge_cv's dict, and ridge_solve's list under "solve"
             return out
         self.ridge_fit_result = out
@@ -879,6 +907,8 @@ class VLBLitModule(_Base):
         checkpoint["vlb_rng"] = self.rng_state()
         if "_ridge_cv_lambda" in self.__dict__:      # ridge_lambda_grid: the l2_lambda the closed-form fit chose (§5.3.6)
             checkpoint["vlb_ridge_l2_lambda"] = float(self.__dict__["_ridge_cv_lambda"])
+        if "_ridge_lambda_rows" in self.__dict__:    # ridge_lambda_per_target: the penalty of every row (§5.3.7)
+            checkpoint["vlb_ridge_l2_lambda_rows"] = self.__dict__["_ridge_lambda_rows"].clone()
 
     def on_load_checkpoint(self, checkpoint: dict) -> None:
         if "vlb_rng" in checkpoint:
@@ -887,6 +917,10 @@ class VLBLitModule(_Base):
             self._ridge_cv_lambda = float(checkpoint["vlb_ridge_l2_lambda"])
             if getattr(self, "head", None) is not None:
                 self.head.l2_lambda = self._ridge_cv_lambda
+        if "vlb_ridge_l2_lambda_rows" in checkpoint:
+            self._ridge_lambda_rows = checkpoint["vlb_ridge_l2_lambda_rows"].detach().to("cpu", torch.float32).clone()
+            if getattr(self, "head", None) is not None:
+                self.head.set_l2_lambda_rows(self._ridge_lambda_rows.to(self.head.dev))
 
     def state_dict(self, *args, **kwargs):
         """Trainables only, upstream / peft names (what a Lightning ModelCheckpoint stores for this module; the reference saves

@@ -93,6 +93,8 @@ def trainable_state(module, step: int, to_host: bool = True) -> dict | None:
     state["rng"] = module.rng_state()
     if "_ridge_cv_lambda" in module.__dict__:      # ridge_lambda_grid: the l2_lambda the closed-form fit chose
         state["ridge_l2_lambda"] = float(module.__dict__["_ridge_cv_lambda"])
+    if "_ridge_lambda_rows" in module.__dict__:    # ridge_lambda_per_target: the penalty of every row
+        state["ridge_l2_lambda_rows"] = module.__dict__["_ridge_lambda_rows"].clone()
     return state
 
 
@@ -163,6 +165,9 @@ def load_trainable_checkpoint(module, path):
         module.set_rng_state(st["rng"])
     if "ridge_l2_lambda" in st:
         module._ridge_cv_lambda = module.head.l2_lambda = float(st["ridge_l2_lambda"])
+    if "ridge_l2_lambda_rows" in st:
+        module._ridge_lambda_rows = st["ridge_l2_lambda_rows"].detach().to("cpu", torch.float32).clone()
+        module.head.set_l2_lambda_rows(module._ridge_lambda_rows.to(module.head.dev))
     return st.get("global_step", 0)
 
 
