@@ -463,6 +463,19 @@ int vlb_grad_sumsq(const float* g, int64_t n, float* sumsq, float* ws, void* str
 int vlb_adamw_step(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
                    float max_norm, void* stream);
+/* vlb_adamw_step with per-range learning rates and weight decay, ONE launch (litmodule.config.optimizer_groups).  The
+ * reference has one param group (configure_optimizers, src/litmodule/videollama2_vlb_litmodule.py:357-363) and switches
+ * upstream's hook for a separate connector rate off (model.config.mm_projector_lr = None, :92); this is what lets the
+ * head, LoRA A / B, norms and biases or the connector train at rates of their own.
+ * bounds[0 .. n_ranges] (int64, DEVICE; ascending, bounds[0] = 0, bounds[n_ranges] = n, every entry a multiple of 8) cuts
+ * the store into ranges, group_of[r] (int32, DEVICE) in [0, n_groups) names range r's group; lr[g] / weight_decay[g] are
+ * HOST arrays of n_groups <= 8 entries, passed to the kernel by value (no upload, no sync).  Per element bit-identical to
+ * vlb_adamw_step on each range with its group's (lr, weight_decay) and the same sumsq / max_norm / step.
+ * n % 8 == 0; master, grad, m, v 16-byte and param_bf16 8-byte aligned. */
+int vlb_adamw_step_groups(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n,
+                          const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                          const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                          const float* sumsq, float max_norm, void* stream);
 /* gradient accumulation over a flat store: acc[i] = first ? g[i] : acc[i] + g[i]  (fp32 accumulator; `first` replaces a
  * memset).  Any n > 0; acc and g 16-byte aligned (the bf16 g: 8-byte).  With sumsq != NULL the same pass also adds
  * sum(acc^2) of the RESULT to sumsq[0] through ws (vlb_sumsq_ws_floats() floats): bit-identical to vlb_grad_sumsq on the
@@ -506,6 +519,11 @@ int vlb_grad_sumsq_bf16(const void* g, int64_t n, float* sumsq, float* ws, void*
 int vlb_adamw_step_g16(float* master, void* param_bf16, const void* grad_bf16, float* m, float* v, int64_t n, float lr,
                        float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq, float max_norm,
                        void* stream);
+/* vlb_adamw_step_groups on bf16 gradients (grad_bf16 8-byte aligned); per element bit-identical to vlb_adamw_step_g16 */
+int vlb_adamw_step_groups_g16(float* master, void* param_bf16, const void* grad_bf16, float* m, float* v, int64_t n,
+                              const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                              const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                              const float* sumsq, float max_norm, void* stream);
 /* STC connector backward pieces: depthwise 3x3 weight gradient [9,C]; squeeze-excite gate-logit and input gradients;
  * inverse of vlb_im2col3d_k2s2p1 (every input element sits in exactly one 2x2x2 window) */
 int64_t vlb_dwconv3x3_bwd_w_ws_floats(int N, int H, int C);

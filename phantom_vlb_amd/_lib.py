@@ -85,6 +85,7 @@ SIGNATURES = {
     "vlb_sumsq_ws_floats": [],
     "vlb_grad_sumsq": [P, L, P, P, P],
     "vlb_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, F, P],
+    "vlb_adamw_step_groups": [P, P, P, P, P, L, P, P, I, P, P, I, F, F, F, I, P, F, P],
     "vlb_grad_accum": [P, P, L, I, P, P, P],
     "vlb_grad_accum_bf16": [P, P, L, I, P, P, P],
     "vlb_dropout_keep_scale": [P, L, F, ctypes.c_uint32, P],
@@ -101,6 +102,7 @@ SIGNATURES = {
     "vlb_embed_grad": [P, I, P, P, P, I, P, I, P],
     "vlb_grad_sumsq_bf16": [P, L, P, P, P],
     "vlb_adamw_step_g16": [P, P, P, P, P, L, F, F, F, F, F, I, P, F, P],
+    "vlb_adamw_step_groups_g16": [P, P, P, P, P, L, P, P, I, P, P, I, F, F, F, I, P, F, P],
     "vlb_dwconv3x3_bwd_w_ws_floats": [I, I, I],
     "vlb_dwconv3x3_bwd_w": [P, P, P, P, I, I, I, I, P],
     "vlb_se_bwd_gate": [P, P, P, P, I, I, I, P],

@@ -2,6 +2,7 @@
 // stencils, splice, weight mask, optimiser).  All use 16-byte per-lane accesses on bf16 data and
 // fp32 arithmetic; none of them is reshaped into a GEMM.
 #include "common.hpp"
+#include "adamw_groups.hpp"
 
 namespace {
 
@@ -925,6 +926,14 @@ extern "C" int vlb_adamw_step(float* master, void* param_bf16, const float* grad
                      grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, sumsq, max_norm);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
+}
+// one launch for a store whose ranges have their own lr / weight_decay (adamw_groups.hpp); fp32 gradients, 16-byte lanes
+extern "C" int vlb_adamw_step_groups(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n,
+                                     const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                                     const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                                     const float* sumsq, float max_norm, void* stream) {
+  return adamw_groups_launch<float>(master, param_bf16, grad, m, v, n, bounds, group_of, n_ranges, lr, weight_decay, n_groups, beta1,
+                                    beta2, eps, step, sumsq, max_norm, stream);
 }
 extern "C" int vlb_grad_accum(float* acc, const float* g, int64_t n, int first, float* sumsq, float* ws, void* stream) {
   VLB_REQUIRE(n > 0 && acc && g && (sumsq == nullptr || ws) && ((uintptr_t)acc % 16) == 0 && ((uintptr_t)g % 16) == 0,

@@ -14,6 +14,7 @@
 //   vlb_se_bwd             squeeze-excite: d gate logits and d input of x * sigmoid(s)
 //   vlb_col2im3d_k2s2p1    inverse of the Conv3d im2col (every input element sits in exactly one window)
 #include "common.hpp"
+#include "adamw_groups.hpp"
 
 namespace {
 __device__ __forceinline__ void ld8(const bf16* p, float (&v)[8]) {
@@ -625,6 +626,15 @@ extern "C" int vlb_adamw_step_g16(float* master, void* param_bf16, const void* g
                      m, v, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, sumsq, max_norm);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
+}
+
+// the same with per-range lr / weight_decay (adamw_groups.hpp), one launch
+extern "C" int vlb_adamw_step_groups_g16(float* master, void* param_bf16, const void* grad_bf16, float* m, float* v, int64_t n,
+                                         const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                                         const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                                         const float* sumsq, float max_norm, void* stream) {
+  return adamw_groups_launch<bf16>(master, param_bf16, (const bf16*)grad_bf16, m, v, n, bounds, group_of, n_ranges, lr, weight_decay,
+                                   n_groups, beta1, beta2, eps, step, sumsq, max_norm, stream);
 }
 
 extern "C" int64_t vlb_dwconv3x3_bwd_w_ws_floats(int N, int H, int C) { return (int64_t)N * H * 9 * C; }

@@ -26,6 +26,7 @@ from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
 from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers, check_subjects
 from .optim import VlbAdamW
+from .optim_groups import assign_groups, group_specs, normalize_optimizer_groups
 
 
 def _lightning():
@@ -190,6 +191,11 @@ class VLBLitModuleConfig:
     # weight is solved with its own l2_lambda and every later step's penalty is sum_v lambda_v ||W_v||^2;
     # head.l2_lambda keeps the one global choice, for reporting.  False: one l2_lambda for the whole head
     ridge_lambda_per_target: bool = False
+    # learning rate / weight decay per group of trainables: up to 7 entries {params: [fnmatch pattern, ...],
+    # lr_scale: float = 1.0, weight_decay: float | None = None} over the names trainable_named_parameters() yields; the first
+    # entry with a matching pattern takes a tensor, what no entry matches keeps lr / weight_decay; lr_scale multiplies lr (the
+    # scheduler then drives every group), weight_decay None = the configured one.  None: one group, as the reference (:357-363)
+    optimizer_groups: list[dict] | None = None
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -235,6 +241,7 @@ class VLBLitModuleConfig:
         if self.ridge_lambda_per_target and self.ridge_lambda_grid is None:
             raise ValueError("ridge_lambda_per_target=True chooses each target's l2_lambda from ridge_lambda_grid: set "
                              "ridge_lambda_grid (or leave ridge_lambda_per_target unset)")
+        self.optimizer_groups = normalize_optimizer_groups(self.optimizer_groups)      # names are checked by configure_optimizers
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
@@ -941,8 +948,12 @@ class VLBLitModule(_Base):
             self.flat = FlatTrainables(self)          # masters / bf16 copies / grads / moments -> flat buffers
         named = self.trainable_named_parameters()
         flats = [self.flat] + ([self.full.flat] if self.full is not None else [])
+        groups = None
+        if cfg.optimizer_groups is not None:      # per-group rates: names -> groups here, where the names exist
+            assignment = assign_groups([n for n, _ in named], cfg.optimizer_groups)
+            groups = (assignment, group_specs(cfg.optimizer_groups, cfg.lr, cfg.weight_decay))
         self.optimizer = VlbAdamW(named, flats, lr=cfg.lr, betas=tuple(cfg.betas), eps=cfg.eps,
-                                  weight_decay=cfg.weight_decay, max_norm=cfg.gradient_clip_val)
+                                  weight_decay=cfg.weight_decay, max_norm=cfg.gradient_clip_val, groups=groups)
         if self.lora is not None:
             self.optimizer.post_step.append(self.lora.refresh)
         if self.full is not None:

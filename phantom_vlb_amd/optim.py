@@ -17,32 +17,61 @@ buffers, and ``accumulate(index_in_window, is_last)`` adds them into one fp32 ac
 ``vlb_grad_accum_bf16``; allocated on first use, never at k = 1).  The ``step()`` that closes the window reads the
 accumulators instead of the gradient buffers; the accumulators are not part of ``state_dict()`` (a checkpoint is taken on a
 window boundary).
+
+Parameter groups (``litmodule.config.optimizer_groups``): with ``groups`` the optimiser has one torch
+``param_groups`` entry per non-empty group, each with its own ``lr`` / ``weight_decay`` (schedulers and learning-rate monitors
+see them like any torch optimiser's), every store gets a range table (``optim_groups.group_ranges``; rebuilt for a rank's slices
+when data parallelism is attached) and the step makes one ``vlb_adamw_step_groups`` / ``_g16`` launch per store.  Without
+``groups`` nothing of this exists: one group, no table, the two launches above.
 """
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
 from ._lib import check, lib
+from .optim_groups import MAX_GROUPS, group_ranges
 from .ops import _stream
 
 
 class VlbAdamW(torch.optim.Optimizer):
     """``flat``: one flat store or a list of them (head + LoRA: fp32 gradients; ``fullft.FlatBackbone``: bf16
-    gradients, attribute ``grad_bf16``).  One clip norm over all of them, one AdamW launch per store."""
+    gradients, attribute ``grad_bf16``).  One clip norm over all of them, one AdamW launch per store.
+
+    ``groups``: None (one group: ``lr`` / ``weight_decay`` for everything), or ``(assignment, specs)`` - ``assignment`` maps
+    every parameter name to an index into ``specs``, a list of ``{"name", "lr", "weight_decay"}`` (index 0: the default
+    group).  Groups no parameter is assigned to are dropped; the rest become ``param_groups`` in that order."""
 
     def __init__(self, named_params, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 max_norm: float = 0.0):
+                 max_norm: float = 0.0, groups=None):
         named_params = list(named_params)
         self.names = [n for n, _ in named_params]
+        self.named_params = named_params
         params = [p for _, p in named_params]
         for p in params:
             assert p.dtype == torch.float32 and p.is_cuda and p.is_contiguous()
+        self.group_names = ["default"]
+        self.group_of_name = None     # name -> index into param_groups; None: one group, no table, the ungrouped kernels
+        if groups is not None:
+            assignment, specs = groups
+            used = sorted({int(assignment[n]) for n in self.names})
+            if len(used) > MAX_GROUPS:
+                raise ValueError(f"{len(used)} optimiser groups: at most {MAX_GROUPS} are supported")
+            if len(used) > 1:
+                self.group_of_name = {n: used.index(int(assignment[n])) for n in self.names}
+                self.group_names = [str(specs[k]["name"]) for k in used]
+                params = [dict(params=[p for n, p in named_params if self.group_of_name[n] == i], lr=float(specs[k]["lr"]),
+                               weight_decay=float(specs[k]["weight_decay"])) for i, k in enumerate(used)]      # one dict per group
+            elif used:                # everything in one group: that group's rates, the parent's path
+                lr, weight_decay = float(specs[used[0]]["lr"]), float(specs[used[0]]["weight_decay"])
+                self.group_names = [str(specs[used[0]]["name"])]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_norm = float(max_norm)
         self.flats = list(flat) if isinstance(flat, (list, tuple)) else [flat]
         self.flat = self.flats[0]         # head (+ LoRA) store
         self.shardeds = [None] * len(self.flats)      # parallel.ShardedFlatState per store under data parallelism
-        dev = params[0].device
+        dev = named_params[0][1].device
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.sumsq_ws = torch.zeros(max(lib.vlb_sumsq_ws_floats(), 1024), dtype=torch.float32, device=dev)
         self.step_count = 0
@@ -51,6 +80,23 @@ class VlbAdamW(torch.optim.Optimizer):
         self._acc_live = False        # accumulate() ran since the last step(): step() consumes the accumulators
         self._acc_sumsq = False       # ... and the last accumulate() left the clip norm's sum of squares in self.sumsq
         self._acc_pos = None          # (index_in_window, is_last) announced by begin_micro_batch (data parallelism)
+        self.tables = None            # groups only: per store (bounds int64, group_of int32) on the device, built and uploaded once
+        if self.group_of_name is not None:
+            self.tables = [self._range_table(i) for i in range(len(self.flats))]
+            self._lr_arg = (ctypes.c_float * MAX_GROUPS)()
+            self._wd_arg = (ctypes.c_float * MAX_GROUPS)()
+
+    def _range_table(self, i: int):
+        """Store i's range table in the coordinates of the buffer its AdamW launch is handed: the flat store, or (data
+        parallelism) this rank's concatenated 1/world slices.  Built on the host, uploaded once."""
+        f, sh = self.flats[i], self._active(i)
+        prefix = "backbone." if i >= 1 else ""             # the backbone store's own names lack the prefix
+        assign = {n: self.group_of_name[prefix + n] for n in f.offsets}
+        shard = (sh.segments, sh.shard_off, sh.world, sh.rank) if sh is not None else None
+        bounds, group_of = group_ranges(f.offsets, f.numel, assign, shard)
+        assert int(bounds[-1]) == (sh.numel if sh is not None else f.numel)
+        dev = f.compute.device
+        return bounds.to(dev), group_of.to(dev)
 
     @property
     def sharded(self):
@@ -62,6 +108,8 @@ class VlbAdamW(torch.optim.Optimizer):
         i = [k for k, f in enumerate(self.flats) if f is state.flat]
         assert i, "attach_sharded: the state wraps a flat store this optimiser does not own"
         self.shardeds[i[0]] = state
+        if self.tables is not None:
+            self.tables[i[0]] = self._range_table(i[0])
 
     def full_state(self, name: str, index: int = 0):
         """Full-size flat fp32 buffer 'master' | 'm' | 'v' of store `index` (gathered from the shards under data parallelism)."""
@@ -239,17 +287,35 @@ class VlbAdamW(torch.optim.Optimizer):
             active = [sh for sh in self.shardeds if sh is not None]
             if active:
                 active[0].all_reduce_scalar(self.sumsq)      # the clip norm covers every rank's slices
-        for b, (g, bf) in zip(bufs, grads):
-            fn = lib.vlb_adamw_step_g16 if bf else lib.vlb_adamw_step
-            check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
-                     float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.step_count,
-                     self.sumsq.data_ptr(), self.max_norm, st), "vlb_adamw_step")
+        if self.tables is not None:          # more than one group: one grouped launch per store
+            self._step_groups(bufs, grads, st)
+        else:
+            for b, (g, bf) in zip(bufs, grads):
+                fn = lib.vlb_adamw_step_g16 if bf else lib.vlb_adamw_step
+                check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
+                         float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.step_count,
+                         self.sumsq.data_ptr(), self.max_norm, st), "vlb_adamw_step")
         for sh in self.shardeds:
             if sh is not None:
                 sh.gather_compute()
         for fn in self.post_step:
             fn()
         return loss
+
+    def _step_groups(self, bufs, grads, st):
+        """More than one group: one grouped launch per store; every group's current lr / weight_decay goes by value."""
+        G = len(self.param_groups)
+        for k, pg in enumerate(self.param_groups):
+            self._lr_arg[k], self._wd_arg[k] = float(pg["lr"]), float(pg["weight_decay"])
+        group = self.param_groups[0]
+        b1, b2 = group["betas"]
+        for b, (g, bf), (bounds, group_of) in zip(bufs, grads, self.tables):
+            assert int(bounds.numel()) >= 2 and b.numel % 8 == 0
+            fn = lib.vlb_adamw_step_groups_g16 if bf else lib.vlb_adamw_step_groups
+            check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
+                     bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), self._lr_arg, self._wd_arg, G,
+                     float(b1), float(b2), float(group["eps"]), self.step_count, self.sumsq.data_ptr(), self.max_norm, st),
+                  "vlb_adamw_step_groups")
 
     def grad_norm(self) -> float:
         """Global gradient norm of the last step (host sync; for logging only)."""

@@ -360,7 +360,7 @@ def attach_data_parallel(module, optimizer, group=None, comm=None, force_collect
         if sb.full_shard:
             full.enter_full_shard(sb)
             empty = torch.empty(0, dtype=torch.float32, device=sb.master.device)
-            for n, p_ in zip(optimizer.names, optimizer.param_groups[0]["params"]):
+            for n, p_ in optimizer.named_params:      # (every param group's: optimizer_groups may have split them)
                 if n.startswith("backbone."):
                     p_.data = empty            # the optimiser's handles were views of the released full-size master
             torch.cuda.empty_cache()

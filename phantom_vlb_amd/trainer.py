@@ -39,20 +39,30 @@ class CSVLogger:
             w.writerows(self.rows)
 
 
+def lr_logs(opt, key: str) -> dict:
+    """``{key: group 0's learning rate}``; an optimiser with several param groups (``optimizer_groups``) adds every group's
+    under ``key/pg1``, ``key/pg2`` ... (Lightning's LearningRateMonitor naming: 1-based, pg1 = group 0)."""
+    out = {key: opt.param_groups[0]["lr"]}
+    if len(opt.param_groups) > 1:
+        out.update({f"{key}/pg{k + 1}": pg["lr"] for k, pg in enumerate(opt.param_groups)})
+    return out
+
+
 class LearningRateMonitor:
     """``lightning.pytorch.callbacks.LearningRateMonitor(logging_interval=...)`` (reference train.py:28): logs the
-    optimiser's learning rate under Lightning's key ``lr-AdamW`` every epoch (or every logged step)."""
+    optimiser's learning rate under Lightning's key ``lr-AdamW`` every epoch (or every logged step); with several param
+    groups also ``lr-AdamW/pg1`` ..."""
 
     def __init__(self, logging_interval="epoch", **kw):
         self.logging_interval = logging_interval
 
     def on_train_epoch_start(self, trainer, module):
         if self.logging_interval != "step":
-            trainer._log({"lr-AdamW": module.optimizer.param_groups[0]["lr"]})
+            trainer._log(lr_logs(module.optimizer, "lr-AdamW"))
 
     def on_train_batch_start(self, trainer, module, batch, batch_idx):
         if self.logging_interval == "step" and trainer.global_step % trainer.log_every_n_steps == 0:
-            trainer._log({"lr-AdamW": module.optimizer.param_groups[0]["lr"]})
+            trainer._log(lr_logs(module.optimizer, "lr-AdamW"))
 
 
 def trainable_state(module, step: int, to_host: bool = True) -> dict | None:
@@ -86,7 +96,7 @@ def trainable_state(module, step: int, to_host: bool = True) -> dict | None:
             sh.release_staging()           # FULL_SHARD keeps no standing full-size master
     if opt is not None:
         state.update(opt_step=opt.step_count, flat_offsets={n: (o, k) for n, (o, k, _) in module.flat.offsets.items()},
-                     lr=opt.param_groups[0]["lr"])
+                     lr=opt.param_groups[0]["lr"], lrs=[pg["lr"] for pg in opt.param_groups], group_names=list(opt.group_names))
     sch = getattr(module, "scheduler", None)
     if sch is not None:
         state["lr_scheduler"] = sch.state_dict()
@@ -143,8 +153,14 @@ def load_trainable_checkpoint(module, path):
     """Resume: trainables, Adam moments and step count, LR-scheduler state, and the dropout counters / generator
     (LoRA's counter-based seed, the head's mask generator) - so the resumed run replays neither LR nor masks."""
     st = torch.load(path, map_location="cpu", weights_only=False)
-    module.load_trainable_state_dict(st["state_dict"])
     opt = getattr(module, "optimizer", None)
+    if opt is not None and "exp_avg" in st:
+        saved = len(st["lrs"]) if "lrs" in st else 1            # (checkpoints from before optimizer_groups: one group)
+        if saved != len(opt.param_groups):
+            raise ValueError(f"{path}: the checkpoint was written with {saved} optimiser group(s) {st.get('group_names', ['default'])}, "
+                             f"this optimiser has {len(opt.param_groups)} {list(opt.group_names)}: resume with the same "
+                             "litmodule.config.optimizer_groups")
+    module.load_trainable_state_dict(st["state_dict"])
     if opt is not None and "exp_avg" in st:
         opt.load_full_state("master", module.flat.master)
         opt.load_full_state("m", st["exp_avg"])
@@ -160,7 +176,8 @@ def load_trainable_checkpoint(module, path):
     if sch is not None and "lr_scheduler" in st:
         sch.load_state_dict(st["lr_scheduler"])
         if opt is not None:
-            opt.param_groups[0]["lr"] = st["lr"]
+            for pg, lr in zip(opt.param_groups, st["lrs"] if "lrs" in st else [st["lr"]]):
+                pg["lr"] = lr
     if "rng" in st:
         module.set_rng_state(st["rng"])
     if "ridge_l2_lambda" in st:
@@ -352,7 +369,7 @@ class Trainer:
                     self.global_step += 1
                     if self.global_step % self.log_every_n_steps == 0:
                         shown = float(loss) if k == 1 else sum(float(x) for x in window) / len(window)
-                        self._log({"train/brain_loss": shown, "lr": opt.param_groups[0]["lr"], "epoch": epoch,
+                        self._log({"train/brain_loss": shown, **lr_logs(opt, "lr"), "epoch": epoch,
                                    "elapsed_s": time.time() - t0})
                     window = []
                     if val_due:
