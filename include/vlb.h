@@ -476,6 +476,21 @@ int vlb_adamw_step_groups(float* master, void* param_bf16, const float* grad, fl
                           const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
                           const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
                           const float* sumsq, float max_norm, void* stream);
+/* vlb_adamw_step that also keeps an exponential moving average of the masters, in the same launch
+ * (litmodule.config.ema_decay): after the update, in fp32, ema[i] = (ema_decay * ema[i]) + ((1 - ema_decay) * master[i]) with
+ * master[i] the value just written, 1 - ema_decay computed once, and the two products and the sum each rounded on their own
+ * (no fused multiply-add), so a float32 restatement on the host reproduces ema bit for bit.  ema_decay goes by value: a
+ * warm-up schedule changes it every step.  master, m, v and the bf16 copy are bit-identical to vlb_adamw_step's.
+ * n % 8 == 0; master, grad, m, v, ema 16-byte and param_bf16 8-byte aligned; 0 <= ema_decay < 1.  fp32 gradients only. */
+int vlb_adamw_step_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq, float max_norm,
+                       float ema_decay, void* stream);
+/* vlb_adamw_step_groups with the same moving average: the table contract of vlb_adamw_step_groups, the ema contract of
+ * vlb_adamw_step_ema; master, m, v and the bf16 copy are bit-identical to vlb_adamw_step_groups'. */
+int vlb_adamw_step_groups_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
+                              const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                              const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                              const float* sumsq, float max_norm, float ema_decay, void* stream);
 /* gradient accumulation over a flat store: acc[i] = first ? g[i] : acc[i] + g[i]  (fp32 accumulator; `first` replaces a
  * memset).  Any n > 0; acc and g 16-byte aligned (the bf16 g: 8-byte).  With sumsq != NULL the same pass also adds
  * sum(acc^2) of the RESULT to sumsq[0] through ws (vlb_sumsq_ws_floats() floats): bit-identical to vlb_grad_sumsq on the

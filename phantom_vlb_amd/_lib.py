@@ -86,6 +86,8 @@ SIGNATURES = {
     "vlb_grad_sumsq": [P, L, P, P, P],
     "vlb_adamw_step": [P, P, P, P, P, L, F, F, F, F, F, I, P, F, P],
     "vlb_adamw_step_groups": [P, P, P, P, P, L, P, P, I, P, P, I, F, F, F, I, P, F, P],
+    "vlb_adamw_step_ema": [P, P, P, P, P, P, L, F, F, F, F, F, I, P, F, F, P],
+    "vlb_adamw_step_groups_ema": [P, P, P, P, P, P, L, P, P, I, P, P, I, F, F, F, I, P, F, F, P],
     "vlb_grad_accum": [P, P, L, I, P, P, P],
     "vlb_grad_accum_bf16": [P, P, L, I, P, P, P],
     "vlb_dropout_keep_scale": [P, L, F, ctypes.c_uint32, P],

@@ -15,6 +15,14 @@
 //     sync); the group's pair is picked by eight selects on SGPR operands - a dynamic index would put the struct in scratch.
 // Memory access is adamw_g16_kernel's: 16-byte lane accesses on master / m / v (and an fp32 gradient), 8 bytes on the bf16
 // copy (and a bf16 gradient), two independent chunks in flight per loop trip, the same grid.  No atomics, vector stores only.
+//
+// EMA (vlb_adamw_step_ema / vlb_adamw_step_groups_ema in ops.hip, fp32 gradients; litmodule.config.ema_decay):
+// the same loop with one more fp32 array.  `ema` is loaded with p / m / v / g of its trip (16-byte lanes, the prefetch of the
+// next trip included) and ema' = (d * ema) + (omd * p') is stored with them, p' being the master just computed and
+// omd = 1 - d; the three operations keep their own roundings (adamw_groups4).  d arrives by value: it changes per step
+// during warm-up.  It is adamw_groups_kernel itself with the EMA switched on at compile time; TABLE = false is the ungrouped
+// call: one (lr, weight_decay) pair, no table, no search.  The kernels without EMA compile to what they were: every EMA
+// statement sits behind `if constexpr`, and the EMA's arguments are a parameter pack that is empty for them.
 #pragma once
 #include "common.hpp"
 
@@ -59,10 +67,14 @@ __device__ __forceinline__ void adamw_group_rates(const AdamwGroupRates& r, int 
 // Which product keeps its rounding is visible in the last bit, so each grouped kernel spells out the operations of the parent
 // it stands in for (G16 = the gradient type's parent) with contraction switched off, instead of leaving the choice to a third
 // run of the same heuristic.  tests/test_gpu_adamw_groups.py holds both to torch.equal against their parents.
-template <bool G16>
+// EMA: ema' = (d * ema) + (omd * p') behind the update, one product, one product, one sum, each rounded to fp32 on its own
+// (contraction is off in this function), so that a float32 restatement on the host reproduces it bit for bit - a fused
+// multiply-add would keep one product unrounded.
+template <bool G16, bool EMA = false>
 __device__ __forceinline__ void adamw_groups4(float* __restrict__ p, bf16* __restrict__ pb, float* __restrict__ m, float* __restrict__ v,
                                               int64_t i4, float clip, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                              float bc2_sqrt, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv) {
+                                              float bc2_sqrt, f32x4 pv, f32x4 mv, f32x4 vv, f32x4 gv, float* __restrict__ ema = nullptr,
+                                              f32x4 ev = f32x4{}, float d = 0.f, float omd = 0.f) {
 #pragma clang fp contract(off)
   bf16x4 o;
   const float decay = __builtin_fmaf(-lr, wd, 1.f), lr_bc = lr / bc1, ob1 = 1.f - b1, ob2 = 1.f - b2;
@@ -74,19 +86,37 @@ __device__ __forceinline__ void adamw_groups4(float* __restrict__ p, bf16* __res
     const float q = (lr_bc * mi) / (sqrtf(vi) / bc2_sqrt + eps);
     const float pi = __builtin_fmaf(decay, pv[k], -q);
     pv[k] = pi; mv[k] = mi; vv[k] = vi; o[k] = (bf16)pi;
+    if constexpr (EMA) ev[k] = (d * ev[k]) + (omd * pi);
   }
   *reinterpret_cast<f32x4*>(p + i4 * 4) = pv;
   *reinterpret_cast<f32x4*>(m + i4 * 4) = mv;
   *reinterpret_cast<f32x4*>(v + i4 * 4) = vv;
   if (pb) *reinterpret_cast<bf16x4*>(pb + i4 * 4) = o;
+  if constexpr (EMA) *reinterpret_cast<f32x4*>(ema + i4 * 4) = ev;
 }
 
-template <typename G, bool LDS>
+// The EMA's two kernel arguments.  They reach adamw_groups_kernel as a trailing parameter PACK: empty for the kernels without
+// EMA, whose signature, kernel-argument layout and generated code therefore stay what they were before the EMA existed.
+struct AdamwEma {
+  float* ema;
+  float d;
+};
+__device__ __forceinline__ AdamwEma adamw_ema_arg() { return AdamwEma{nullptr, 0.f}; }
+__device__ __forceinline__ AdamwEma adamw_ema_arg(AdamwEma e) { return e; }
+
+// TABLE = false (EMA only, LDS = false): no table, rates.lr[0] / rates.wd[0] for every element; bounds / group_of / n_ranges
+// are not read.  E: nothing, or one AdamwEma.
+template <typename G, bool LDS, bool TABLE = true, typename... E>
 __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p, bf16* __restrict__ pb, const G* __restrict__ g,
                                                            float* __restrict__ m, float* __restrict__ v, int64_t n4,
                                                            const int64_t* __restrict__ bounds, const int32_t* __restrict__ group_of,
                                                            int n_ranges, AdamwGroupRates rates, float b1, float b2, float eps, float bc1,
-                                                           float bc2_sqrt, const float* __restrict__ sumsq, float max_norm) {
+                                                           float bc2_sqrt, const float* __restrict__ sumsq, float max_norm, E... ema_arg) {
+  constexpr bool EMA = sizeof...(E) == 1;
+  static_assert(sizeof...(E) <= 1 && (TABLE || !LDS), "one AdamwEma at most; no table: nothing to stage");
+  const AdamwEma ea = adamw_ema_arg(ema_arg...);
+  float* __restrict__ ema = ea.ema;
+  const float d = ea.d, omd = 1.f - d;
   __shared__ int64_t s_bounds[LDS ? kAdamwLdsRanges : 1];
   __shared__ int32_t s_group[LDS ? kAdamwLdsRanges : 1];
   float clip = 1.f;
@@ -94,13 +124,14 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   // first trip's loads go out before the table is staged: the staging and the search run under their latency
-  f32x4 p0{}, m0{}, v0{}, g0{}, p1{}, m1{}, v1{}, g1{};
-  auto load = [&](int64_t a, f32x4& pp, f32x4& mm, f32x4& vv, f32x4& gg) {
+  f32x4 p0{}, m0{}, v0{}, g0{}, e0{}, p1{}, m1{}, v1{}, g1{}, e1{};
+  auto load = [&](int64_t a, f32x4& pp, f32x4& mm, f32x4& vv, f32x4& gg, f32x4& ee) {
     pp = *reinterpret_cast<const f32x4*>(p + a * 4); mm = *reinterpret_cast<const f32x4*>(m + a * 4);
     vv = *reinterpret_cast<const f32x4*>(v + a * 4); gg = adamw_ld_grad4(g + a * 4);
+    if constexpr (EMA) ee = *reinterpret_cast<const f32x4*>(ema + a * 4);
   };
-  if (i < n4) load(i, p0, m0, v0, g0);
-  if (i + stride < n4) load(i + stride, p1, m1, v1, g1);
+  if (i < n4) load(i, p0, m0, v0, g0, e0);
+  if (i + stride < n4) load(i + stride, p1, m1, v1, g1, e1);
   if (LDS) {                      // (entries 0 .. n_ranges - 1 suffice: the search never reads bounds[n_ranges])
     for (int k = threadIdx.x; k < n_ranges; k += 256) { s_bounds[k] = bounds[k]; s_group[k] = group_of[k]; }
     __syncthreads();
@@ -111,13 +142,17 @@ __global__ __launch_bounds__(256) void adamw_groups_kernel(float* __restrict__ p
     const int64_t j = i + stride;
     const bool two = j < n4;
     float lr0, wd0, lr1 = 0.f, wd1 = 0.f;
-    adamw_group_rates(rates, sg[adamw_find_range(sb, n_ranges, i * 4)], lr0, wd0);
-    if (two) adamw_group_rates(rates, sg[adamw_find_range(sb, n_ranges, j * 4)], lr1, wd1);
-    adamw_groups4<sizeof(G) == 2>(p, pb, m, v, i, clip, lr0, b1, b2, eps, wd0, bc1, bc2_sqrt, p0, m0, v0, g0);
-    if (two) adamw_groups4<sizeof(G) == 2>(p, pb, m, v, j, clip, lr1, b1, b2, eps, wd1, bc1, bc2_sqrt, p1, m1, v1, g1);
+    if constexpr (TABLE) {
+      adamw_group_rates(rates, sg[adamw_find_range(sb, n_ranges, i * 4)], lr0, wd0);
+      if (two) adamw_group_rates(rates, sg[adamw_find_range(sb, n_ranges, j * 4)], lr1, wd1);
+    } else {
+      lr0 = lr1 = rates.lr[0]; wd0 = wd1 = rates.wd[0];
+    }
+    adamw_groups4<sizeof(G) == 2, EMA>(p, pb, m, v, i, clip, lr0, b1, b2, eps, wd0, bc1, bc2_sqrt, p0, m0, v0, g0, ema, e0, d, omd);
+    if (two) adamw_groups4<sizeof(G) == 2, EMA>(p, pb, m, v, j, clip, lr1, b1, b2, eps, wd1, bc1, bc2_sqrt, p1, m1, v1, g1, ema, e1, d, omd);
     const int64_t ni = i + 2 * stride;
-    if (ni < n4) load(ni, p0, m0, v0, g0);
-    if (ni + stride < n4) load(ni + stride, p1, m1, v1, g1);
+    if (ni < n4) load(ni, p0, m0, v0, g0, e0);
+    if (ni + stride < n4) load(ni + stride, p1, m1, v1, g1, e1);
   }
 }
 
@@ -148,6 +183,47 @@ static int adamw_groups_launch(float* master, void* param_bf16, const G* grad, f
   else
     hipLaunchKernelGGL((adamw_groups_kernel<G, false>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), master, (bf16*)param_bf16,
                        grad, m, v, n4, bounds, group_of, n_ranges, rates, beta1, beta2, eps, bc1, bc2s, sumsq, max_norm);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// host side of vlb_adamw_step_ema (TABLE = false: one (lr, weight_decay) pair, bounds / group_of / n_ranges unused) and of
+// vlb_adamw_step_groups_ema (TABLE = true: adamw_groups_launch's table contract); fp32 gradients.  A template, so that only
+// the source file that calls it (ops.hip) carries the kernels.
+template <bool TABLE>
+static int adamw_ema_launch(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
+                            const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr, const float* weight_decay,
+                            int n_groups, float beta1, float beta2, float eps, int step, const float* sumsq, float max_norm,
+                            float ema_decay, void* stream) {
+  VLB_REQUIRE(n > 0 && n % 8 == 0 && master && grad && m && v && ema && step >= 1, "adamw_ema: n must be a positive multiple of 8");
+  VLB_REQUIRE(ema_decay >= 0.f && ema_decay < 1.f, "adamw_ema: 0 <= ema_decay < 1 is needed");
+  VLB_REQUIRE(lr && weight_decay && n_groups >= 1 && n_groups <= kAdamwMaxGroups, "adamw_ema: 1 <= n_groups <= 8 with their rates are needed");
+  VLB_REQUIRE(!TABLE || (bounds && group_of && n_ranges >= 1 && (int64_t)n_ranges <= n / 8 && ((uintptr_t)bounds % 8) == 0 &&
+                         ((uintptr_t)group_of % 4) == 0),
+              "adamw_ema: 1 <= n_ranges <= n / 8 with both tables (8- / 4-byte aligned) is needed");
+  VLB_REQUIRE((((uintptr_t)master | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)grad) % 16) == 0 &&
+                  ((uintptr_t)param_bf16 % 8) == 0,
+              "adamw_ema: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned");
+  AdamwGroupRates rates;
+  for (int k = 0; k < kAdamwMaxGroups; ++k) {
+    rates.lr[k] = lr[k < n_groups ? k : 0];
+    rates.wd[k] = weight_decay[k < n_groups ? k : 0];
+  }
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
+  const int64_t n4 = n / 4;
+  int64_t nb = (n4 + 511) / 512; if (nb > 32768) nb = 32768;
+  bf16* pb = (bf16*)param_bf16;
+  const AdamwEma ea{ema, ema_decay};
+  if (!TABLE)
+    hipLaunchKernelGGL((adamw_groups_kernel<float, false, false, AdamwEma>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), master,
+                       pb, grad, m, v, n4, bounds, group_of, n_ranges, rates, beta1, beta2, eps, bc1, bc2s, sumsq, max_norm, ea);
+  else if (n_ranges <= kAdamwLdsRanges)
+    hipLaunchKernelGGL((adamw_groups_kernel<float, true, true, AdamwEma>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), master,
+                       pb, grad, m, v, n4, bounds, group_of, n_ranges, rates, beta1, beta2, eps, bc1, bc2s, sumsq, max_norm, ea);
+  else
+    hipLaunchKernelGGL((adamw_groups_kernel<float, false, true, AdamwEma>), dim3((unsigned)nb), dim3(256), 0, as_stream(stream), master,
+                       pb, grad, m, v, n4, bounds, group_of, n_ranges, rates, beta1, beta2, eps, bc1, bc2s, sumsq, max_norm, ea);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }

@@ -935,6 +935,20 @@ extern "C" int vlb_adamw_step_groups(float* master, void* param_bf16, const floa
   return adamw_groups_launch<float>(master, param_bf16, grad, m, v, n, bounds, group_of, n_ranges, lr, weight_decay, n_groups, beta1,
                                     beta2, eps, step, sumsq, max_norm, stream);
 }
+// the two steps above with an exponential moving average of the masters kept in the same launch (adamw_groups.hpp)
+extern "C" int vlb_adamw_step_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
+                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
+                                  float max_norm, float ema_decay, void* stream) {
+  return adamw_ema_launch<false>(master, param_bf16, grad, m, v, ema, n, nullptr, nullptr, 0, &lr, &weight_decay, 1, beta1, beta2, eps,
+                          step, sumsq, max_norm, ema_decay, stream);
+}
+extern "C" int vlb_adamw_step_groups_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
+                                         const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
+                                         const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
+                                         const float* sumsq, float max_norm, float ema_decay, void* stream) {
+  return adamw_ema_launch<true>(master, param_bf16, grad, m, v, ema, n, bounds, group_of, n_ranges, lr, weight_decay, n_groups, beta1,
+                          beta2, eps, step, sumsq, max_norm, ema_decay, stream);
+}
 extern "C" int vlb_grad_accum(float* acc, const float* g, int64_t n, int first, float* sumsq, float* ws, void* stream) {
   VLB_REQUIRE(n > 0 && acc && g && (sumsq == nullptr || ws) && ((uintptr_t)acc % 16) == 0 && ((uintptr_t)g % 16) == 0,
               "grad_accum: n > 0, acc and g 16-byte aligned, ws with sumsq");

@@ -88,5 +88,10 @@ class FlatTrainables:
                     lora.bt[n] = view(self.compute, n)
         self.names = [n for n, _, _ in entries]
 
+    def view(self, buf, n):
+        """Tensor ``n`` inside ``buf``, any flat buffer in this store's element order (the optimiser's EMA for instance)."""
+        o, k, shp = self.offsets[n]
+        return buf[o:o + k].view(shp)
+
     def named_masters(self):
         return [(n, self.master[o:o + k].view(shp)) for n, (o, k, shp) in self.offsets.items()]

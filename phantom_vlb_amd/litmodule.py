@@ -14,6 +14,7 @@ loss), because there is no autograd graph through hand-written kernels.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import warnings
@@ -25,7 +26,7 @@ from . import ops
 from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
 from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers, check_subjects
-from .optim import VlbAdamW
+from .optim import FULLFT_EMA_MESSAGE, VlbAdamW
 from .optim_groups import assign_groups, group_specs, normalize_optimizer_groups
 
 
@@ -196,6 +197,11 @@ class VLBLitModuleConfig:
     # entry with a matching pattern takes a tensor, what no entry matches keeps lr / weight_decay; lr_scale multiplies lr (the
     # scheduler then drives every group), weight_decay None = the configured one.  None: one group, as the reference (:357-363)
     optimizer_groups: list[dict] | None = None
+    # exponential moving average of the trainables, kept inside the fused AdamW launch: 0 < ema_decay < 1, the
+    # decay of the average (0.999 is usual); LoRA and frozen-backbone runs, one process.  None: no average, nothing changes
+    ema_decay: float | None = None
+    ema_warmup: bool = True             # the t-th update's decay is min(ema_decay, (1 + t) / (10 + t)); False: ema_decay from the first
+    ema_eval: bool = True               # validation and the merged export read the averaged weights (VLBLitModule.averaged_weights)
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -242,6 +248,17 @@ class VLBLitModuleConfig:
             raise ValueError("ridge_lambda_per_target=True chooses each target's l2_lambda from ridge_lambda_grid: set "
                              "ridge_lambda_grid (or leave ridge_lambda_per_target unset)")
         self.optimizer_groups = normalize_optimizer_groups(self.optimizer_groups)      # names are checked by configure_optimizers
+        if self.ema_decay is not None:
+            d = self.ema_decay
+            if isinstance(d, bool) or not isinstance(d, (int, float)) or not 0 < d < 1:
+                raise ValueError(f"ema_decay={d!r}: a number with 0 < ema_decay < 1 is needed (0.999 is usual; leave it unset for "
+                                 "no moving average)")
+            self.ema_decay = float(d)
+            for name in ("ema_warmup", "ema_eval"):
+                if not isinstance(getattr(self, name), bool):
+                    raise ValueError(f"{name}={getattr(self, name)!r}: true or false is needed")
+            if not self.freeze_backbone and not self.use_lora:
+                raise ValueError(FULLFT_EMA_MESSAGE)
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
         if self.readout_layers is not None:
@@ -442,9 +459,20 @@ class VLBLitModule(_Base):
         k = self.accumulate_grad_batches
         return k > 1 and (self._micro >= k or bool(self.__dict__.get("_window_closed")))
 
-    def trainable_state_dict(self) -> dict:
+    def trainable_state_dict(self, averaged: bool = False) -> dict:
         """Trainables on the host under their upstream / peft names and layouts (LoRA B as [out, r], rank padding
-        removed): what checkpoints store and what ``configure_model(state_dict=...)`` / peft accept."""
+        removed): what checkpoints store and what ``configure_model(state_dict=...)`` / peft accept.  ``averaged``: the
+        moving average of every tensor (``ema_decay``) in place of its master, same names and layouts."""
+        if averaged:
+            ema = self._ema_buffer()
+            if ema is None:
+                raise ValueError("trainable_state_dict(averaged=True) needs litmodule.config.ema_decay and configure_optimizers(): "
+                                 "there is no moving average")
+            view = lambda n: self.flat.view(ema, n)            # noqa: E731
+            sd = {n: view(n).detach().cpu().clone() for n in self.head.param_names}
+            if self.lora is not None:
+                sd.update({n: t.cpu() for n, t in self.lora.state_dict({n: view(n) for n in self.lora.master}).items()})
+            return sd
         sd = {n: self.head.master[n].detach().cpu().clone() for n in self.head.param_names}
         if self.lora is not None:
             sd.update({n: t.cpu() for n, t in self.lora.state_dict().items()})
@@ -460,6 +488,51 @@ class VLBLitModule(_Base):
         if self.lora is not None:
             self.lora.load_state_dict(sd)
         # full fine-tune: the backbone masters travel as the flat store itself (trainer.trainable_state 'stores')
+
+    # ------------------------------------------------------------------ weight averaging (ema_decay)
+    def _ema_buffer(self):
+        """The optimiser's flat fp32 moving average of the trainables, or None (no ``ema_decay``, no optimiser yet)."""
+        return getattr(getattr(self, "optimizer", None), "ema", None)
+
+    @contextlib.contextmanager
+    def averaged_weights(self):
+        """Inside the context every forward reads the moving average of the trainables instead of the last iterate: the
+        bf16 compute buffer of the flat store is stashed, ``bf16(ema)`` is written over it and the optimiser's ``post_step``
+        callables rebuild what is derived from it (LoRA's A^T / B layouts; ``lora.version`` moves, so ``merge()`` re-merges).
+        On exit, after an exception too, the stash is copied back and ``post_step`` runs again: the restored copies are the
+        stashed bits, not a re-cast of the masters.  Masters, moments and the average itself are never touched.  Without
+        ``ema_decay``, and when entered a second time inside itself, it does nothing."""
+        ema = self._ema_buffer()
+        if ema is None or self.__dict__.get("_ema_swapped", False):
+            yield
+            return
+        from ._lib import check, lib
+        compute, opt = self.flat.compute, self.optimizer
+        stash = self.__dict__.get("_ema_stash")
+        if stash is None or stash.numel() != compute.numel():
+            stash = self._ema_stash = torch.empty_like(compute)
+        stash.copy_(compute)
+        self._ema_swapped = True
+        try:
+            check(lib.vlb_cast_f32_to_bf16(ema.data_ptr(), compute.data_ptr(), ema.numel(), ops._stream()), "vlb_cast_f32_to_bf16")
+            for fn in opt.post_step:
+                fn()
+            yield
+        finally:
+            compute.copy_(stash)
+            for fn in opt.post_step:
+                fn()
+            self._ema_swapped = False
+
+    def _eval_weights(self):
+        """``averaged_weights()`` when ``ema_eval`` asks validation and the merged export to read the average, else nothing."""
+        return self.averaged_weights() if getattr(self.config, "ema_eval", False) else contextlib.nullcontext()
+
+    def log_ema_decay(self):
+        """``ema/decay``, the decay of the last EMA update, once per validation epoch (both runners call this at its end)."""
+        d = getattr(getattr(self, "optimizer", None), "ema_last_decay", None)
+        if d is not None:
+            self.log("ema/decay", float(d))
 
     # ------------------------------------------------------------------ dropout randomness (counter based)
     def _dropout_seed(self) -> int:
@@ -547,13 +620,19 @@ class VLBLitModule(_Base):
     def merged_state_dict(self) -> dict:
         """The decoder linears with the adapters merged in (``W + (alpha/r) B A``, bf16, host) under their upstream names,
         de-stacked and de-interleaved, plus the head tensors: with the untouched rest of the base checkpoint it loads as a
-        plain decoder, ``configure_model(state_dict={**base, **merged})`` under ``use_lora=False, freeze_backbone=True``."""
+        plain decoder, ``configure_model(state_dict={**base, **merged})`` under ``use_lora=False, freeze_backbone=True``.
+        With ``ema_decay`` and ``ema_eval`` the adapters and the head tensors are their moving averages."""
         sd = {}
-        for i, mw in enumerate(self._merged_layers()):
-            lins = destack_decoder_layer(self.geometry, mw["wqkv"], mw["wo"], mw["wdown"], mw.get("wgu"), mw.get("wgu_il"))
-            for n, t in lins.items():
-                sd[f"model.layers.{i}.{n}.weight"] = t.detach().cpu().contiguous().clone()
-        sd.update({n: self.head.master[n].detach().cpu().clone() for n in self.head.param_names})
+        averaged = self._ema_buffer() is not None and bool(getattr(self.config, "ema_eval", False))
+        with self._eval_weights():          # ema_decay + ema_eval: the averaged adapters (and head), as validation reads them
+            for i, mw in enumerate(self._merged_layers()):
+                lins = destack_decoder_layer(self.geometry, mw["wqkv"], mw["wo"], mw["wdown"], mw.get("wgu"), mw.get("wgu_il"))
+                for n, t in lins.items():
+                    sd[f"model.layers.{i}.{n}.weight"] = t.detach().cpu().contiguous().clone()
+        if averaged:
+            sd.update({n: self.flat.view(self._ema_buffer(), n).detach().cpu().clone() for n in self.head.param_names})
+        else:
+            sd.update({n: self.head.master[n].detach().cpu().clone() for n in self.head.param_names})
         return sd
 
     def save_merged(self, path: str) -> str:
@@ -708,6 +787,7 @@ class VLBLitModule(_Base):
         opt = getattr(self, "optimizer", None)
         if opt is not None:
             opt.reset_moments(["ridge_layer.linear.weight", "ridge_layer.linear.bias"])
+            opt.reset_ema(["ridge_layer.linear.weight", "ridge_layer.linear.bias"])      # ema_decay: the average restarts at the new values
         mse.append(float(self.head.forward_cached(cache, first[0], first[1], None, first[2])[1][0]))
         self.log("ridge_fit/n", float(sum(o["n"] for o in out)))
         self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]) if "l2_lambda" in out[0] else float(cv["best_lambda"]))
@@ -764,6 +844,10 @@ class VLBLitModule(_Base):
             self.feature_cache_end("train")
 
     def on_validation_epoch_start(self):
+        """Lightning hook.  ``ema_decay`` with ``ema_eval``: the whole validation epoch runs inside ``averaged_weights()``."""
+        if self.__dict__.get("_ema_val_ctx") is None and self._ema_buffer() is not None and getattr(self.config, "ema_eval", False):
+            self._ema_val_ctx = self.averaged_weights()
+            self._ema_val_ctx.__enter__()
         if self.config.cache_features:
             if not self.feature_caches:
                 self.setup_feature_cache(self._datamodule_dataset("train"), self._datamodule_dataset("val"))
@@ -772,7 +856,11 @@ class VLBLitModule(_Base):
     def on_validation_epoch_end(self):
         if self.config.cache_features:
             self.feature_cache_end("val")
+        ctx, self._ema_val_ctx = self.__dict__.get("_ema_val_ctx"), None
+        if ctx is not None:
+            ctx.__exit__(None, None, None)         # back on the last iterate before any checkpoint callback runs
         self.log_readout_alpha()
+        self.log_ema_decay()
 
     def log_readout_alpha(self):
         """``readout/alpha_<layer>`` = softmax(layer_mix.weight) of the bf16 copy the kernels read, once per validation
@@ -953,7 +1041,8 @@ class VLBLitModule(_Base):
             assignment = assign_groups([n for n, _ in named], cfg.optimizer_groups)
             groups = (assignment, group_specs(cfg.optimizer_groups, cfg.lr, cfg.weight_decay))
         self.optimizer = VlbAdamW(named, flats, lr=cfg.lr, betas=tuple(cfg.betas), eps=cfg.eps,
-                                  weight_decay=cfg.weight_decay, max_norm=cfg.gradient_clip_val, groups=groups)
+                                  weight_decay=cfg.weight_decay, max_norm=cfg.gradient_clip_val, groups=groups,
+                                  ema_decay=getattr(cfg, "ema_decay", None), ema_warmup=getattr(cfg, "ema_warmup", True))
         if self.lora is not None:
             self.optimizer.post_step.append(self.lora.refresh)
         if self.full is not None:

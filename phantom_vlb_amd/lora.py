@@ -258,10 +258,11 @@ class LoraState:
         self._merged_version = self.version
         return self._merged
 
-    def state_dict(self):
-        """peft layout: lora_A [r,in], lora_B [out,r] (rank padding removed)."""
+    def state_dict(self, masters=None):
+        """peft layout: lora_A [r,in], lora_B [out,r] (rank padding removed).  ``masters``: tensors in the masters' own
+        layout to export in their place (the optimiser's moving average), default the masters."""
         r = self.r
-        return {n: (t[:r].t().contiguous() if "lora_B" in n else t[:r].clone()) for n, t in self.master.items()}
+        return {n: (t[:r].t().contiguous() if "lora_B" in n else t[:r].clone()) for n, t in (masters or self.master).items()}
 
     def load_state_dict(self, sd: dict):
         """peft-layout tensors -> fp32 masters (padded rows stay zero), then bf16 copies + derived layouts."""

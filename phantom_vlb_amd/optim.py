@@ -23,6 +23,12 @@ Parameter groups (``litmodule.config.optimizer_groups``): with ``g
 see them like any torch optimiser's), every store gets a range table (``optim_groups.group_ranges``; rebuilt for a rank's slices
 when data parallelism is attached) and the step makes one ``vlb_adamw_step_groups`` / ``_g16`` launch per store.  Without
 ``groups`` nothing of this exists: one group, no table, the two launches above.
+
+Weight averaging (``litmodule.config.ema_decay``): with ``ema_decay`` the optimiser owns one more flat fp32 buffer,
+``ema``, an exponential moving average of store 0's masters.  The AdamW launch of the step is then ``vlb_adamw_step_ema`` (or
+``vlb_adamw_step_groups_ema``), which updates the average in the same pass with the decay ``ema_decay_at`` gives for this
+update; master, moments and bf16 copies come out bit-identical to the plain launch.  Without ``ema_decay`` there is no buffer
+and the launches above are the ones made.
 """
 from __future__ import annotations
 
@@ -35,16 +41,32 @@ from .optim_groups import MAX_GROUPS, group_ranges
 from .ops import _stream
 
 
+def ema_decay_at(t: int, decay: float, warmup: bool = True) -> float:
+    """Decay of the t-th EMA update (t = 1, 2, ...): ``decay``, or with ``warmup`` ``min(decay, (1 + t) / (10 + t))`` - the
+    usual warm-up (2/11, 3/12, ... up to the cap), so that the average is not dominated by the initial weights."""
+    if t < 1:
+        raise ValueError(f"ema_decay_at: updates count from 1 (got t={t})")
+    return min(float(decay), (1 + t) / (10 + t)) if warmup else float(decay)
+
+
+FULLFT_EMA_MESSAGE = ("ema_decay with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported: the backbone's "
+                      "bf16-gradient store has no EMA kernel, and an fp32 average of 7B weights costs 28 GB.  Average a LoRA or "
+                      "frozen-backbone run (use_lora=True or freeze_backbone=True), or leave ema_decay unset")
+
+
 class VlbAdamW(torch.optim.Optimizer):
     """``flat``: one flat store or a list of them (head + LoRA: fp32 gradients; ``fullft.FlatBackbone``: bf16
     gradients, attribute ``grad_bf16``).  One clip norm over all of them, one AdamW launch per store.
 
     ``groups``: None (one group: ``lr`` / ``weight_decay`` for everything), or ``(assignment, specs)`` - ``assignment`` maps
     every parameter name to an index into ``specs``, a list of ``{"name", "lr", "weight_decay"}`` (index 0: the default
-    group).  Groups no parameter is assigned to are dropped; the rest become ``param_groups`` in that order."""
+    group).  Groups no parameter is assigned to are dropped; the rest become ``param_groups`` in that order.
+
+    ``ema_decay``: None, or the decay of the moving average of store 0's masters kept in ``ema`` (``ema_warmup``: see
+    ``ema_decay_at``); one update per ``step()``, ``ema_updates`` counts them."""
 
     def __init__(self, named_params, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 max_norm: float = 0.0, groups=None):
+                 max_norm: float = 0.0, groups=None, ema_decay: float | None = None, ema_warmup: bool = True):
         named_params = list(named_params)
         self.names = [n for n, _ in named_params]
         self.named_params = named_params
@@ -85,6 +107,14 @@ class VlbAdamW(torch.optim.Optimizer):
             self.tables = [self._range_table(i) for i in range(len(self.flats))]
             self._lr_arg = (ctypes.c_float * MAX_GROUPS)()
             self._wd_arg = (ctypes.c_float * MAX_GROUPS)()
+        self.ema = None               # ema_decay only: flat fp32 moving average of store 0's masters, same element order
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self.ema_updates = 0          # EMA updates so far (the warm-up's t)
+        self.ema_last_decay = None    # decay the last update used
+        if ema_decay is not None:
+            if len(self.flats) > 1 or getattr(self.flat, "grad_bf16", False):
+                raise ValueError(FULLFT_EMA_MESSAGE)
+            self.ema = self.flat.master.detach().clone()
 
     def _range_table(self, i: int):
         """Store i's range table in the coordinates of the buffer its AdamW launch is handed: the flat store, or (data
@@ -107,6 +137,10 @@ class VlbAdamW(torch.optim.Optimizer):
         and the bf16 copies are all-gathered (parallel.ShardedFlatState); one state per flat store."""
         i = [k for k, f in enumerate(self.flats) if f is state.flat]
         assert i, "attach_sharded: the state wraps a flat store this optimiser does not own"
+        if self.ema is not None:
+            raise ValueError("ema_decay under data parallelism (WORLD_SIZE > 1) is not supported: every rank updates a 1/world slice "
+                             "of the optimiser state, and the moving average would need a slice of its own, which is not built.  "
+                             "Run one process, or leave ema_decay unset")
         self.shardeds[i[0]] = state
         if self.tables is not None:
             self.tables[i[0]] = self._range_table(i[0])
@@ -150,6 +184,32 @@ class VlbAdamW(torch.optim.Optimizer):
             f.m[o:o + k].zero_()
             f.v[o:o + k].zero_()
 
+    def reset_ema(self, names):
+        """EMA of the named tensors of the head (+ LoRA) store <- their masters (``reset_moments``' sibling: the average of
+        the values the closed-form ridge fit replaced says nothing about the new ones).  Nothing without ``ema_decay``."""
+        if self.ema is None:
+            return
+        f = self.flats[0]
+        for n in names:
+            if n not in f.offsets:
+                raise KeyError(f"VlbAdamW.reset_ema: {n!r} is not a tensor of the flat store ({sorted(f.offsets)[:6]} ...)")
+            o, k, _ = f.offsets[n]
+            self.ema[o:o + k].copy_(f.master[o:o + k])
+
+    def load_ema(self, ema=None, updates: int = 0):
+        """Checkpoint resume with ``ema_decay``: the saved average and its update count - or, from a checkpoint without them,
+        a fresh average of the (already restored) masters: starting to average late is a legitimate use."""
+        if self.ema is None:
+            return
+        if ema is None:
+            self.ema.copy_(self.flat.master)
+            self.ema_updates = 0
+        else:
+            if ema.numel() != self.ema.numel():
+                raise ValueError(f"the checkpoint's ema holds {ema.numel()} elements, this optimiser's flat store {self.ema.numel()}")
+            self.ema.copy_(ema.to(self.ema.device, torch.float32))
+            self.ema_updates = int(updates)
+
     # ------------------------------------------------------------------ checkpoint surface (torch.optim.Optimizer)
     def state_dict(self):
         """``torch.optim`` layout (``state`` / ``param_groups``) plus ``vlb``: the bias-correction step count and, per flat
@@ -165,6 +225,8 @@ class VlbAdamW(torch.optim.Optimizer):
                 st["master"] = self.full_state("master", i).detach().cpu().clone()
             stores.append(st)
         sd["vlb"] = {"step_count": self.step_count, "stores": stores}
+        if self.ema is not None:
+            sd["vlb"].update(ema=self.ema.detach().cpu().clone(), ema_updates=self.ema_updates)
         return sd
 
     def load_state_dict(self, state_dict):
@@ -185,6 +247,7 @@ class VlbAdamW(torch.optim.Optimizer):
                 self.compute_from_master(i)
             self.load_full_state("m", st["m"], i)
             self.load_full_state("v", st["v"], i)
+        self.load_ema(vlb.get("ema"), vlb.get("ema_updates", 0))
         for fn in self.post_step:
             fn()                      # derived layouts (LoRA A^T / B pads, W^T copies) from the restored weights
 
@@ -287,7 +350,9 @@ class VlbAdamW(torch.optim.Optimizer):
             active = [sh for sh in self.shardeds if sh is not None]
             if active:
                 active[0].all_reduce_scalar(self.sumsq)      # the clip norm covers every rank's slices
-        if self.tables is not None:          # more than one group: one grouped launch per store
+        if self.ema is not None:             # ema_decay: the same one launch, which also updates the average
+            self._step_ema(bufs[0], grads[0][0], st)
+        elif self.tables is not None:        # more than one group: one grouped launch per store
             self._step_groups(bufs, grads, st)
         else:
             for b, (g, bf) in zip(bufs, grads):
@@ -316,6 +381,30 @@ class VlbAdamW(torch.optim.Optimizer):
                      bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), self._lr_arg, self._wd_arg, G,
                      float(b1), float(b2), float(group["eps"]), self.step_count, self.sumsq.data_ptr(), self.max_norm, st),
                   "vlb_adamw_step_groups")
+
+    def _step_ema(self, b, g, st):
+        """ema_decay: store 0's (only) launch with the moving average in it, grouped when there are groups.  The decay of this
+        update goes by value; the kernel knows nothing about the warm-up."""
+        d = ema_decay_at(self.ema_updates + 1, self.ema_decay, self.ema_warmup)
+        group = self.param_groups[0]
+        b1, b2 = group["betas"]
+        if self.tables is not None:
+            G = len(self.param_groups)
+            for k, pg in enumerate(self.param_groups):
+                self._lr_arg[k], self._wd_arg[k] = float(pg["lr"]), float(pg["weight_decay"])
+            bounds, group_of = self.tables[0]
+            check(lib.vlb_adamw_step_groups_ema(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(),
+                                                self.ema.data_ptr(), b.numel, bounds.data_ptr(), group_of.data_ptr(), group_of.numel(),
+                                                self._lr_arg, self._wd_arg, G, float(b1), float(b2), float(group["eps"]),
+                                                self.step_count, self.sumsq.data_ptr(), self.max_norm, d, st),
+                  "vlb_adamw_step_groups_ema")
+        else:
+            check(lib.vlb_adamw_step_ema(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(),
+                                         self.ema.data_ptr(), b.numel, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                         float(group["weight_decay"]), self.step_count, self.sumsq.data_ptr(), self.max_norm, d, st),
+                  "vlb_adamw_step_ema")
+        self.ema_updates += 1
+        self.ema_last_decay = d
 
     def grad_norm(self) -> float:
         """Global gradient norm of the last step (host sync; for logging only)."""

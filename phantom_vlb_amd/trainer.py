@@ -13,6 +13,7 @@ batch where ``val_check_interval`` falls due, so no checkpoint carries a half-fi
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import os
 import time
@@ -88,6 +89,8 @@ def trainable_state(module, step: int, to_host: bool = True) -> dict | None:
             state.update(exp_avg=gathered("m"), exp_avg_sq=gathered("v"))
             # further flat stores (full fine-tune: the backbone in kernel layouts) travel whole: master + both moments
             state["stores"] = [{k: gathered(k, i) for k in ("master", "m", "v")} for i in range(1, n_stores)]
+            if getattr(opt, "ema", None) is not None and to_host:      # ema_decay (one process): the moving average and its update count
+                state.update(ema=opt.ema.detach().cpu().clone(), ema_updates=opt.ema_updates)
         if not to_host:
             return None
         state.update(state_dict=module.trainable_state_dict(), global_step=step, format=2)
@@ -170,6 +173,8 @@ def load_trainable_checkpoint(module, path):
             for k in ("master", "m", "v"):
                 opt.load_full_state(k, store[k], i)
             opt.compute_from_master(i)
+        # ema_decay: the saved average - or, from a checkpoint without one, a fresh average of the restored masters
+        opt.load_ema(st.get("ema"), st.get("ema_updates", 0))
         for fn in opt.post_step:
             fn()                          # derived layouts (LoRA A^T / B pads, W^T copies) from the restored weights
     sch = getattr(module, "scheduler", None)
@@ -265,11 +270,14 @@ class Trainer:
         tot, n = None, 0                     # summed on the device: one host sync per validation epoch, not per batch
         strided = self.world > 1 and getattr(model.backbone, "store", None) is None
         mine = (lambda bi: bi % self.world == self.rank) if strided else None
-        for bi, batch in _iter_selected(loader, mine, self.limit_val_batches):
-            out = model.validation_step(batch)
-            self._cb("on_validation_batch_end", model, out, batch, bi)
-            tot = out["loss"].detach().double() if tot is None else tot + out["loss"].detach().double()
-            n += 1
+        # ema_decay with ema_eval: every batch of the epoch reads the averaged weights; the last iterate is back before the
+        # checkpoint callback below runs
+        with model._eval_weights() if hasattr(model, "_eval_weights") else contextlib.nullcontext():
+            for bi, batch in _iter_selected(loader, mine, self.limit_val_batches):
+                out = model.validation_step(batch)
+                self._cb("on_validation_batch_end", model, out, batch, bi)
+                tot = out["loss"].detach().double() if tot is None else tot + out["loss"].detach().double()
+                n += 1
         if strided:
             import torch.distributed as dist
             t = torch.zeros(2, dtype=torch.float64, device=model.device)
@@ -287,8 +295,10 @@ class Trainer:
             metrics["feature_cache/val_hit_rate"] = rate
         if getattr(getattr(model, "head", None), "readout_layers", None) is not None:
             model.log_readout_alpha()             # readout/alpha_<layer>: the learned mix over the tapped layers
+        if hasattr(model, "log_ema_decay"):
+            model.log_ema_decay()                 # ema/decay: the decay of the last EMA update (ema_decay only)
         metrics.update({k: float(v) for k, v in getattr(model, "logged", {}).items()
-                        if k.startswith("val_corr_avg") or k.startswith("readout/alpha_")})
+                        if k.startswith("val_corr_avg") or k.startswith("readout/alpha_") or k == "ema/decay"})
         for c in self.callbacks:
             if hasattr(c, "on_validation_end") and isinstance(c, TrainableCheckpoint):
                 c.on_validation_end(self, model, metrics)
