@@ -459,7 +459,10 @@ int vlb_sumsq_ws_floats(void);
 int vlb_grad_sumsq(const float* g, int64_t n, float* sumsq, float* ws, void* stream);
 /* fused clip + AdamW on an fp32 master with fp32 moments; writes the bf16 compute copy when
  * param_bf16 != NULL.  clip coefficient = min(1, max_norm/(sqrt(sumsq[0])+1e-6)) read on device
- * (max_norm <= 0 disables clipping).  step counts from 1. */
+ * (max_norm <= 0 disables clipping).  step counts from 1.
+ * Any n > 0 and any element-aligned pointers are accepted.  With n % 8 == 0, master / grad / m / v 16-byte and param_bf16
+ * 8-byte aligned (every flat store of the package) the kernel moves 16 bytes per lane; any other call runs the same kernel
+ * with one element per lane - the same bits per element, slower. */
 int vlb_adamw_step(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
                    float max_norm, void* stream);

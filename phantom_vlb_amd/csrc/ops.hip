@@ -2,7 +2,6 @@
 // stencils, splice, weight mask, optimiser).  All use 16-byte per-lane accesses on bf16 data and
 // fp32 arithmetic; none of them is reshaped into a GEMM.
 #include "common.hpp"
-#include "adamw_groups.hpp"
 
 namespace {
 
@@ -585,22 +584,6 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(const float* __restric
   s = block_sum(s, red);
   if (threadIdx.x == 0) out[0] += s;
 }
-__global__ void adamw_kernel(float* __restrict__ p, bf16* __restrict__ pb, const float* __restrict__ g,
-                             float* __restrict__ m, float* __restrict__ v, int64_t n, float lr, float b1, float b2,
-                             float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ sumsq, float max_norm) {
-  float clip = 1.f;
-  if (max_norm > 0.f && sumsq) clip = fminf(1.f, max_norm / (sqrtf(sumsq[0]) + 1e-6f));
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * clip;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    p[i] = pi; m[i] = mi; v[i] = vi;
-    if (pb) pb[i] = (bf16)pi;
-  }
-}
-
 // ---- gradient accumulation (accumulate_grad_batches > 1): acc = first ? g : acc + g over a flat store, fp32 or bf16 g.
 // One 16-byte lane access per fp32 array and trip (8 bytes for a bf16 g), kAccumUnroll independent trips issued before the
 // first use so that a thread keeps up to 8 loads in flight.  n is arbitrary: the last n % 4 elements are done one by one
@@ -915,39 +898,6 @@ extern "C" int vlb_grad_sumsq(const float* g, int64_t n, float* sumsq, float* ws
   hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, ws, nb, sumsq);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
-}
-extern "C" int vlb_adamw_step(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n,
-                              float lr, float beta1, float beta2, float eps, float weight_decay, int step,
-                              const float* sumsq, float max_norm, void* stream) {
-  VLB_REQUIRE(n > 0 && master && grad && m && v && step >= 1, "adamw: bad args");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n, 256)), dim3(256), 0, as_stream(stream), master, (bf16*)param_bf16,
-                     grad, m, v, n, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, sumsq, max_norm);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
-}
-// one launch for a store whose ranges have their own lr / weight_decay (adamw_groups.hpp); fp32 gradients, 16-byte lanes
-extern "C" int vlb_adamw_step_groups(float* master, void* param_bf16, const float* grad, float* m, float* v, int64_t n,
-                                     const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
-                                     const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
-                                     const float* sumsq, float max_norm, void* stream) {
-  return adamw_groups_launch<float>(master, param_bf16, grad, m, v, n, bounds, group_of, n_ranges, lr, weight_decay, n_groups, beta1,
-                                    beta2, eps, step, sumsq, max_norm, stream);
-}
-// the two steps above with an exponential moving average of the masters kept in the same launch (adamw_groups.hpp)
-extern "C" int vlb_adamw_step_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
-                                  float lr, float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq,
-                                  float max_norm, float ema_decay, void* stream) {
-  return adamw_ema_launch<false>(master, param_bf16, grad, m, v, ema, n, nullptr, nullptr, 0, &lr, &weight_decay, 1, beta1, beta2, eps,
-                          step, sumsq, max_norm, ema_decay, stream);
-}
-extern "C" int vlb_adamw_step_groups_ema(float* master, void* param_bf16, const float* grad, float* m, float* v, float* ema, int64_t n,
-                                         const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
-                                         const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
-                                         const float* sumsq, float max_norm, float ema_decay, void* stream) {
-  return adamw_ema_launch<true>(master, param_bf16, grad, m, v, ema, n, bounds, group_of, n_ranges, lr, weight_decay, n_groups, beta1,
-                          beta2, eps, step, sumsq, max_norm, ema_decay, stream);
 }
 extern "C" int vlb_grad_accum(float* acc, const float* g, int64_t n, int first, float* sumsq, float* ws, void* stream) {
   VLB_REQUIRE(n > 0 && acc && g && (sumsq == nullptr || ws) && ((uintptr_t)acc % 16) == 0 && ((uintptr_t)g % 16) == 0,

@@ -6,7 +6,7 @@
 //   vlb_transpose_pad      out[C, Rpad] = in[R, C]^T, columns R..Rpad-1 zero
 //   vlb_rmsnorm_bwd_dw     d gamma of RMSNorm: sum_rows dy * x * rstd (fixed-order two-stage reduction)
 //   vlb_embed_grad         d embed_tokens: per-token sum of d(inputs_embeds) rows, occurrence lists from the host
-//   vlb_grad_sumsq_bf16 / vlb_adamw_step_g16   clip norm and AdamW reading bf16 gradients (what the wgrad GEMMs write)
+//   vlb_grad_sumsq_bf16    clip norm of bf16 gradients (what the wgrad GEMMs write; AdamW on them: adamw.hip)
 //   vlb_colsum             bias gradients: column sums of a [rows, C] bf16 matrix
 //   vlb_layernorm_bwd      LayerNorm (+ residual, + activation) backward: dx, d residual, d gamma / d beta partials
 //   vlb_act_bwd            dx = dy * act'(x) for SiLU / GELU
@@ -14,7 +14,6 @@
 //   vlb_se_bwd             squeeze-excite: d gate logits and d input of x * sigmoid(s)
 //   vlb_col2im3d_k2s2p1    inverse of the Conv3d im2col (every input element sits in exactly one window)
 #include "common.hpp"
-#include "adamw_groups.hpp"
 
 namespace {
 __device__ __forceinline__ void ld8(const bf16* p, float (&v)[8]) {
@@ -195,7 +194,7 @@ __global__ __launch_bounds__(256) void embed_grad_kernel(const bf16* __restrict_
   }
 }
 
-// ---------------------------------------------------------------- optimiser on bf16 gradients
+// ---------------------------------------------------------------- clip norm of bf16 gradients
 constexpr int kSumsqBlocksB = 1024;
 __global__ __launch_bounds__(256) void sumsq_bf16_kernel(const bf16* __restrict__ g, int64_t n8, float* __restrict__ part) {
   __shared__ float red[16];
@@ -214,49 +213,6 @@ __global__ __launch_bounds__(256) void sumsq_final_b_kernel(const float* __restr
   for (int i = threadIdx.x; i < nb; i += 256) s += part[i];
   s = block_sum(s, red);
   if (threadIdx.x == 0) out[0] += s;
-}
-// 4 consecutive parameters per thread: every fp32 state access is one fully coalesced 16-byte lane access (1 KiB per
-// wave instruction), the bf16 gradient / copy 8 bytes per lane; two independent chunks per loop trip keep 14 loads in
-// flight per thread.
-__device__ __forceinline__ void adamw4(float* __restrict__ p, bf16* __restrict__ pb, const bf16* __restrict__ g, float* __restrict__ m,
-                                       float* __restrict__ v, int64_t i4, float clip, float lr, float b1, float b2, float eps, float wd,
-                                       float bc1, float bc2_sqrt, f32x4 pv, f32x4 mv, f32x4 vv, bf16x4 gv) {
-  bf16x4 o;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const float gi = (float)gv[k] * clip;
-    float pi = pv[k] * (1.f - lr * wd);
-    const float mi = b1 * mv[k] + (1.f - b1) * gi;
-    const float vi = b2 * vv[k] + (1.f - b2) * gi * gi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    pv[k] = pi; mv[k] = mi; vv[k] = vi; o[k] = (bf16)pi;
-  }
-  *reinterpret_cast<f32x4*>(p + i4 * 4) = pv;
-  *reinterpret_cast<f32x4*>(m + i4 * 4) = mv;
-  *reinterpret_cast<f32x4*>(v + i4 * 4) = vv;
-  if (pb) *reinterpret_cast<bf16x4*>(pb + i4 * 4) = o;
-}
-__global__ __launch_bounds__(256) void adamw_g16_kernel(float* __restrict__ p, bf16* __restrict__ pb, const bf16* __restrict__ g,
-                                                        float* __restrict__ m, float* __restrict__ v, int64_t n4, float lr, float b1,
-                                                        float b2, float eps, float wd, float bc1, float bc2_sqrt,
-                                                        const float* __restrict__ sumsq, float max_norm) {
-  float clip = 1.f;
-  if (max_norm > 0.f && sumsq) clip = fminf(1.f, max_norm / (sqrtf(sumsq[0]) + 1e-6f));
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += 2 * stride) {
-    const int64_t j = i + stride;
-    const bool two = j < n4;
-    const f32x4 p0 = *reinterpret_cast<const f32x4*>(p + i * 4), m0 = *reinterpret_cast<const f32x4*>(m + i * 4),
-                v0 = *reinterpret_cast<const f32x4*>(v + i * 4);
-    const bf16x4 g0 = *reinterpret_cast<const bf16x4*>(g + i * 4);
-    f32x4 p1{}, m1{}, v1{}; bf16x4 g1{};
-    if (two) {
-      p1 = *reinterpret_cast<const f32x4*>(p + j * 4); m1 = *reinterpret_cast<const f32x4*>(m + j * 4);
-      v1 = *reinterpret_cast<const f32x4*>(v + j * 4); g1 = *reinterpret_cast<const bf16x4*>(g + j * 4);
-    }
-    adamw4(p, pb, g, m, v, i, clip, lr, b1, b2, eps, wd, bc1, bc2_sqrt, p0, m0, v0, g0);
-    if (two) adamw4(p, pb, g, m, v, j, clip, lr, b1, b2, eps, wd, bc1, bc2_sqrt, p1, m1, v1, g1);
-  }
 }
 
 // ---------------------------------------------------------------- activations backward
@@ -610,31 +566,6 @@ extern "C" int vlb_grad_sumsq_bf16(const void* g, int64_t n, float* sumsq, float
   hipLaunchKernelGGL(sumsq_final_b_kernel, dim3(1), dim3(256), 0, st, ws, nb, sumsq);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
-}
-
-extern "C" int vlb_adamw_step_g16(float* master, void* param_bf16, const void* grad_bf16, float* m, float* v, int64_t n, float lr,
-                                  float beta1, float beta2, float eps, float weight_decay, int step, const float* sumsq, float max_norm,
-                                  void* stream) {
-  VLB_REQUIRE(n > 0 && n % 8 == 0 && master && grad_bf16 && m && v && step >= 1, "adamw_g16: n must be a positive multiple of 8");
-  VLB_REQUIRE((((uintptr_t)master | (uintptr_t)m | (uintptr_t)v) % 16) == 0 && (((uintptr_t)grad_bf16 | (uintptr_t)param_bf16) % 8) == 0,
-              "adamw_g16: buffers must be 16-byte (fp32) / 8-byte (bf16) aligned");
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-  const int64_t n4 = n / 4;
-  int64_t nb = (n4 + 511) / 512; if (nb > 32768) nb = 32768;
-  hipLaunchKernelGGL(adamw_g16_kernel, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), master, (bf16*)param_bf16, (const bf16*)grad_bf16,
-                     m, v, n4, lr, beta1, beta2, eps, weight_decay, bc1, bc2s, sumsq, max_norm);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
-}
-
-// the same with per-range lr / weight_decay (adamw_groups.hpp), one launch
-extern "C" int vlb_adamw_step_groups_g16(float* master, void* param_bf16, const void* grad_bf16, float* m, float* v, int64_t n,
-                                         const int64_t* bounds, const int32_t* group_of, int n_ranges, const float* lr,
-                                         const float* weight_decay, int n_groups, float beta1, float beta2, float eps, int step,
-                                         const float* sumsq, float max_norm, void* stream) {
-  return adamw_groups_launch<bf16>(master, param_bf16, (const bf16*)grad_bf16, m, v, n, bounds, group_of, n_ranges, lr, weight_decay,
-                                   n_groups, beta1, beta2, eps, step, sumsq, max_norm, stream);
 }
 
 extern "C" int64_t vlb_dwconv3x3_bwd_w_ws_floats(int N, int H, int C) { return (int64_t)N * H * 9 * C; }

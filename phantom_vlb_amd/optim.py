@@ -323,7 +323,6 @@ class VlbAdamW(torch.optim.Optimizer):
         if closure is not None:               # Lightning's automatic optimisation: training_step + zero_grad + backward
             with torch.enable_grad():
                 loss = closure()
-        group = self.param_groups[0]
         self.step_count += 1
         st = _stream()
         acc_live, acc_sumsq = self._acc_live, self._acc_sumsq
@@ -340,7 +339,6 @@ class VlbAdamW(torch.optim.Optimizer):
                  for i, (f, b) in enumerate(zip(self.flats, bufs))]
         if not acc_sumsq:
             self.sumsq.zero_()
-        b1, b2 = group["betas"]
         if self.max_norm > 0:
             for b, (g, bf) in zip(bufs, grads):
                 if acc_sumsq:
@@ -350,16 +348,8 @@ class VlbAdamW(torch.optim.Optimizer):
             active = [sh for sh in self.shardeds if sh is not None]
             if active:
                 active[0].all_reduce_scalar(self.sumsq)      # the clip norm covers every rank's slices
-        if self.ema is not None:             # ema_decay: the same one launch, which also updates the average
-            self._step_ema(bufs[0], grads[0][0], st)
-        elif self.tables is not None:        # more than one group: one grouped launch per store
-            self._step_groups(bufs, grads, st)
-        else:
-            for b, (g, bf) in zip(bufs, grads):
-                fn = lib.vlb_adamw_step_g16 if bf else lib.vlb_adamw_step
-                check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
-                         float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), self.step_count,
-                         self.sumsq.data_ptr(), self.max_norm, st), "vlb_adamw_step")
+        for i, (b, (g, bf)) in enumerate(zip(bufs, grads)):      # one launch per store (ema_decay: there is only store 0)
+            self._launch(b, g, bf, self.tables[i] if self.tables is not None else None, st)
         for sh in self.shardeds:
             if sh is not None:
                 sh.gather_compute()
@@ -367,44 +357,36 @@ class VlbAdamW(torch.optim.Optimizer):
             fn()
         return loss
 
-    def _step_groups(self, bufs, grads, st):
-        """More than one group: one grouped launch per store; every group's current lr / weight_decay goes by value."""
-        G = len(self.param_groups)
-        for k, pg in enumerate(self.param_groups):
-            self._lr_arg[k], self._wd_arg[k] = float(pg["lr"]), float(pg["weight_decay"])
+    def _launch(self, b, g, bf, table, st):
+        """The clip+AdamW launch of one store.  Its entry point follows from (bf16 gradient?, range table?, EMA?):
+        ``vlb_adamw_step`` [``_groups``] [``_g16`` | ``_ema``] - all six run the same kernel family (csrc/adamw.hip).  With a table
+        every group's current lr / weight_decay goes by value, as does the EMA decay of this update (the kernel knows nothing
+        about the warm-up); there is no bf16-gradient EMA (``__init__`` refuses it)."""
         group = self.param_groups[0]
         b1, b2 = group["betas"]
-        for b, (g, bf), (bounds, group_of) in zip(bufs, grads, self.tables):
+        ema = self.ema is not None
+        name = "vlb_adamw_step" + ("_groups" if table is not None else "") + ("_ema" if ema else "_g16" if bf else "")
+        args = [b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr()]
+        if ema:
+            args.append(self.ema.data_ptr())
+        args.append(b.numel)
+        if table is not None:
+            bounds, group_of = table
             assert int(bounds.numel()) >= 2 and b.numel % 8 == 0
-            fn = lib.vlb_adamw_step_groups_g16 if bf else lib.vlb_adamw_step_groups
-            check(fn(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(), b.numel,
-                     bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), self._lr_arg, self._wd_arg, G,
-                     float(b1), float(b2), float(group["eps"]), self.step_count, self.sumsq.data_ptr(), self.max_norm, st),
-                  "vlb_adamw_step_groups")
-
-    def _step_ema(self, b, g, st):
-        """ema_decay: store 0's (only) launch with the moving average in it, grouped when there are groups.  The decay of this
-        update goes by value; the kernel knows nothing about the warm-up."""
-        d = ema_decay_at(self.ema_updates + 1, self.ema_decay, self.ema_warmup)
-        group = self.param_groups[0]
-        b1, b2 = group["betas"]
-        if self.tables is not None:
-            G = len(self.param_groups)
             for k, pg in enumerate(self.param_groups):
                 self._lr_arg[k], self._wd_arg[k] = float(pg["lr"]), float(pg["weight_decay"])
-            bounds, group_of = self.tables[0]
-            check(lib.vlb_adamw_step_groups_ema(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(),
-                                                self.ema.data_ptr(), b.numel, bounds.data_ptr(), group_of.data_ptr(), group_of.numel(),
-                                                self._lr_arg, self._wd_arg, G, float(b1), float(b2), float(group["eps"]),
-                                                self.step_count, self.sumsq.data_ptr(), self.max_norm, d, st),
-                  "vlb_adamw_step_groups_ema")
+            args += [bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), self._lr_arg, self._wd_arg, len(self.param_groups),
+                     float(b1), float(b2), float(group["eps"])]
         else:
-            check(lib.vlb_adamw_step_ema(b.master.data_ptr(), b.compute.data_ptr(), g.data_ptr(), b.m.data_ptr(), b.v.data_ptr(),
-                                         self.ema.data_ptr(), b.numel, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                         float(group["weight_decay"]), self.step_count, self.sumsq.data_ptr(), self.max_norm, d, st),
-                  "vlb_adamw_step_ema")
-        self.ema_updates += 1
-        self.ema_last_decay = d
+            args += [float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"])]
+        args += [self.step_count, self.sumsq.data_ptr(), self.max_norm]
+        if ema:
+            d = ema_decay_at(self.ema_updates + 1, self.ema_decay, self.ema_warmup)
+            args.append(d)
+        check(getattr(lib, name)(*args, st), name)
+        if ema:
+            self.ema_updates += 1
+            self.ema_last_decay = d
 
     def grad_norm(self) -> float:
         """Global gradient norm of the last step (host sync; for logging only)."""

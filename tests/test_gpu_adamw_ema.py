@@ -1,41 +1,23 @@
-"""vlb_adamw_step_ema / vlb_adamw_step_groups_ema against the kernels they stand in for.
+"""vlb_adamw_step_ema / vlb_adamw_step_groups_ema against the entries they stand in for (helpers shared with
+test_gpu_adamw_groups.py live in adamw_cases.py).
 
 master, both moments and the bf16 copy must be torch.equal to the parent's (vlb_adamw_step / vlb_adamw_step_groups) on the
 same inputs; ``ema`` must be torch.equal to tests/ema_emul.py's float32 restatement applied to the kernel's OWN new master
 (three separately rounded operations: a fused multiply-add in the kernel would show).  Bare buffers with 64 guard elements
 behind each; the shapes are the smallest at which the loop can go wrong (one vector pair, a workgroup chunk's edge, a
 ragged last workgroup, the grid-stride loop's second trip with its prefetch of ``ema``)."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 
 import ema_emul as E
+from adamw_cases import BETAS, EPS, LR, MAX_NORM, TAIL, WD, _clone, _random_bounds, _rates, _state, _stream, _table_args
 
 pytestmark = pytest.mark.gpu
-BF = torch.bfloat16
-BETAS, EPS, MAX_NORM = (0.9, 0.999), 1e-8, 1.0
-LR, WD = 1e-3, 1e-2
-TAIL = 64               # guard elements behind every buffer
 
 SHAPES = {"one_vector_pair": 8, "chunk_edge": 8 * 1031, "ragged_last_workgroup": 8 * (3 * 2 ** 16 + 5),
           "second_grid_stride_trip": 8 * (2 ** 23 + 2 ** 10 + 3)}
 DECAYS = (0.0, 0.5, 0.999)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _state(n, dev, seed):
-    gen = torch.Generator(device=dev).manual_seed(seed)
-    r = lambda: torch.randn(n + TAIL, device=dev, generator=gen)            # noqa: E731
-    return {"p": r(), "m": r() * 0.1, "v": r().square() * 0.01, "g": r(), "pb": r().to(BF), "ema": r()}
-
-
-def _clone(st):
-    return {k: t.clone() for k, t in st.items()}
 
 
 def _parent(st, n, step, sumsq, with_pb, lr=LR, wd=WD):
@@ -50,11 +32,6 @@ def _ema_step(st, n, step, sumsq, with_pb, d, ema_off=0, lr=LR, wd=WD):
     check(lib.vlb_adamw_step_ema(st["p"].data_ptr(), st["pb"].data_ptr() if with_pb else None, st["g"].data_ptr(), st["m"].data_ptr(),
                                  st["v"].data_ptr(), st["ema"].data_ptr() + ema_off, n, lr, BETAS[0], BETAS[1], EPS, wd, step,
                                  sumsq.data_ptr(), MAX_NORM, d, _stream()), "vlb_adamw_step_ema")
-
-
-def _table_args(bounds, group_of, lrs, wds):
-    G = len(lrs)
-    return bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), (ctypes.c_float * G)(*lrs), (ctypes.c_float * G)(*wds), G
 
 
 def _parent_groups(st, n, table, step, sumsq, with_pb):
@@ -106,7 +83,7 @@ def _variants(n):
 @pytest.mark.parametrize("shape", list(SHAPES))
 def test_ungrouped_equals_vlb_adamw_step_and_the_emulation(dev, shape):
     n = SHAPES[shape]
-    st0 = _state(n, dev, seed=n % 1000)
+    st0 = _state(n, dev, seed=n % 1000, ema=True)
     seen = set()
     for ss, step, with_pb, d in _variants(n):
         seen.add(d)
@@ -119,19 +96,6 @@ def test_ungrouped_equals_vlb_adamw_step_and_the_emulation(dev, shape):
         _compare(got, want, st0, n, d, with_pb, (shape, ss, step, with_pb, d))
         del want, got
     assert seen == set(DECAYS)
-
-
-def _random_bounds(n, n_ranges, seed):
-    gen = torch.Generator().manual_seed(seed)
-    cuts = torch.randperm(n // 8 - 1, generator=gen)[:n_ranges - 1].add(1).sort().values * 8
-    return [0] + cuts.tolist() + [n]
-
-
-def _rates(G):
-    lrs = [1e-3 * (1 + 3 * k) for k in range(G)]
-    wds = [1e-2 * (1 + k) for k in range(G)]
-    wds[1] = 0.0
-    return lrs, wds
 
 
 @pytest.mark.parametrize("table", ["ranges300_G3_lds", "ranges700_G5_global"])
@@ -147,7 +111,7 @@ def test_grouped_equals_vlb_adamw_step_groups_and_the_emulation(dev, shape, tabl
     d_bounds = torch.tensor(bounds, dtype=torch.int64, device=dev)
     d_groups = torch.tensor(groups, dtype=torch.int32, device=dev)
     args = _table_args(d_bounds, d_groups, lrs, wds)
-    st0 = _state(n, dev, seed=n % 1000 + G)
+    st0 = _state(n, dev, seed=n % 1000 + G, ema=True)
     for ss, step, with_pb, d in _variants(n):
         sumsq = torch.tensor([ss], dtype=torch.float32, device=dev)
         want, got = _clone(st0), _clone(st0)
@@ -163,7 +127,7 @@ def test_trajectory_of_six_steps_with_the_warm_up_decays(dev):
     derived bound (ema_emul.drift_bound) of the float64 reference fed with the same masters."""
     from phantom_vlb_amd.optim import ema_decay_at
     n = SHAPES["chunk_edge"]
-    st = _state(n, dev, seed=5)
+    st = _state(n, dev, seed=5, ema=True)
     twin = _clone(st)
     gen = torch.Generator(device=dev).manual_seed(6)
     emu = st["ema"][:n].cpu().numpy().copy()
@@ -194,7 +158,7 @@ def test_trajectory_of_six_steps_with_the_warm_up_decays(dev):
 def test_bad_arguments_are_refused_before_any_launch(dev):
     from phantom_vlb_amd._lib import VlbError
     n = 64
-    st = _state(n, dev, seed=2)
+    st = _state(n, dev, seed=2, ema=True)
     before = _clone(st)
     ss = torch.zeros(1, device=dev)
     bounds = torch.tensor([0, n], dtype=torch.int64, device=dev)

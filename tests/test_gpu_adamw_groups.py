@@ -1,32 +1,17 @@
-"""vlb_adamw_step_groups / vlb_adamw_step_groups_g16 against the kernels they stand in for.
+"""vlb_adamw_step_groups / vlb_adamw_step_groups_g16 against the ungrouped entries they stand in for.  All four
+launch one kernel family (csrc/adamw.hip): this tests the table search, the LDS staging and the pointer offsets; the arithmetic
+is anchored by test_gpu_adamw_bits.py.  Helpers shared with test_gpu_adamw_ema.py live in adamw_cases.py.
 
 AdamW is element-wise once the clip scalar is known, so the grouped step over a range table IS one parent launch
 (vlb_adamw_step / vlb_adamw_step_g16) per range, pointers offset to the range, with the range's group's (lr, weight_decay) and
 the same sumsq / max_norm / step.  Every comparison is torch.equal on master, both moments and the bf16 copy; the elements
 behind the buffer's end must stay untouched.  Bare buffers; the whole file takes a few seconds."""
-import ctypes
-
 import pytest
 import torch
 
+from adamw_cases import BETAS, BF, EPS, MAX_NORM, _clone, _random_bounds, _rates, _state, _stream, _table_args
+
 pytestmark = pytest.mark.gpu
-BF = torch.bfloat16
-BETAS, EPS, MAX_NORM = (0.9, 0.999), 1e-8, 1.0
-TAIL = 64               # guard elements behind every buffer
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _state(n, gdtype, dev, seed):
-    gen = torch.Generator(device=dev).manual_seed(seed)
-    r = lambda: torch.randn(n + TAIL, device=dev, generator=gen)            # noqa: E731
-    return {"p": r(), "m": r() * 0.1, "v": r().square() * 0.01, "g": r().to(gdtype), "pb": r().to(BF)}
-
-
-def _clone(st):
-    return {k: t.clone() for k, t in st.items()}
 
 
 def _parent(st, s, e, lr, wd, step, sumsq, with_pb):
@@ -42,28 +27,8 @@ def _grouped(st, n, bounds, group_of, lrs, wds, step, sumsq, with_pb):
     from phantom_vlb_amd._lib import check, lib
     bf = st["g"].dtype == BF
     fn = lib.vlb_adamw_step_groups_g16 if bf else lib.vlb_adamw_step_groups
-    G = len(lrs)
     check(fn(st["p"].data_ptr(), st["pb"].data_ptr() if with_pb else None, st["g"].data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), n,
-             bounds.data_ptr(), group_of.data_ptr(), group_of.numel(), (ctypes.c_float * G)(*lrs), (ctypes.c_float * G)(*wds), G,
-             BETAS[0], BETAS[1], EPS, step, sumsq.data_ptr(), MAX_NORM, _stream()), "vlb_adamw_step_groups")
-
-
-def _rates(G):
-    """G (lr, weight_decay) pairs: group 1 has weight_decay 0; with three or more, the last two are equal."""
-    lrs = [1e-3 * (1 + 3 * k) for k in range(G)]
-    wds = [1e-2 * (1 + k) for k in range(G)]
-    if G >= 2:
-        wds[1] = 0.0
-    if G >= 3:
-        lrs[-1], wds[-1] = lrs[-2], wds[-2]
-    return lrs, wds
-
-
-def _random_bounds(n, n_ranges, seed):
-    """n_ranges ranges of random multiple-of-8 lengths >= 8 that fill [0, n)."""
-    gen = torch.Generator().manual_seed(seed)
-    cuts = torch.randperm(n // 8 - 1, generator=gen)[:n_ranges - 1].add(1).sort().values * 8
-    return [0] + cuts.tolist() + [n]
+             *_table_args(bounds, group_of, lrs, wds), BETAS[0], BETAS[1], EPS, step, sumsq.data_ptr(), MAX_NORM, _stream()), "vlb_adamw_step_groups")
 
 
 def _case(name):
@@ -97,10 +62,10 @@ CASES = ["one_vector_pair", "block_edges", "ranges300_G2", "ranges300_G3", "rang
 def test_grouped_step_equals_one_parent_launch_per_range(dev, case, gdtype):
     n, bounds, groups, G = _case(case)
     assert bounds[0] == 0 and bounds[-1] == n and all(b % 8 == 0 for b in bounds) and len(groups) == len(bounds) - 1
-    lrs, wds = _rates(G)
+    lrs, wds = _rates(G, tie_last_two=True)
     d_bounds = torch.tensor(bounds, dtype=torch.int64, device=dev)
     d_groups = torch.tensor(groups, dtype=torch.int32, device=dev)
-    st0 = _state(n, gdtype, dev, seed=n % 1000 + G)
+    st0 = _state(n, dev, seed=n % 1000 + G, gdtype=gdtype)
     big = n > 2 ** 24
     # (sum of squares for the clip, step, write the bf16 copy): clip active and inactive, bias correction at step 1 and 7
     variants = [(1e4, 1, True), (1e-2, 7, False)] if big else \
@@ -129,7 +94,7 @@ def test_groups_actually_differ(dev):
     n = 8 * 600
     bounds = torch.tensor([0, 8 * 100, 8 * 350, n], dtype=torch.int64, device=dev)
     groups = torch.tensor([0, 1, 0], dtype=torch.int32, device=dev)
-    st0 = _state(n, torch.float32, dev, seed=1)
+    st0 = _state(n, dev, seed=1, gdtype=torch.float32)
     got = _clone(st0)
     _grouped(got, n, bounds, groups, [1e-3, 0.0], [1e-2, 0.0], 1, torch.tensor([1e-2], device=dev), True)
     torch.cuda.synchronize()
@@ -141,7 +106,7 @@ def test_groups_actually_differ(dev):
 def test_bad_arguments_are_refused_before_any_launch(dev):
     from phantom_vlb_amd._lib import VlbError
     n = 64
-    st = _state(n, torch.float32, dev, seed=2)
+    st = _state(n, dev, seed=2, gdtype=torch.float32)
     before = _clone(st)
     bounds = torch.tensor([0, n], dtype=torch.int64, device=dev)
     groups = torch.zeros(1, dtype=torch.int32, device=dev)

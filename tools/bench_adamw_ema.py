@@ -1,12 +1,14 @@
-"""The EMA variants of the fused clip + AdamW step (vlb_adamw_step_ema / vlb_adamw_step_groups_ema) against the
-launches they stand in for, on the same buffers.
+"""The EMA entries of the fused clip + AdamW step (vlb_adamw_step_ema / vlb_adamw_step_groups_ema) against the
+same steps without the average, on the same buffers.  All four launch instantiations of ONE kernel (csrc/adamw.hip), with and
+without the average, so both pairs are like for like and should sit on the byte ratio.  (Before the kernels were unified
+vlb_adamw_step was a separate 4-byte-lane kernel and the ungrouped pair came out below it: profiles/adamw_ema_kernels.txt.)
 
   python tools/bench_adamw_ema.py [repetitions >= 20]
 
 The 7B LoRA r=16 flat store (50.6 M elements, flat.FlatTrainables' layout with its padding), fp32 gradients:
 * vlb_adamw_step against vlb_adamw_step_ema;
 * vlb_adamw_step_groups against vlb_adamw_step_groups_ema, with the range table the README's example optimizer_groups gives.
-The two kernels of a pair alternate in one process; every launch is timed on its own with device events; the medians over the
+The two entries of a pair alternate in one process; every launch is timed on its own with device events; the medians over the
 repetitions (after three warm-up rounds) and their ratio are printed.  30 B move per element without the average, 38 B with
 it (one more fp32 read and write): by bytes the expected ratio is 38 / 30 = 1.27.
 """

@@ -1,11 +1,15 @@
-"""Grouped clip + AdamW (vlb_adamw_step_groups / _g16) against the kernels it stands in for, on the same buffers.
+"""Clip + AdamW with a range table (vlb_adamw_step_groups / _g16) against the same step without one, on the same
+buffers.  Both entries of a pair launch instantiations of ONE kernel (csrc/adamw.hip), so the ratio is the price of the table:
+its staging in LDS and the binary search per lane, on top of the same bytes and the same arithmetic.  (Before the kernels were
+unified the ungrouped fp32 step was a separate 4-byte-lane kernel and the pair measured that difference too;
+profiles/adamw_groups_kernels.txt keeps those numbers, profiles/adamw_unified_kernels.txt has today's against them.)
 
   python tools/bench_adamw_groups.py [repetitions >= 20]
 
 * fp32 gradients: the 7B LoRA r=16 flat store (50.6 M elements, flat.FlatTrainables' layout with its padding) with the range
   table the README's example optimizer_groups gives it, against ONE vlb_adamw_step over the store;
 * bf16 gradients: 268 M elements cut into 64 ranges over three groups, against ONE vlb_adamw_step_g16.
-The two kernels of a pair alternate in one process; every launch is timed on its own with device events; the medians over the
+The two entries of a pair alternate in one process; every launch is timed on its own with device events; the medians over the
 repetitions (after three warm-up rounds) and their ratio are printed.  30 B (fp32 g) / 28 B (bf16 g) move per element.
 """
 import ctypes
