@@ -212,16 +212,28 @@ __global__ __launch_bounds__(256) void feature_cache_gather_kernel(const float* 
   if (blockIdx.x == 0 && threadIdx.x == 0) sumw[b] = cache_sumw[r];
 }
 
+// ================================================================ the ridge layer: one head, or G heads, one per subject
+// Plain head: W [V, E], bias [V].  Per-subject heads: W [G*V, E], bias [G*V], group[b] in [0, G) names the
+// head of clip b; pred / y stay [B, V]:   pred[b, v] = W[group[b]*V + v, :] . z[b, :] + bias[group[b]*V + v].
+// Every ridge kernel is ONE template with a compile-time GROUPED.  GROUPED splits the row index into (head g, row v of the
+// head) and lets a clip take part only in its own head's rows; !GROUPED fixes g = 0, row = v, every clip takes part, and
+// `group` is never read (the plain entries pass nullptr).  A clip's chain of additions is the same in both, the blocks /
+// tiles of head g come in the plain order behind those of the heads before it, and the (sum err^2, sum W^2) partials keep
+// one pair per block: with G = 1 the grouped instantiation gives the plain one's bits.
+
 // ---------------------------------------------------------------- forward 3: ridge GEMV + loss partials
-// block = 4 waves x RIDGE_ROWS/4 rows of W; z (bf16 [<=BMAX, E]) is staged once per block into LDS and
-// re-read from there for every row (the W stream, 16-byte lanes, is the only HBM traffic).
+// grid G * bpg, bpg = ceil(V/RIDGE_ROWS): block -> (g, RIDGE_ROWS rows of head g) = 4 waves x RIDGE_ROWS/4 rows of W; z (bf16
+// [<=BMAX, E]) is staged once per block into LDS and re-read from there for every row (the W stream, 16-byte lanes, is the
+// only HBM traffic).
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void ridge_fwd_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
                                                         const bf16* __restrict__ z, const float* __restrict__ y,
-                                                        float* __restrict__ pred, float* __restrict__ lpart, int B, int E,
-                                                        int V) {
+                                                        const int* __restrict__ group, float* __restrict__ pred,
+                                                        float* __restrict__ lpart, int B, int E, int V, int bpg) {
   extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
   __shared__ float red[8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = GROUPED ? blockIdx.x / bpg : 0, vb = GROUPED ? blockIdx.x % bpg : blockIdx.x;   // head, block of rows inside it
   float mse = 0.f, w2 = 0.f;
   for (int b0 = 0; b0 < B; b0 += BMAX) {
     const int nb = min(BMAX, B - b0);
@@ -229,10 +241,17 @@ __global__ __launch_bounds__(256) void ridge_fwd_kernel(const bf16* __restrict__
     for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
       *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
     __syncthreads();
+    bool mine[BMAX];
+#pragma unroll
+    for (int i = 0; i < BMAX; ++i) {
+      mine[i] = i < nb;
+      if constexpr (GROUPED) mine[i] = mine[i] && group[b0 + i] == g;
+    }
     for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
-      const int v = blockIdx.x * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
+      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
       if (v >= V) break;
-      const bf16* wr = W + (int64_t)v * E;
+      const int64_t row = (int64_t)g * V + v;
+      const bf16* wr = W + row * E;
       float acc[BMAX];
 #pragma unroll
       for (int i = 0; i < BMAX; ++i) acc[i] = 0.f;
@@ -245,7 +264,7 @@ __global__ __launch_bounds__(256) void ridge_fwd_kernel(const bf16* __restrict__
         }
 #pragma unroll
         for (int i = 0; i < BMAX; ++i) {
-          if (i < nb) {
+          if (mine[i]) {
             float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i] += w[j] * zz[j];
@@ -254,8 +273,8 @@ __global__ __launch_bounds__(256) void ridge_fwd_kernel(const bf16* __restrict__
       }
 #pragma unroll
       for (int i = 0; i < BMAX; ++i) {
-        if (i < nb) {
-          const float pv = wave_sum(acc[i]) + (float)bias[v];
+        if (mine[i]) {
+          const float pv = wave_sum(acc[i]) + (float)bias[row];
           if (lane == 0) {
             pred[(int64_t)(b0 + i) * V + v] = pv;
             const float d = y ? pv - y[(int64_t)(b0 + i) * V + v] : 0.f;
@@ -279,11 +298,16 @@ __global__ __launch_bounds__(256) void ridge_fwd_kernel(const bf16* __restrict__
 // of E and keeps its z fragments in registers for the whole kernel (<= 128 VGPRs), so the only memory
 // stream is W: 32 independent 1-KiB fragment loads per wave per row tile.  Blocks are persistent over
 // row tiles; the four K-quarters are summed through LDS; sum(W^2) and the squared error ride along.
-template <int KSTEPS>   // E / 128: k-steps of 32 per wave
+// The ntiles = G * tpg row tiles, tpg = ceil(V/16): tile t is rows [16 tl, 16 tl + 16) of head g = t / tpg, tl = t % tpg - a
+// tile never spans two heads, the last tile of a head clamps its rows to the head's own last row.  All 16 clip columns are
+// contracted with every tile (no extra matrix work per head: the W stream is the cost); the epilogue keeps column b only
+// where group[b] == g.  sum W^2 counts every live row of every tile.
+template <int KSTEPS, bool GROUPED>   // KSTEPS = E / 128: k-steps of 32 per wave
 __global__ __launch_bounds__(256) void ridge_fwd_mfma_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
                                                              const bf16* __restrict__ z, const float* __restrict__ y,
-                                                             float* __restrict__ pred, float* __restrict__ lpart, int B,
-                                                             int E, int V) {
+                                                             const int* __restrict__ group, float* __restrict__ pred,
+                                                             float* __restrict__ lpart, int B, int E, int V, int tpg,
+                                                             int ntiles) {
   __shared__ float red[3][4][64];
   __shared__ float lred[8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -296,13 +320,15 @@ __global__ __launch_bounds__(256) void ridge_fwd_mfma_kernel(const bf16* __restr
     zf[s] = bf16x8{};
     if (fr < B) zf[s] = *reinterpret_cast<const bf16x8*>(z + (int64_t)fr * E + kq + 32 * s + 8 * fq);
   }
+  int myg = 0;                                             // head of this lane's clip column
+  if constexpr (GROUPED) myg = fr < B ? group[fr] : -1;
   float mse = 0.f, w2 = 0.f;
-  const int ntiles = (V + 15) / 16;
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int v = min(t * 16 + fr, V - 1);
-    const bf16* wr = W + (int64_t)v * E + kq + 8 * fq;
+    const int g = GROUPED ? t / tpg : 0, tl = GROUPED ? t % tpg : t;
+    const int v = min(tl * 16 + fr, V - 1);
+    const bf16* wr = W + ((int64_t)g * V + v) * E + kq + 8 * fq;
     f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool count = t * 16 + fr < V;
+    const bool count = tl * 16 + fr < V;
 #pragma unroll
     for (int s = 0; s < KSTEPS; ++s) {
       const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wr + 32 * s);
@@ -318,13 +344,13 @@ __global__ __launch_bounds__(256) void ridge_fwd_mfma_kernel(const bf16* __restr
       for (int e = 0; e < 4; ++e) red[wave - 1][e][lane] = acc[e];
     }
     __syncthreads();
-    if (wave == 0 && fr < B) {
-      // lane holds clip b = fr, rows v = t*16 + 4*fq + e
+    if (wave == 0 && (GROUPED ? myg == g : fr < B)) {
+      // lane holds clip b = fr (of head g), rows v = tl*16 + 4*fq + e of that head
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const int vv = t * 16 + 4 * fq + e;
+        const int vv = tl * 16 + 4 * fq + e;
         if (vv < V) {
-          const float pv = acc[e] + red[0][e][lane] + red[1][e][lane] + red[2][e][lane] + (float)bias[vv];
+          const float pv = acc[e] + red[0][e][lane] + red[1][e][lane] + red[2][e][lane] + (float)bias[(int64_t)g * V + vv];
           pred[(int64_t)fr * V + vv] = pv;
           const float d = y ? pv - y[(int64_t)fr * V + vv] : 0.f;
           mse += d * d;
@@ -479,81 +505,101 @@ __device__ __forceinline__ float dpred_corr(const float* __restrict__ coef, int 
   return c[0] * (p - c[2]) + c[1] * (yv - c[3]);
 }
 
-// d pred^T as the skinny-wgrad G operand: dpT[v, b] = gscale * (pred[b,v] - y[b,v]) for b < B, 0 for b < 16
+// d pred of clip b at row v of ITS head, the one spelling for both objectives (the other heads' rows see 0 for this clip):
+// gscale * (pred - y), or the correlation form above.
 template <bool CORR>
-__global__ void dpred_t_kernel(const float* __restrict__ pred, const float* __restrict__ y, bf16* __restrict__ dpT, int B,
-                               int V, float gscale, const float* __restrict__ coef) {
+__device__ __forceinline__ float dpred_own(const float* __restrict__ pred, const float* __restrict__ y, int b, int v, int V,
+                                           float gscale, const float* __restrict__ coef) {
+  if constexpr (CORR) return dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]);
+  else return gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]);
+}
+
+// d pred^T over all GV = G*V rows as the skinny-wgrad G operand: dpT[g*V + v, b] = d pred[b, v] for b < B (and, GROUPED,
+// group[b] == g), else 0 - the columns b < 16 are all written
+template <bool CORR, bool GROUPED>
+__global__ void dpred_t_kernel(const float* __restrict__ pred, const float* __restrict__ y, const int* __restrict__ group,
+                               bf16* __restrict__ dpT, int B, int V, int64_t GV, float gscale, const float* __restrict__ coef) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= (int64_t)V * 16) return;
-  const int v = i >> 4, b = i & 15;
-  if constexpr (CORR)
-    dpT[i] = (bf16)(b < B ? dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]) : 0.f);
-  else
-    dpT[i] = (bf16)(b < B ? gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]) : 0.f);
+  if (i >= GV * 16) return;
+  const int64_t row = i >> 4;
+  const int b = (int)(i & 15), g = GROUPED ? (int)(row / V) : 0, v = GROUPED ? (int)(row % V) : (int)row;
+  bool mine = b < B;
+  if constexpr (GROUPED) mine = mine && group[b] == g;
+  dpT[i] = (bf16)(mine ? dpred_own<CORR>(pred, y, b, v, V, gscale, coef) : 0.f);
 }
 
 // ---------------------------------------------------------------- backward 1: dW, dbias   (z staged in LDS)
-template <bool CORR>
+// grid G * bpg as ridge_fwd_kernel, one row of dW per (g, v).  A clip of another head adds nothing to the row: it is skipped,
+// so a head without a clip gets the fp32 product l2coef * W and dbias = 0 exactly.
+template <bool CORR, bool GROUPED>
 __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict__ W, const bf16* __restrict__ z,
                                                           const float* __restrict__ pred, const float* __restrict__ y,
-                                                          float* __restrict__ dW, float* __restrict__ dbias, int B, int E,
-                                                          int V, float gscale, float l2coef, const float* __restrict__ coef) {
+                                                          const int* __restrict__ group, float* __restrict__ dW,
+                                                          float* __restrict__ dbias, int B, int E, int V, int bpg, float gscale,
+                                                          float l2coef, const float* __restrict__ coef) {
   extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = GROUPED ? blockIdx.x / bpg : 0, vb = GROUPED ? blockIdx.x % bpg : blockIdx.x;
   for (int b0 = 0; b0 < B; b0 += BMAX) {
     const int nb = min(BMAX, B - b0);
     __syncthreads();
     for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
       *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
     __syncthreads();
+    bool own[BMAX];                                          // GROUPED: the clips of this pass that belong to head g
+    if constexpr (GROUPED) {
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) own[i] = i < nb && group[b0 + i] == g;
+    }
+    auto mine = [&](int i) { return GROUPED ? own[i] : i < nb; };
     for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
-      const int v = blockIdx.x * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
+      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
       if (v >= V) break;
+      const int64_t row = (int64_t)g * V + v;
       float dp[BMAX];
       float db = 0.f;
 #pragma unroll
       for (int i = 0; i < BMAX; ++i) {
-        if constexpr (CORR)
-          dp[i] = i < nb ? dpred_corr(coef, b0 + i, pred[(int64_t)(b0 + i) * V + v], y[(int64_t)(b0 + i) * V + v]) : 0.f;
-        else
-          dp[i] = i < nb ? gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]) : 0.f;
+        dp[i] = mine(i) ? dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef) : 0.f;
         db += dp[i];
       }
-      if (lane == 0) dbias[v] = (b0 == 0 ? 0.f : dbias[v]) + db;
-      const bf16* wr = W + (int64_t)v * E;
+      if (lane == 0) dbias[row] = (b0 == 0 ? 0.f : dbias[row]) + db;
+      const bf16* wr = W + row * E;
 #pragma unroll 4
       for (int c = lane * 8; c < E; c += 512) {
-        float g[8];
-        float* o = dW + (int64_t)v * E + c;
+        float gr[8];
+        float* o = dW + row * E + c;
         if (b0 == 0) {
           float w[8]; ld8(wr + c, w);
 #pragma unroll
-          for (int j = 0; j < 8; ++j) g[j] = l2coef * w[j];
+          for (int j = 0; j < 8; ++j) gr[j] = l2coef * w[j];
         } else {
           const f32x4 lo = *reinterpret_cast<const f32x4*>(o), hi = *reinterpret_cast<const f32x4*>(o + 4);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) { g[j] = lo[j]; g[4 + j] = hi[j]; }
+          for (int j = 0; j < 4; ++j) { gr[j] = lo[j]; gr[4 + j] = hi[j]; }
         }
 #pragma unroll
         for (int i = 0; i < BMAX; ++i) {
-          if (i < nb) {
+          if (mine(i)) {
             float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) g[j] += dp[i] * zz[j];
+            for (int j = 0; j < 8; ++j) gr[j] += dp[i] * zz[j];
           }
         }
-        *reinterpret_cast<f32x4*>(o) = f32x4{g[0], g[1], g[2], g[3]};
-        *reinterpret_cast<f32x4*>(o + 4) = f32x4{g[4], g[5], g[6], g[7]};
+        *reinterpret_cast<f32x4*>(o) = f32x4{gr[0], gr[1], gr[2], gr[3]};
+        *reinterpret_cast<f32x4*>(o + 4) = f32x4{gr[4], gr[5], gr[6], gr[7]};
       }
     }
   }
 }
-// ---------------------------------------------------------------- backward 2: dz partials over V splits
-// grid (ceil(E/512), DZ_SPLIT), block 256 (4 waves share a split's rows); out part[split][B][E]
-template <bool CORR>
+// ---------------------------------------------------------------- backward 2: dz partials over V splits (B > 16)
+// grid (ceil(E/512), DZ_SPLIT), block 256 (4 waves share a split's rows); out part[split][B][E].  GROUPED: the split's rows of
+// every head are walked in turn, heads ascending; clip b accumulates only over the rows of head group[b], in the plain order.
+template <bool CORR, bool GROUPED>
 __global__ __launch_bounds__(256) void ridge_bwd_z_kernel(const bf16* __restrict__ W, const float* __restrict__ pred,
-                                                          const float* __restrict__ y, float* __restrict__ part, int B,
-                                                          int E, int V, float gscale, const float* __restrict__ coef) {
+                                                          const float* __restrict__ y, const int* __restrict__ group,
+                                                          float* __restrict__ part, int B, int E, int V, int G, float gscale,
+                                                          const float* __restrict__ coef) {
   __shared__ float red[3][BMAX][512];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 512 + lane * 8;
@@ -561,24 +607,40 @@ __global__ __launch_bounds__(256) void ridge_bwd_z_kernel(const bf16* __restrict
   const int v0 = blockIdx.y * per, v1 = min(V, v0 + per);
   for (int b0 = 0; b0 < B; b0 += BMAX) {
     const int nb = min(BMAX, B - b0);
+    int gi[BMAX];                                            // GROUPED: head of every clip of this pass
+    if constexpr (GROUPED) {
+#pragma unroll
+      for (int i = 0; i < BMAX; ++i) gi[i] = i < nb ? group[b0 + i] : -1;
+    }
     float acc[BMAX][8];
 #pragma unroll
     for (int i = 0; i < BMAX; ++i)
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
-    if (c < E) {
+    auto walk = [&](int g, auto mine) {                      // this split's rows of head g, for the clips that are mine(i)
       for (int v = v0 + wave; v < v1; v += 4) {
-        float w[8]; ld8(W + (int64_t)v * E + c, w);
+        float w[8]; ld8(W + ((int64_t)g * V + v) * E + c, w);
 #pragma unroll
         for (int i = 0; i < BMAX; ++i) {
-          if (i < nb) {
-            float dp;
-            if constexpr (CORR) dp = dpred_corr(coef, b0 + i, pred[(int64_t)(b0 + i) * V + v], y[(int64_t)(b0 + i) * V + v]);
-            else dp = gscale * (pred[(int64_t)(b0 + i) * V + v] - y[(int64_t)(b0 + i) * V + v]);
+          if (mine(i)) {
+            const float dp = dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef);
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] += dp * w[j];
           }
         }
+      }
+    };
+    if (c < E) {
+      if constexpr (GROUPED) {
+        for (int g = 0; g < G; ++g) {
+          bool any = false;
+#pragma unroll
+          for (int i = 0; i < BMAX; ++i) any = any || gi[i] == g;
+          if (!any) continue;                                // no clip of this pass reads head g: skip its rows
+          walk(g, [&](int i) { return gi[i] == g; });
+        }
+      } else {
+        walk(0, [&](int i) { return i < nb; });
       }
     }
     __syncthreads();
@@ -899,11 +961,16 @@ __global__ __launch_bounds__(256) void hrf_pool_reduce_kernel(const float* __res
 int reserve_ridge_lds(int bytes) {
   static int reserved = 0;
   if (bytes > reserved) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e2 == hipSuccess)
-      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e1 != hipSuccess || e2 != hipSuccess) { vlb_set_error("head: cannot reserve %d bytes of LDS for z", bytes); return VLB_ERR_LAUNCH; }
+    // every instantiation that stages z in dynamic LDS
+    const void* const kernels[] = {
+        reinterpret_cast<const void*>(&ridge_fwd_kernel<false>),          reinterpret_cast<const void*>(&ridge_fwd_kernel<true>),
+        reinterpret_cast<const void*>(&ridge_bwd_w_kernel<false, false>), reinterpret_cast<const void*>(&ridge_bwd_w_kernel<false, true>),
+        reinterpret_cast<const void*>(&ridge_bwd_w_kernel<true, false>),  reinterpret_cast<const void*>(&ridge_bwd_w_kernel<true, true>)};
+    for (const void* k : kernels)
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+        vlb_set_error("head: cannot reserve %d bytes of LDS for z", bytes);
+        return VLB_ERR_LAUNCH;
+      }
     reserved = bytes;
   }
   return VLB_OK;
@@ -949,11 +1016,24 @@ int64_t head_bwd_ws_floats(int B, int E, int V) {
   return dz_mfma > dz ? dz_mfma : dz;
 }
 
-// (sum err^2, sum W^2) pairs head_fwd_tail's ridge launch leaves in lpart: one per block, a restatement of its grid
-int ridge_fwd_parts(int B, int E, int V) {
-  const bool mfma = B <= 16 && E % 128 == 0 && E <= 4096;
-  const int ntiles = (V + 15) / 16;
-  return mfma ? (ntiles < 2048 ? ntiles : 2048) : (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+// the ridge planner: which forward form, and how many (sum err^2, sum W^2) pairs its launch leaves in lpart - one per block
+constexpr int64_t GROUPED_MAX_ROWS = (int64_t)1 << 27;      // G*V: 16 bf16 per row of d pred^T and every tile count fit an int
+bool ridge_fwd_is_mfma(int B, int E) { return B <= 16 && E % 128 == 0 && E <= 4096; }
+int ridge_fwd_parts(int B, int E, int V, int G, bool mfma) {
+  const int64_t ntiles = (int64_t)G * ((V + 15) / 16);      // the MFMA form is persistent over row tiles
+  return mfma ? (int)(ntiles < 2048 ? ntiles : 2048) : G * ((V + RIDGE_ROWS - 1) / RIDGE_ROWS);
+}
+
+void feature_cache_gather_launch(const float* cache_pooled, const float* cache_sumw, const int* rows, float* pooled_raw,
+                                 float* sumw, int B, int E, int n_rows, hipStream_t st) {
+  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
+                     pooled_raw, sumw, E, n_rows);
+}
+
+void head_dhidden_launch(const void* hidden, const float* wmask, const float* stats, const float* draw, void* dh, int B, int S,
+                         int E, int64_t rows, const int* cu_rows, hipStream_t st) {
+  hipLaunchKernelGGL(head_dhidden_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const bf16*)hidden, wmask, stats,
+                     draw, (bf16*)dh, S, E, rows, B, cu_rows);
 }
 
 // The LN1-affine + LN2 (+ dropout) launch on its own: head_fwd_tail's first launch, and all of vlb_head_features_cached.
@@ -966,20 +1046,17 @@ int head_ln2_launch(const float* pooled_raw, const float* sumw, const void* ln1_
   return VLB_OK;
 }
 
-// LN1 affine + LN2 + dropout -> z, ridge GEMV, loss: everything of the forward that reads only (pooled_raw, sumw).
-// vlb_head_fwd and vlb_head_fwd_cached both end here, so the two give the same bits for the same (pooled_raw, sumw).
-int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w, const void* ln1_b, const void* ln2_w,
-                  const void* ln2_b, const void* ridge_w, const void* ridge_b, const float* y, const float* keep_scale,
-                  float* lpart, float* zhat, float* ln2_rstd, void* z, float* pred, float* loss_terms, int B, int E, int V,
-                  float eps, float l2_lambda, hipStream_t st) {
-  if (int rc = head_ln2_launch(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, keep_scale, zhat, ln2_rstd, z, B, E, eps, st)) return rc;
-  int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-  if (B <= 16 && E % 128 == 0 && E <= 4096) {
-    const int ntiles = (V + 15) / 16;
-    rblk = ntiles < 2048 ? ntiles : 2048;          // persistent over row tiles; lpart has room for V/16 >= rblk entries
+// The ridge forward: pred and the loss partials in lpart.  `mfma` = ridge_fwd_is_mfma(B, E) for the head (vlb_ridge_fwd, the
+// layer on its own, always runs the scalar form).  -> the number of (sum err^2, sum W^2) pairs written, or an error (< 0).
+template <bool GROUPED>
+int ridge_fwd_launch_as(const bf16* W, const bf16* bias, const bf16* z, const float* y, const int* group, float* pred,
+                        float* lpart, int B, int E, int V, int G, bool mfma, hipStream_t st) {
+  const int parts = ridge_fwd_parts(B, E, V, G, mfma);
+  if (mfma) {
+    const int tpg = (V + 15) / 16, ntiles = G * tpg;
     switch (E / 128) {
-#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL(ridge_fwd_mfma_kernel<KS>, dim3(rblk), dim3(256), 0, st, (const bf16*)ridge_w, \
-                                                       (const bf16*)ridge_b, (const bf16*)z, y, pred, lpart, B, E, V); break;
+#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL((ridge_fwd_mfma_kernel<KS, GROUPED>), dim3(parts), dim3(256), 0, st, W, bias, z, \
+                                                       y, group, pred, lpart, B, E, V, tpg, ntiles); break;
       VLB_RIDGE_CASE(1) VLB_RIDGE_CASE(2) VLB_RIDGE_CASE(3) VLB_RIDGE_CASE(4) VLB_RIDGE_CASE(5) VLB_RIDGE_CASE(6) VLB_RIDGE_CASE(7)
       VLB_RIDGE_CASE(8) VLB_RIDGE_CASE(9) VLB_RIDGE_CASE(10) VLB_RIDGE_CASE(11) VLB_RIDGE_CASE(12) VLB_RIDGE_CASE(13)
       VLB_RIDGE_CASE(14) VLB_RIDGE_CASE(15) VLB_RIDGE_CASE(16) VLB_RIDGE_CASE(17) VLB_RIDGE_CASE(18) VLB_RIDGE_CASE(19)
@@ -989,381 +1066,116 @@ int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w,
 #undef VLB_RIDGE_CASE
     }
   } else {
+    const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
     const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-    if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
-    hipLaunchKernelGGL(ridge_fwd_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b,
-                       (const bf16*)z, y, pred, lpart, B, E, V);
+    if (int rc = reserve_ridge_lds(zlds)) return rc;
+    hipLaunchKernelGGL(ridge_fwd_kernel<GROUPED>, dim3(parts), dim3(256), zlds, st, W, bias, z, y, group, pred, lpart, B, E, V, bpg);
   }
   VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, rblk, 1.f / ((float)B * (float)V),
-                     l2_lambda, loss_terms);
+  return parts;
+}
+int ridge_fwd_launch(const void* W, const void* bias, const void* z, const float* y, const int* group, float* pred, float* lpart,
+                     int B, int E, int V, int G, bool mfma, hipStream_t st) {
+  return group ? ridge_fwd_launch_as<true>((const bf16*)W, (const bf16*)bias, (const bf16*)z, y, group, pred, lpart, B, E, V, G, mfma, st)
+               : ridge_fwd_launch_as<false>((const bf16*)W, (const bf16*)bias, (const bf16*)z, y, nullptr, pred, lpart, B, E, V, 1, mfma, st);
+}
+
+// The correlation objectives' forward on a finished pred: row statistics, then the loss terms from them and the ridge partials.
+int head_loss_corr_launch(const float* pred, const float* y, const float* lpart, int parts, float* rowstat, float* loss_terms,
+                          float* loss_aux, int B, int V, int loss_kind, float l2_lambda, hipStream_t st) {
+  if (loss_kind == VLB_LOSS_PEARSON) hipLaunchKernelGGL(head_rowstat_kernel<true>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+  else hipLaunchKernelGGL(head_rowstat_kernel<false>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(loss_finalize_corr_kernel, dim3(1), dim3(256), 0, st, lpart, parts, 1.f / ((float)B * (float)V), l2_lambda,
+                     rowstat, B, loss_terms, loss_aux);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
 
-// Ridge, dropout, LN2 and LN1-affine gradients (dpooled_ws = d loss / d pooled_raw is left for head_dhidden_kernel):
-// vlb_head_bwd and vlb_head_bwd_cached both run this, so their parameter gradients are the same bits.
-int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
-                    const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd, const void* z,
-                    const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
-                    float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, float l2_lambda,
-                    float loss_scale, float l2_scale, void* stream, int loss_kind = 0, const float* rowstat = nullptr) {
+// LN1 affine + LN2 + dropout -> z, ridge GEMV, loss: everything of the forward that reads only (pooled_raw, sumw).
+// vlb_head_fwd, vlb_head_fwd_cached (group = nullptr, G = 1) and vlb_head_fwd_grouped all end here, so they give the same bits
+// for the same (pooled_raw, sumw).  loss_kind: the plain entries pass VLB_LOSS_MSE (vlb_head_loss_fwd finishes a correlation
+// objective in a call of its own); the grouped entry finishes it here.
+int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w, const void* ln1_b, const void* ln2_w,
+                  const void* ln2_b, const void* ridge_w, const void* ridge_b, const float* y, const float* keep_scale,
+                  const int* group, float* lpart, float* zhat, float* ln2_rstd, void* z, float* pred, float* rowstat,
+                  float* loss_terms, float* loss_aux, int B, int E, int V, int G, float eps, float l2_lambda, int loss_kind,
+                  hipStream_t st) {
+  if (int rc = head_ln2_launch(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, keep_scale, zhat, ln2_rstd, z, B, E, eps, st)) return rc;
+  const int parts = ridge_fwd_launch(ridge_w, ridge_b, z, y, group, pred, lpart, B, E, V, G, ridge_fwd_is_mfma(B, E), st);
+  if (parts < 0) return parts;
+  if (loss_kind != VLB_LOSS_MSE)
+    return head_loss_corr_launch(pred, y, lpart, parts, rowstat, loss_terms, loss_aux, B, V, loss_kind, l2_lambda, st);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, parts, 1.f / ((float)B * (float)V), l2_lambda,
+                     loss_terms);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// dW, dbias and the unmasked dz of the ridge layer over GV = G*V rows, one (objective, GROUPED) instantiation per call
+template <bool CORR, bool GROUPED>
+int ridge_bwd_launch(const void* ridge_w, const void* z, const float* pred, const float* y, const float* keep_scale,
+                     const int* group, float* d_ridge_w, float* d_ridge_b, float* ws, float* dz_ws, const float* coef, int B, int E,
+                     int V, int G, float gscale, float l2coef, void* stream) {
   hipStream_t st = as_stream(stream);
-  const float gscale = loss_scale * 2.f / ((float)B * (float)V);
-  const int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
+  const int GV = G * V;
+  const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
   const int zlds = (B < BMAX ? B : BMAX) * E * 2;
   if (int rc2 = reserve_ridge_lds(zlds)) return rc2;
+  hipLaunchKernelGGL((ridge_bwd_w_kernel<CORR, GROUPED>), dim3(G * bpg), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred,
+                     y, group, d_ridge_w, d_ridge_b, B, E, V, bpg, gscale, l2coef, coef);
+  VLB_LAUNCH_CHECK();
+  if (B <= 16 && E % 8 == 0) {
+    // dz[b,e] = sum_{(g,v)} dpT[g*V+v, b] W[g*V+v, e]: contraction over the ROWS of W -> ONE MFMA skinny-wgrad call over all
+    // G*V rows (G operand = dpred^T [GV,16] bf16, zeros off the clip's head; X = W).  Rows b < B of a [16,E] fp32 block -> dz16.
+    const int splits = vlb_wgrad_splits(GV);
+    float* wg_ws = ws;                                             // [splits][16][E]
+    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
+    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [G*V][16] bf16
+    hipLaunchKernelGGL((dpred_t_kernel<CORR, GROUPED>), dim3((unsigned)(((int64_t)GV * 16 + 255) / 256)), dim3(256), 0, st, pred, y,
+                       group, dpT, B, V, (int64_t)GV, gscale, coef);
+    VLB_LAUNCH_CHECK();
+    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, GV, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
+    if (rc3 != VLB_OK) return rc3;
+    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
+  } else {
+    hipLaunchKernelGGL((ridge_bwd_z_kernel<CORR, GROUPED>), dim3((E + 511) / 512, DZ_SPLIT), dim3(256), 0, st, (const bf16*)ridge_w,
+                       pred, y, group, ws, B, E, V, G, gscale, coef);
+    VLB_LAUNCH_CHECK();
+    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
+  }
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// Ridge, dropout, LN2 and LN1-affine gradients (dpooled_ws = d loss / d pooled_raw is left for head_dhidden_kernel): every
+// backward entry runs this (the plain ones with group = nullptr, G = 1), so their parameter gradients are the same bits.
+int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
+                    const int* group, const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd,
+                    const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b,
+                    float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, const float* rowstat, int B, int E,
+                    int V, int G, float l2_lambda, float loss_scale, float l2_scale, int loss_kind, void* stream) {
+  hipStream_t st = as_stream(stream);
+  const float gscale = loss_scale * 2.f / ((float)B * (float)V);      // B: the whole batch, whatever the heads' shares
+  const float l2coef = l2_scale * 2.f * l2_lambda;
   // correlation objectives: the per-clip coefficients live behind everything the backward keeps in ws
-  float* coef = ws + head_bwd_ws_floats(B, E, V);
-  const bool corr = loss_kind != 0;
+  float* coef = ws + head_bwd_ws_floats(B, E, G * V);
+  const bool corr = loss_kind != VLB_LOSS_MSE;
   if (corr) {
     hipLaunchKernelGGL(head_loss_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rowstat, coef, B, loss_scale);
     VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ridge_bwd_w_kernel<true>, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
-                       d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda, coef);
-  } else {
-    hipLaunchKernelGGL(ridge_bwd_w_kernel<false>, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z, pred, y,
-                       d_ridge_w, d_ridge_b, B, E, V, gscale, l2_scale * 2.f * l2_lambda, coef);
   }
-  VLB_LAUNCH_CHECK();
-  if (B <= 16 && E % 8 == 0) {
-    // dz[b,e] = sum_v dpred[b,v] W[v,e]: contraction over the ROWS of W -> the MFMA skinny-wgrad kernel
-    // (G = dpred^T [V,16] bf16, X = W).  Result rows b < B of a [16,E] fp32 block land in dz_part[0].
-    const int splits = vlb_wgrad_splits(V);
-    float* wg_ws = ws;                                             // [splits][16][E]
-    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
-    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [V][16] bf16
-    const dim3 tgrid((unsigned)(((int64_t)V * 16 + 255) / 256));
-    if (corr) hipLaunchKernelGGL(dpred_t_kernel<true>, tgrid, dim3(256), 0, st, pred, y, dpT, B, V, gscale, coef);
-    else hipLaunchKernelGGL(dpred_t_kernel<false>, tgrid, dim3(256), 0, st, pred, y, dpT, B, V, gscale, coef);
-    VLB_LAUNCH_CHECK();
-    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, V, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
-    if (rc3 != VLB_OK) return rc3;
-    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
-    VLB_LAUNCH_CHECK();
-  } else {
-    const dim3 zgrid((E + 511) / 512, DZ_SPLIT);
-    if (corr) hipLaunchKernelGGL(ridge_bwd_z_kernel<true>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, ws, B, E, V, gscale, coef);
-    else hipLaunchKernelGGL(ridge_bwd_z_kernel<false>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, ws, B, E, V, gscale, coef);
-    VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
-    VLB_LAUNCH_CHECK();
-  }
+  const auto ridge_bwd = corr ? (group ? &ridge_bwd_launch<true, true> : &ridge_bwd_launch<true, false>)
+                              : (group ? &ridge_bwd_launch<false, true> : &ridge_bwd_launch<false, false>);
+  if (int rc = ridge_bwd(ridge_w, z, pred, y, keep_scale, group, d_ridge_w, d_ridge_b, ws, dz_ws, coef, B, E, V, G, gscale, l2coef,
+                         stream))
+    return rc;
   hipLaunchKernelGGL(head_ln2_bwd_kernel, dim3(B), dim3(1024), 0, st, dz_ws, (const bf16*)ln2_w, zhat, ln2_rstd, dpooled_ws, E);
   VLB_LAUNCH_CHECK();
   hipLaunchKernelGGL(head_param_grads_kernel, dim3((E + 255) / 256), dim3(256), 0, st, dz_ws, dpooled_ws, (const bf16*)ln1_w,
                      pooled_raw, sumw, zhat, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, B, E);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
-}
-
-// ================================================================ grouped ridge: G heads, one per subject
-// W is [G*V, E], bias [G*V]; group[b] in [0, G) names the head of clip b; pred / y stay [B, V]:
-//   pred[b, v] = W[group[b]*V + v, :] . z[b, :] + bias[group[b]*V + v].
-// Each kernel below is its ungrouped neighbour with the row index split into (head g, row v of the head) and a clip taking
-// part only in its own head's rows.  A clip's chain of additions is the one the ungrouped kernel runs on W[g] alone, the
-// blocks / tiles of head g come in the ungrouped order behind those of the heads before it, and the (sum err^2, sum W^2)
-// partials keep one pair per block: with G = 1 every output has the ungrouped bits.
-
-// scalar form: grid G * ceil(V/RIDGE_ROWS); block -> (g, RIDGE_ROWS rows of head g).  z staged in LDS as ridge_fwd_kernel.
-__global__ __launch_bounds__(256) void ridge_fwd_grouped_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
-                                                                const bf16* __restrict__ z, const float* __restrict__ y,
-                                                                const int* __restrict__ group, float* __restrict__ pred,
-                                                                float* __restrict__ lpart, int B, int E, int V, int bpg) {
-  extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
-  __shared__ float red[8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = blockIdx.x / bpg, vb = blockIdx.x % bpg;           // head, block of rows inside the head
-  float mse = 0.f, w2 = 0.f;
-  for (int b0 = 0; b0 < B; b0 += BMAX) {
-    const int nb = min(BMAX, B - b0);
-    __syncthreads();
-    for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
-      *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
-    __syncthreads();
-    bool mine[BMAX];
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i) mine[i] = i < nb && group[b0 + i] == g;
-    for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
-      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
-      if (v >= V) break;
-      const int64_t row = (int64_t)g * V + v;
-      const bf16* wr = W + row * E;
-      float acc[BMAX];
-#pragma unroll
-      for (int i = 0; i < BMAX; ++i) acc[i] = 0.f;
-#pragma unroll 4
-      for (int c = lane * 8; c < E; c += 512) {
-        float w[8]; ld8(wr + c, w);
-        if (b0 == 0) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) w2 += w[j] * w[j];
-        }
-#pragma unroll
-        for (int i = 0; i < BMAX; ++i) {
-          if (mine[i]) {
-            float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i] += w[j] * zz[j];
-          }
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < BMAX; ++i) {
-        if (mine[i]) {
-          const float pv = wave_sum(acc[i]) + (float)bias[row];
-          if (lane == 0) {
-            pred[(int64_t)(b0 + i) * V + v] = pv;
-            const float d = y ? pv - y[(int64_t)(b0 + i) * V + v] : 0.f;
-            mse += d * d;
-          }
-        }
-      }
-    }
-  }
-  w2 = wave_sum(w2);
-  if (lane == 0) { red[wave] = mse; red[4 + wave] = w2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    lpart[blockIdx.x * 2] = red[0] + red[1] + red[2] + red[3];
-    lpart[blockIdx.x * 2 + 1] = red[4] + red[5] + red[6] + red[7];
-  }
-}
-
-// MFMA form (B <= 16, E % 128 == 0, E <= 4096): ridge_fwd_mfma_kernel's operand layout, unchanged (rows of the A operand =
-// 16 rows of W, columns of the B operand = clips, each wave one quarter of E with its z fragments in registers).  Persistent
-// over G * tpg row tiles, tpg = ceil(V/16): tile t is rows [16 tl, 16 tl + 16) of head g = t / tpg, tl = t % tpg - a tile
-// never spans two heads, the last tile of a head clamps its rows to the head's own last row.  All 16 clip columns are
-// contracted with every tile (no extra matrix work per head: the W stream is the cost); the epilogue keeps column b only
-// where group[b] == g.  sum W^2 counts every live row of every tile.
-template <int KSTEPS>
-__global__ __launch_bounds__(256) void ridge_fwd_grouped_mfma_kernel(const bf16* __restrict__ W, const bf16* __restrict__ bias,
-                                                                     const bf16* __restrict__ z, const float* __restrict__ y,
-                                                                     const int* __restrict__ group, float* __restrict__ pred,
-                                                                     float* __restrict__ lpart, int B, int E, int V, int tpg,
-                                                                     int ntiles) {
-  __shared__ float red[3][4][64];
-  __shared__ float lred[8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int kq = wave * KSTEPS * 32;                       // first column of this wave's quarter
-  // B operand: lane holds z[b = fr][kq + 32*s + 8*fq .. +8]  (zero rows for b >= B)
-  bf16x8 zf[KSTEPS];
-#pragma unroll
-  for (int s = 0; s < KSTEPS; ++s) {
-    zf[s] = bf16x8{};
-    if (fr < B) zf[s] = *reinterpret_cast<const bf16x8*>(z + (int64_t)fr * E + kq + 32 * s + 8 * fq);
-  }
-  const int myg = fr < B ? group[fr] : -1;                 // head of this lane's clip column
-  float mse = 0.f, w2 = 0.f;
-  for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    const int g = t / tpg, tl = t % tpg;
-    const int v = min(tl * 16 + fr, V - 1);
-    const bf16* wr = W + ((int64_t)g * V + v) * E + kq + 8 * fq;
-    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool count = tl * 16 + fr < V;
-#pragma unroll
-    for (int s = 0; s < KSTEPS; ++s) {
-      const bf16x8 wf = *reinterpret_cast<const bf16x8*>(wr + 32 * s);
-      if (count) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = (float)wf[j]; w2 += f * f; }
-      }
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, zf[s], acc, 0, 0, 0);
-    }
-    __syncthreads();                                       // red[] free again
-    if (wave > 0) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) red[wave - 1][e][lane] = acc[e];
-    }
-    __syncthreads();
-    if (wave == 0 && myg == g) {
-      // lane holds clip b = fr (of head g), rows v = tl*16 + 4*fq + e of that head
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int vv = tl * 16 + 4 * fq + e;
-        if (vv < V) {
-          const float pv = acc[e] + red[0][e][lane] + red[1][e][lane] + red[2][e][lane] + (float)bias[(int64_t)g * V + vv];
-          pred[(int64_t)fr * V + vv] = pv;
-          const float d = y ? pv - y[(int64_t)fr * V + vv] : 0.f;
-          mse += d * d;
-        }
-      }
-    }
-  }
-  mse = wave_sum(mse);
-  w2 = wave_sum(w2);
-  if (lane == 0) { lred[wave] = mse; lred[4 + wave] = w2; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    lpart[blockIdx.x * 2] = lred[0] + lred[1] + lred[2] + lred[3];
-    lpart[blockIdx.x * 2 + 1] = lred[4] + lred[5] + lred[6] + lred[7];
-  }
-}
-
-// d pred of clip b at row v of ITS head (both objectives); the other heads' rows see 0 for this clip.
-template <bool CORR>
-__device__ __forceinline__ float dpred_own(const float* __restrict__ pred, const float* __restrict__ y, int b, int v, int V,
-                                           float gscale, const float* __restrict__ coef) {
-  if constexpr (CORR) return dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]);
-  else return gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]);
-}
-
-// d pred^T over all G*V rows as the skinny-wgrad G operand: dpT[g*V + v, b] = d pred[b, v] where group[b] == g, else 0
-template <bool CORR>
-__global__ void dpred_t_grouped_kernel(const float* __restrict__ pred, const float* __restrict__ y, const int* __restrict__ group,
-                                       bf16* __restrict__ dpT, int B, int V, int64_t GV, float gscale,
-                                       const float* __restrict__ coef) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= GV * 16) return;
-  const int64_t row = i >> 4;
-  const int b = (int)(i & 15), g = (int)(row / V), v = (int)(row % V);
-  dpT[i] = (bf16)(b < B && group[b] == g ? dpred_own<CORR>(pred, y, b, v, V, gscale, coef) : 0.f);
-}
-
-// dW, dbias: grid G * ceil(V/RIDGE_ROWS), one row of dW per (g, v).  A clip of another head adds nothing to the row: it is
-// skipped, so a head without a clip gets the fp32 product l2coef * W and dbias = 0 exactly.
-template <bool CORR>
-__global__ __launch_bounds__(256) void ridge_bwd_w_grouped_kernel(const bf16* __restrict__ W, const bf16* __restrict__ z,
-                                                                  const float* __restrict__ pred, const float* __restrict__ y,
-                                                                  const int* __restrict__ group, float* __restrict__ dW,
-                                                                  float* __restrict__ dbias, int B, int E, int V, int bpg,
-                                                                  float gscale, float l2coef, const float* __restrict__ coef) {
-  extern __shared__ __attribute__((aligned(16))) char zsm[];     // [nb][E] bf16
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int g = blockIdx.x / bpg, vb = blockIdx.x % bpg;
-  for (int b0 = 0; b0 < B; b0 += BMAX) {
-    const int nb = min(BMAX, B - b0);
-    __syncthreads();
-    for (int i = threadIdx.x * 8; i < nb * E; i += 256 * 8)
-      *reinterpret_cast<bf16x8*>(zsm + (int64_t)i * 2) = *reinterpret_cast<const bf16x8*>(z + (int64_t)b0 * E + i);
-    __syncthreads();
-    bool mine[BMAX];
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i) mine[i] = i < nb && group[b0 + i] == g;
-    for (int rr = 0; rr < RIDGE_ROWS / 4; ++rr) {
-      const int v = vb * RIDGE_ROWS + wave * (RIDGE_ROWS / 4) + rr;
-      if (v >= V) break;
-      const int64_t row = (int64_t)g * V + v;
-      float dp[BMAX];
-      float db = 0.f;
-#pragma unroll
-      for (int i = 0; i < BMAX; ++i) {
-        dp[i] = mine[i] ? dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef) : 0.f;
-        db += dp[i];
-      }
-      if (lane == 0) dbias[row] = (b0 == 0 ? 0.f : dbias[row]) + db;
-      const bf16* wr = W + row * E;
-#pragma unroll 4
-      for (int c = lane * 8; c < E; c += 512) {
-        float gr[8];
-        float* o = dW + row * E + c;
-        if (b0 == 0) {
-          float w[8]; ld8(wr + c, w);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) gr[j] = l2coef * w[j];
-        } else {
-          const f32x4 lo = *reinterpret_cast<const f32x4*>(o), hi = *reinterpret_cast<const f32x4*>(o + 4);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { gr[j] = lo[j]; gr[4 + j] = hi[j]; }
-        }
-#pragma unroll
-        for (int i = 0; i < BMAX; ++i) {
-          if (mine[i]) {
-            float zz[8]; ld8(reinterpret_cast<const bf16*>(zsm) + (int64_t)i * E + c, zz);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) gr[j] += dp[i] * zz[j];
-          }
-        }
-        *reinterpret_cast<f32x4*>(o) = f32x4{gr[0], gr[1], gr[2], gr[3]};
-        *reinterpret_cast<f32x4*>(o + 4) = f32x4{gr[4], gr[5], gr[6], gr[7]};
-      }
-    }
-  }
-}
-
-// dz partials over V splits (B > 16): ridge_bwd_z_kernel with the rows of every head walked in turn, heads ascending; clip b
-// accumulates only over the rows of head group[b], in the ungrouped order.  grid (ceil(E/512), DZ_SPLIT).
-template <bool CORR>
-__global__ __launch_bounds__(256) void ridge_bwd_z_grouped_kernel(const bf16* __restrict__ W, const float* __restrict__ pred,
-                                                                  const float* __restrict__ y, const int* __restrict__ group,
-                                                                  float* __restrict__ part, int B, int E, int V, int G,
-                                                                  float gscale, const float* __restrict__ coef) {
-  __shared__ float red[3][BMAX][512];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 512 + lane * 8;
-  const int per = (V + DZ_SPLIT - 1) / DZ_SPLIT;
-  const int v0 = blockIdx.y * per, v1 = min(V, v0 + per);
-  for (int b0 = 0; b0 < B; b0 += BMAX) {
-    const int nb = min(BMAX, B - b0);
-    int gi[BMAX];
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i) gi[i] = i < nb ? group[b0 + i] : -1;
-    float acc[BMAX][8];
-#pragma unroll
-    for (int i = 0; i < BMAX; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
-    if (c < E) {
-      for (int g = 0; g < G; ++g) {
-        bool any = false;
-#pragma unroll
-        for (int i = 0; i < BMAX; ++i) any = any || gi[i] == g;
-        if (!any) continue;                                  // no clip of this pass reads head g: skip its rows
-        for (int v = v0 + wave; v < v1; v += 4) {
-          float w[8]; ld8(W + ((int64_t)g * V + v) * E + c, w);
-#pragma unroll
-          for (int i = 0; i < BMAX; ++i) {
-            if (gi[i] == g) {
-              const float dp = dpred_own<CORR>(pred, y, b0 + i, v, V, gscale, coef);
-#pragma unroll
-              for (int j = 0; j < 8; ++j) acc[i][j] += dp * w[j];
-            }
-          }
-        }
-      }
-    }
-    __syncthreads();
-    if (wave > 0) {
-#pragma unroll
-      for (int i = 0; i < BMAX; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) red[wave - 1][i][lane * 8 + j] = acc[i][j];
-    }
-    __syncthreads();
-    if (wave == 0 && c < E) {
-#pragma unroll
-      for (int i = 0; i < BMAX; ++i) {
-        if (i < nb) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            part[((int64_t)blockIdx.y * B + b0 + i) * E + c + j] =
-                acc[i][j] + red[0][i][lane * 8 + j] + red[1][i][lane * 8 + j] + red[2][i][lane * 8 + j];
-        }
-      }
-    }
-  }
-}
-
-int reserve_grouped_lds(int bytes) {
-  static int reserved = 0;
-  if (bytes > reserved) {
-    hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_fwd_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_grouped_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e2 == hipSuccess)
-      e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&ridge_bwd_w_grouped_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e1 != hipSuccess || e2 != hipSuccess) { vlb_set_error("head: cannot reserve %d bytes of LDS for z", bytes); return VLB_ERR_LAUNCH; }
-    reserved = bytes;
-  }
-  return VLB_OK;
-}
-
-// the grouped planner: which forward form, how many (sum err^2, sum W^2) pairs it leaves, which dz form
-constexpr int64_t GROUPED_MAX_ROWS = (int64_t)1 << 27;      // G*V: 16 bf16 per row of d pred^T and every tile count fit an int
-int grouped_fwd_parts(int B, int E, int V, int G) {
-  const bool mfma = B <= 16 && E % 128 == 0 && E <= 4096;
-  const int64_t ntiles = (int64_t)G * ((V + 15) / 16);
-  return mfma ? (int)(ntiles < 2048 ? ntiles : 2048) : G * ((V + RIDGE_ROWS - 1) / RIDGE_ROWS);
 }
 }  // namespace
 
@@ -1387,9 +1199,51 @@ extern "C" int vlb_head_fwd(const void* hidden, const float* wmask, const void* 
   hipStream_t st = as_stream(stream);
   float* lpart = ws + (int64_t)B * vlb_head_partial_rows(S) * (E + 2);
   if (int rc = head_pool(hidden, wmask, ws, stats, pooled_raw, sumw, B, S, E, eps, cu_rows, st)) return rc;
-  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, lpart, zhat, ln2_rstd,
-                       z, pred, loss_terms, B, E, V, eps, l2_lambda, st);
+  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, nullptr, lpart, zhat,
+                       ln2_rstd, z, pred, nullptr, loss_terms, nullptr, B, E, V, 1, eps, l2_lambda, VLB_LOSS_MSE, st);
 }
+
+namespace {
+// vlb_head_bwd (loss_kind = VLB_LOSS_MSE, rowstat = nullptr) and vlb_head_bwd_loss, which checks its loss_kind first
+int head_bwd_entry(const char* who, const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w,
+                   const void* ridge_w, const float* y, const float* keep_scale, const float* stats, const float* pooled_raw,
+                   const float* sumw, const float* zhat, const float* ln2_rstd, const void* z, const float* pred,
+                   float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws,
+                   float* dz_ws, float* dpooled_ws, void* dhidden, int B, int S, int E, int V, float l2_lambda, float loss_scale,
+                   float l2_scale, const int* cu_rows, int total_rows, void* stream, int loss_kind, const float* rowstat) {
+  VLB_REQUIRE(hidden && wmask && ln1_w && ln2_w && ridge_w && y && stats && pooled_raw && sumw && zhat && ln2_rstd && z &&
+                  pred && d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
+              "%s: null argument", who);
+  VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "%s: bad shape", who);
+  const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
+  VLB_REQUIRE(!dhidden || (rows > 0 && rows <= (int64_t)B * S), "%s: total_rows=%d out of range", who, total_rows);
+  if (int rc = head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, nullptr, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
+                               d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, rowstat, B, E, V, 1, l2_lambda,
+                               loss_scale, l2_scale, loss_kind, stream))
+    return rc;
+  if (dhidden) {
+    head_dhidden_launch(hidden, wmask, stats, dpooled_ws, dhidden, B, S, E, rows, cu_rows, as_stream(stream));
+    VLB_LAUNCH_CHECK();
+  }
+  return VLB_OK;
+}
+
+// vlb_head_bwd_cached and vlb_head_bwd_cached_loss likewise
+int head_bwd_cached_entry(const char* who, const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
+                          const float* keep_scale, const float* pooled_raw, const float* sumw, const float* zhat,
+                          const float* ln2_rstd, const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b,
+                          float* d_ln2_w, float* d_ln2_b, float* d_ln1_w, float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws,
+                          int B, int E, int V, float l2_lambda, float loss_scale, float l2_scale, void* stream, int loss_kind,
+                          const float* rowstat) {
+  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w && d_ridge_b &&
+                  d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
+              "%s: null argument", who);
+  VLB_REQUIRE(B > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "%s: bad shape", who);
+  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, nullptr, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
+                         d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, rowstat, B, E, V, 1, l2_lambda,
+                         loss_scale, l2_scale, loss_kind, stream);
+}
+}  // namespace
 
 extern "C" int vlb_head_bwd(const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w,
                             const void* ridge_w, const float* y, const float* keep_scale, const float* stats,
@@ -1399,23 +1253,9 @@ extern "C" int vlb_head_bwd(const void* hidden, const float* wmask, const void* 
                             void* dhidden, int B, int S, int E, int V, float eps, float l2_lambda, float loss_scale,
                             float l2_scale, const int* cu_rows, int total_rows, void* stream) {
   (void)eps;
-  VLB_REQUIRE(hidden && wmask && ln1_w && ln2_w && ridge_w && y && stats && pooled_raw && sumw && zhat && ln2_rstd && z &&
-                  pred && d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
-              "head_bwd: null argument");
-  VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd: bad shape");
-  if (int rc = head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
-                               d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale,
-                               l2_scale, stream))
-    return rc;
-  hipStream_t st = as_stream(stream);
-  if (dhidden) {
-    const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
-    VLB_REQUIRE(rows > 0 && rows <= (int64_t)B * S, "head_bwd: total_rows=%d out of range", total_rows);
-    hipLaunchKernelGGL(head_dhidden_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const bf16*)hidden,
-                       wmask, stats, dpooled_ws, (bf16*)dhidden, S, E, rows, B, cu_rows);
-    VLB_LAUNCH_CHECK();
-  }
-  return VLB_OK;
+  return head_bwd_entry("head_bwd", hidden, wmask, ln1_w, ln2_w, ridge_w, y, keep_scale, stats, pooled_raw, sumw, zhat, ln2_rstd, z,
+                        pred, d_ridge_w, d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, dhidden, B, S, E, V,
+                        l2_lambda, loss_scale, l2_scale, cu_rows, total_rows, stream, VLB_LOSS_MSE, nullptr);
 }
 
 // ---------------------------------------------------------------- frozen-backbone feature cache
@@ -1439,11 +1279,10 @@ extern "C" int vlb_head_fwd_cached(const float* cache_pooled, const float* cache
   VLB_REQUIRE(B > 0 && V > 0 && n_rows > 0 && E % 8 == 0 && E > 0 && E <= 8192,
               "head_fwd_cached: bad shape B=%d E=%d V=%d n_rows=%d", B, E, V, n_rows);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
-                     pooled_raw, sumw, E, n_rows);
+  feature_cache_gather_launch(cache_pooled, cache_sumw, rows, pooled_raw, sumw, B, E, n_rows, st);
   VLB_LAUNCH_CHECK();
-  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, ws, zhat, ln2_rstd, z,
-                       pred, loss_terms, B, E, V, eps, l2_lambda, st);
+  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, nullptr, ws, zhat, ln2_rstd, z,
+                       pred, nullptr, loss_terms, nullptr, B, E, V, 1, eps, l2_lambda, VLB_LOSS_MSE, st);
 }
 
 // The features the ridge layer reads, for the closed-form fit (ridge_solve.hip): the same gather, the same LN2 launch with
@@ -1456,8 +1295,7 @@ extern "C" int vlb_head_features_cached(const float* cache_pooled, const float* 
   VLB_REQUIRE(B > 0 && n_rows > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_features_cached: bad shape B=%d E=%d n_rows=%d", B, E,
               n_rows);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
-                     pooled_raw, sumw, E, n_rows);
+  feature_cache_gather_launch(cache_pooled, cache_sumw, rows, pooled_raw, sumw, B, E, n_rows, st);
   VLB_LAUNCH_CHECK();
   return head_ln2_launch(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, nullptr, zhat, ln2_rstd, z, B, E, eps, st);
 }
@@ -1469,13 +1307,9 @@ extern "C" int vlb_head_bwd_cached(const void* ln1_w, const void* ln2_w, const v
                                    float* dpooled_ws, int B, int E, int V, float eps, float l2_lambda, float loss_scale,
                                    float l2_scale, void* stream) {
   (void)eps;
-  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w && d_ridge_b &&
-                  d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
-              "head_bwd_cached: null argument");
-  VLB_REQUIRE(B > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_cached: bad shape");
-  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
-                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
-                         stream);
+  return head_bwd_cached_entry("head_bwd_cached", ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred,
+                               d_ridge_w, d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda,
+                               loss_scale, l2_scale, stream, VLB_LOSS_MSE, nullptr);
 }
 
 // ---------------------------------------------------------------- correlation objectives: entry points
@@ -1486,16 +1320,10 @@ extern "C" int vlb_head_loss_fwd(const float* pred, const float* y, const float*
   VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_loss_fwd: unknown loss_kind %d", loss_kind);
   VLB_REQUIRE(B > 0 && S >= 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_loss_fwd: bad shape B=%d S=%d E=%d V=%d", B, S, E, V);
   VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_loss_fwd: pearson needs V >= 2 (V=%d)", V);
-  hipStream_t st = as_stream(stream);
   // where the forward left the ridge partials: behind the pooling slabs (vlb_head_fwd), or at ws (vlb_head_fwd_cached)
   const float* lpart = ws + (S > 0 ? (int64_t)B * vlb_head_partial_rows(S) * (E + 2) : 0);
-  if (loss_kind == VLB_LOSS_PEARSON) hipLaunchKernelGGL(head_rowstat_kernel<true>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
-  else hipLaunchKernelGGL(head_rowstat_kernel<false>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
-  VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loss_finalize_corr_kernel, dim3(1), dim3(256), 0, st, lpart, ridge_fwd_parts(B, E, V),
-                     1.f / ((float)B * (float)V), l2_lambda, rowstat, B, loss_terms, loss_aux);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  return head_loss_corr_launch(pred, y, lpart, ridge_fwd_parts(B, E, V, 1, ridge_fwd_is_mfma(B, E)), rowstat, loss_terms, loss_aux, B,
+                               V, loss_kind, l2_lambda, as_stream(stream));
 }
 
 extern "C" int vlb_head_bwd_loss(const void* hidden, const float* wmask, const void* ln1_w, const void* ln2_w,
@@ -1507,25 +1335,13 @@ extern "C" int vlb_head_bwd_loss(const void* hidden, const float* wmask, const v
                                  float l2_scale, const int* cu_rows, int total_rows, void* stream, int loss_kind,
                                  const float* rowstat) {
   (void)eps;
-  VLB_REQUIRE(hidden && wmask && ln1_w && ln2_w && ridge_w && y && stats && pooled_raw && sumw && zhat && ln2_rstd && z &&
-                  pred && d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws && rowstat,
-              "head_bwd_loss: null argument");
+  VLB_REQUIRE(rowstat, "head_bwd_loss: null argument");
   VLB_REQUIRE(loss_kind != VLB_LOSS_MSE, "head_bwd_loss: loss_kind 0 (mse) is vlb_head_bwd's");
   VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_bwd_loss: unknown loss_kind %d", loss_kind);
-  VLB_REQUIRE(B > 0 && S > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_loss: bad shape");
   VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_loss: pearson needs V >= 2 (V=%d)", V);
-  const int64_t rows = cu_rows ? (int64_t)total_rows : (int64_t)B * S;
-  VLB_REQUIRE(!dhidden || (rows > 0 && rows <= (int64_t)B * S), "head_bwd_loss: total_rows=%d out of range", total_rows);
-  if (int rc = head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w,
-                               d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale,
-                               l2_scale, stream, loss_kind, rowstat))
-    return rc;
-  if (dhidden) {
-    hipLaunchKernelGGL(head_dhidden_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, as_stream(stream), (const bf16*)hidden,
-                       wmask, stats, dpooled_ws, (bf16*)dhidden, S, E, rows, B, cu_rows);
-    VLB_LAUNCH_CHECK();
-  }
-  return VLB_OK;
+  return head_bwd_entry("head_bwd_loss", hidden, wmask, ln1_w, ln2_w, ridge_w, y, keep_scale, stats, pooled_raw, sumw, zhat, ln2_rstd,
+                        z, pred, d_ridge_w, d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, dhidden, B, S, E, V,
+                        l2_lambda, loss_scale, l2_scale, cu_rows, total_rows, stream, loss_kind, rowstat);
 }
 
 extern "C" int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
@@ -1535,22 +1351,19 @@ extern "C" int vlb_head_bwd_cached_loss(const void* ln1_w, const void* ln2_w, co
                                         float* dz_ws, float* dpooled_ws, int B, int E, int V, float eps, float l2_lambda,
                                         float loss_scale, float l2_scale, void* stream, int loss_kind, const float* rowstat) {
   (void)eps;
-  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && pooled_raw && sumw && zhat && ln2_rstd && z && pred && d_ridge_w && d_ridge_b &&
-                  d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws && rowstat,
-              "head_bwd_cached_loss: null argument");
+  VLB_REQUIRE(rowstat, "head_bwd_cached_loss: null argument");
   VLB_REQUIRE(loss_kind != VLB_LOSS_MSE, "head_bwd_cached_loss: loss_kind 0 (mse) is vlb_head_bwd_cached's");
   VLB_REQUIRE(loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON, "head_bwd_cached_loss: unknown loss_kind %d", loss_kind);
-  VLB_REQUIRE(B > 0 && V > 0 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_cached_loss: bad shape");
   VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_cached_loss: pearson needs V >= 2 (V=%d)", V);
-  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
-                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda, loss_scale, l2_scale,
-                         stream, loss_kind, rowstat);
+  return head_bwd_cached_entry("head_bwd_cached_loss", ln1_w, ln2_w, ridge_w, y, keep_scale, pooled_raw, sumw, zhat, ln2_rstd, z, pred,
+                               d_ridge_w, d_ridge_b, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, B, E, V, l2_lambda,
+                               loss_scale, l2_scale, stream, loss_kind, rowstat);
 }
 
 // ---------------------------------------------------------------- per-subject ridge heads on one trunk: the grouped tail
 extern "C" int64_t vlb_head_grouped_ws_floats(int B, int E, int V, int G) {
   if (B <= 0 || E <= 0 || V <= 0 || G <= 0 || (int64_t)G * V > GROUPED_MAX_ROWS) return 0;
-  const int64_t fwd = 2 * (int64_t)G * ((V + 15) / 16);                  // >= 2 * grouped_fwd_parts, either form
+  const int64_t fwd = 2 * (int64_t)G * ((V + 15) / 16);                  // >= 2 * ridge_fwd_parts, either form
   const int64_t bwd = head_bwd_ws_floats(B, E, G * V) + 4 * (int64_t)B;  // + coef[B][4] of the correlation objectives
   return bwd > fwd ? bwd : fwd;
 }
@@ -1571,48 +1384,10 @@ extern "C" int vlb_head_fwd_grouped(const float* cache_pooled, const float* cach
   VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_fwd_grouped: G*V = %lld rows, at most 2^27", (long long)G * V);
   VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_fwd_grouped: pearson needs V >= 2 (V=%d)", V);
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, cache_pooled, cache_sumw, rows,
-                     pooled_raw, sumw, E, n_rows);
+  feature_cache_gather_launch(cache_pooled, cache_sumw, rows, pooled_raw, sumw, B, E, n_rows, st);
   VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_ln2_kernel, dim3(B), dim3(1024), 0, st, pooled_raw, sumw, (const bf16*)ln1_w, (const bf16*)ln1_b,
-                     (const bf16*)ln2_w, (const bf16*)ln2_b, keep_scale, zhat, ln2_rstd, (bf16*)z, E, eps);
-  VLB_LAUNCH_CHECK();
-  float* lpart = ws;
-  const int parts = grouped_fwd_parts(B, E, V, G);
-  if (B <= 16 && E % 128 == 0 && E <= 4096) {
-    const int tpg = (V + 15) / 16, ntiles = G * tpg;       // persistent over row tiles: parts = min(ntiles, 2048) blocks
-    switch (E / 128) {
-#define VLB_RIDGE_CASE(KS) case KS: hipLaunchKernelGGL(ridge_fwd_grouped_mfma_kernel<KS>, dim3(parts), dim3(256), 0, st, \
-                                                       (const bf16*)ridge_w, (const bf16*)ridge_b, (const bf16*)z, y, group, pred, lpart, \
-                                                       B, E, V, tpg, ntiles); break;
-      VLB_RIDGE_CASE(1) VLB_RIDGE_CASE(2) VLB_RIDGE_CASE(3) VLB_RIDGE_CASE(4) VLB_RIDGE_CASE(5) VLB_RIDGE_CASE(6) VLB_RIDGE_CASE(7)
-      VLB_RIDGE_CASE(8) VLB_RIDGE_CASE(9) VLB_RIDGE_CASE(10) VLB_RIDGE_CASE(11) VLB_RIDGE_CASE(12) VLB_RIDGE_CASE(13)
-      VLB_RIDGE_CASE(14) VLB_RIDGE_CASE(15) VLB_RIDGE_CASE(16) VLB_RIDGE_CASE(17) VLB_RIDGE_CASE(18) VLB_RIDGE_CASE(19)
-      VLB_RIDGE_CASE(20) VLB_RIDGE_CASE(21) VLB_RIDGE_CASE(22) VLB_RIDGE_CASE(23) VLB_RIDGE_CASE(24) VLB_RIDGE_CASE(25)
-      VLB_RIDGE_CASE(26) VLB_RIDGE_CASE(27) VLB_RIDGE_CASE(28) VLB_RIDGE_CASE(29) VLB_RIDGE_CASE(30) VLB_RIDGE_CASE(31)
-      VLB_RIDGE_CASE(32)
-#undef VLB_RIDGE_CASE
-    }
-  } else {
-    const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-    const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-    if (int rc2 = reserve_grouped_lds(zlds)) return rc2;
-    hipLaunchKernelGGL(ridge_fwd_grouped_kernel, dim3(parts), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b,
-                       (const bf16*)z, y, group, pred, lpart, B, E, V, bpg);
-  }
-  VLB_LAUNCH_CHECK();
-  const float inv_bv = 1.f / ((float)B * (float)V);
-  if (loss_kind == VLB_LOSS_MSE) {
-    hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, parts, inv_bv, l2_lambda, loss_terms);
-  } else {
-    if (loss_kind == VLB_LOSS_PEARSON) hipLaunchKernelGGL(head_rowstat_kernel<true>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
-    else hipLaunchKernelGGL(head_rowstat_kernel<false>, dim3(B), dim3(1024), 0, st, pred, y, rowstat, V);
-    VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(loss_finalize_corr_kernel, dim3(1), dim3(256), 0, st, lpart, parts, inv_bv, l2_lambda, rowstat, B,
-                       loss_terms, loss_aux);
-  }
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  return head_fwd_tail(pooled_raw, sumw, ln1_w, ln1_b, ln2_w, ln2_b, ridge_w, ridge_b, y, keep_scale, group, ws, zhat, ln2_rstd, z,
+                       pred, rowstat, loss_terms, loss_aux, B, E, V, G, eps, l2_lambda, loss_kind, st);
 }
 
 extern "C" int vlb_head_bwd_grouped(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y,
@@ -1631,53 +1406,9 @@ extern "C" int vlb_head_bwd_grouped(const void* ln1_w, const void* ln2_w, const 
   VLB_REQUIRE(B > 0 && V > 0 && G >= 1 && E % 8 == 0 && E > 0 && E <= 8192, "head_bwd_grouped: bad shape B=%d E=%d V=%d G=%d", B, E, V, G);
   VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_bwd_grouped: G*V = %lld rows, at most 2^27", (long long)G * V);
   VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_grouped: pearson needs V >= 2 (V=%d)", V);
-  hipStream_t st = as_stream(stream);
-  const int GV = G * V;
-  const float gscale = loss_scale * 2.f / ((float)B * (float)V);      // B: the whole batch, whatever the heads' shares
-  const float l2coef = l2_scale * 2.f * l2_lambda;
-  const int bpg = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-  const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-  if (int rc2 = reserve_grouped_lds(zlds)) return rc2;
-  float* coef = ws + head_bwd_ws_floats(B, E, GV);
-  const bool corr = loss_kind != VLB_LOSS_MSE;
-  if (corr) {
-    hipLaunchKernelGGL(head_loss_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rowstat, coef, B, loss_scale);
-    VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ridge_bwd_w_grouped_kernel<true>, dim3(G * bpg), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z,
-                       pred, y, group, d_ridge_w, d_ridge_b, B, E, V, bpg, gscale, l2coef, coef);
-  } else {
-    hipLaunchKernelGGL(ridge_bwd_w_grouped_kernel<false>, dim3(G * bpg), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)z,
-                       pred, y, group, d_ridge_w, d_ridge_b, B, E, V, bpg, gscale, l2coef, coef);
-  }
-  VLB_LAUNCH_CHECK();
-  if (B <= 16 && E % 8 == 0) {
-    // dz[b,e] = sum_{(g,v)} dpT[g*V+v, b] W[g*V+v, e]: one skinny-wgrad contraction over all G*V rows (zeros off the clip's head)
-    const int splits = vlb_wgrad_splits(GV);
-    float* wg_ws = ws;                                             // [splits][16][E]
-    float* dz16 = ws + (int64_t)splits * 16 * E;                   // [16][E]
-    bf16* dpT = reinterpret_cast<bf16*>(dz16 + (int64_t)16 * E);   // [G*V][16] bf16
-    const dim3 tgrid((unsigned)(((int64_t)GV * 16 + 255) / 256));
-    if (corr) hipLaunchKernelGGL(dpred_t_grouped_kernel<true>, tgrid, dim3(256), 0, st, pred, y, group, dpT, B, V, (int64_t)GV, gscale, coef);
-    else hipLaunchKernelGGL(dpred_t_grouped_kernel<false>, tgrid, dim3(256), 0, st, pred, y, group, dpT, B, V, (int64_t)GV, gscale, coef);
-    VLB_LAUNCH_CHECK();
-    int rc3 = vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, GV, 16, E, 1.f, 0.f, 0.f, nullptr, stream);
-    if (rc3 != VLB_OK) return rc3;
-    hipLaunchKernelGGL(head_dz_from16_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, dz16, keep_scale, dz_ws, E);
-    VLB_LAUNCH_CHECK();
-  } else {
-    const dim3 zgrid((E + 511) / 512, DZ_SPLIT);
-    if (corr) hipLaunchKernelGGL(ridge_bwd_z_grouped_kernel<true>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, group, ws, B, E, V, G, gscale, coef);
-    else hipLaunchKernelGGL(ridge_bwd_z_grouped_kernel<false>, zgrid, dim3(256), 0, st, (const bf16*)ridge_w, pred, y, group, ws, B, E, V, G, gscale, coef);
-    VLB_LAUNCH_CHECK();
-    hipLaunchKernelGGL(head_dz_reduce_kernel, dim3((E + 255) / 256, B), dim3(256), 0, st, ws, keep_scale, dz_ws, B, E);
-    VLB_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(head_ln2_bwd_kernel, dim3(B), dim3(1024), 0, st, dz_ws, (const bf16*)ln2_w, zhat, ln2_rstd, dpooled_ws, E);
-  VLB_LAUNCH_CHECK();
-  hipLaunchKernelGGL(head_param_grads_kernel, dim3((E + 255) / 256), dim3(256), 0, st, dz_ws, dpooled_ws, (const bf16*)ln1_w,
-                     pooled_raw, sumw, zhat, d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, B, E);
-  VLB_LAUNCH_CHECK();
-  return VLB_OK;
+  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, group, pooled_raw, sumw, zhat, ln2_rstd, z, pred, d_ridge_w, d_ridge_b,
+                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, rowstat, B, E, V, G, l2_lambda, loss_scale,
+                         l2_scale, loss_kind, stream);
 }
 
 // ---------------------------------------------------------------- readout from chosen layers: pool, mix, d hidden on their own
@@ -1692,8 +1423,7 @@ extern "C" int vlb_feature_cache_gather(const float* cache_pooled, const float* 
                                         float* sumw, int B, int E, int n_rows, void* stream) {
   VLB_REQUIRE(cache_pooled && cache_sumw && rows && pooled_raw && sumw, "feature_cache_gather: null argument");
   VLB_REQUIRE(B > 0 && E > 0 && n_rows > 0, "feature_cache_gather: bad shape B=%d E=%d n_rows=%d", B, E, n_rows);
-  hipLaunchKernelGGL(feature_cache_gather_kernel, dim3((E + 255) / 256, B), dim3(256), 0, as_stream(stream), cache_pooled,
-                     cache_sumw, rows, pooled_raw, sumw, E, n_rows);
+  feature_cache_gather_launch(cache_pooled, cache_sumw, rows, pooled_raw, sumw, B, E, n_rows, as_stream(stream));
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
@@ -1747,8 +1477,7 @@ extern "C" int vlb_head_dhidden(const void* hidden, const float* wmask, const fl
     else VLB_DH_ACC(16);
 #undef VLB_DH_ACC
   } else
-    hipLaunchKernelGGL(head_dhidden_kernel, grid, dim3(256), 0, st, (const bf16*)hidden, wmask, stats, draw, (bf16*)dx, S, E, rows,
-                       B, cu_rows);
+    head_dhidden_launch(hidden, wmask, stats, draw, dx, B, S, E, rows, cu_rows, st);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
@@ -1780,13 +1509,10 @@ extern "C" int vlb_ridge_fwd(const void* x, const void* ridge_w, const void* rid
                              int V, float l2_lambda, void* stream) {
   VLB_REQUIRE(x && ridge_w && ridge_b && pred && l2_out && ws && B > 0 && V > 0 && E > 0 && E % 8 == 0, "ridge_fwd: bad arguments");
   hipStream_t st = as_stream(stream);
-  const int rblk = (V + RIDGE_ROWS - 1) / RIDGE_ROWS;
-  const int zlds = (B < BMAX ? B : BMAX) * E * 2;
-  if (int rc = reserve_ridge_lds(zlds)) return rc;
+  // y = nullptr: no error term.  The layer on its own always runs the scalar form: its bits do not depend on (B, E).
+  const int rblk = ridge_fwd_launch(ridge_w, ridge_b, x, nullptr, nullptr, pred, ws, B, E, V, 1, false, st);
+  if (rblk < 0) return rblk;
   float* terms = ws + 2 * (int64_t)rblk;
-  hipLaunchKernelGGL(ridge_fwd_kernel, dim3(rblk), dim3(256), zlds, st, (const bf16*)ridge_w, (const bf16*)ridge_b, (const bf16*)x,
-                     (const float*)nullptr, pred, ws, B, E, V);
-  VLB_LAUNCH_CHECK();
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, ws, rblk, 1.f / ((float)B * (float)V), l2_lambda, terms);
   VLB_LAUNCH_CHECK();
   hipError_t e = hipMemcpyAsync(l2_out, terms + 1, sizeof(float), hipMemcpyDeviceToDevice, st);

@@ -4,11 +4,11 @@ tests/head_emul.py (``H``: the staged fp64 head) and tests/head_loss_emul.py (``
 kernels vlb_head_fwd_grouped / vlb_head_bwd_grouped launch:
 
   ln2          head_ln2_kernel                      unchanged, shared by all heads                        (H.ln2)
-  ridge        ridge_fwd_grouped_mfma_kernel<KS> / ridge_fwd_grouped_kernel + loss_finalize[_corr]_kernel
+  ridge        ridge_fwd_mfma_kernel<KS,grouped> / ridge_fwd_kernel<grouped> + loss_finalize[_corr]_kernel
   rowstat/loss head_rowstat_kernel, loss_finalize_corr_kernel on the [B,V] rows (cosine / pearson only)   (L.rowstat ...)
-  ridge_bwd_w  ridge_bwd_w_grouped_kernel<CORR>     dW [G,V,E], dbias [G,V]
-  dz           dpred_t_grouped_kernel + skinny wgrad over all G*V rows + head_dz_from16, or
-               ridge_bwd_z_grouped_kernel + head_dz_reduce
+  ridge_bwd_w  ridge_bwd_w_kernel<CORR,grouped>     dW [G,V,E], dbias [G,V]
+  dz           dpred_t_kernel<CORR,grouped> + skinny wgrad over all G*V rows + head_dz_from16, or
+               ridge_bwd_z_kernel<CORR,grouped> + head_dz_reduce
   ln2_bwd      head_ln2_bwd_kernel + head_param_grads_kernel, unchanged                                   (H.ln2_bwd)
 
 Semantics.  W [G,V,E], bias [G,V], group[b] in [0,G):  pred[b] = W[group[b]] z[b] + bias[group[b]];  the data term is the
@@ -56,7 +56,7 @@ GROUPED_MAX_ROWS = 1 << 27
 
 # ---------------------------------------------------------------------------------------------------- the planner
 def grouped_fwd_parts(B, E, V, G):
-    """grouped_fwd_parts of head.hip: (sum err^2, sum W^2) pairs the grouped ridge forward leaves, one per block"""
+    """ridge_fwd_parts of head.hip with G heads: (sum err^2, sum W^2) pairs the grouped ridge forward leaves, one per block"""
     ntiles = G * H.cdiv(V, 16)
     return min(ntiles, 2048) if H.mfma_ridge(B, E) else G * H.cdiv(V, 16)
 
@@ -69,19 +69,19 @@ def tile_of(t, V):
 
 def dispatch(B, E, G):
     """Kernels vlb_head_fwd_grouped + vlb_head_bwd_grouped run for (B, E): their branch conditions, restated"""
-    k = {"feature_cache_gather_kernel", "head_ln2_kernel", "ridge_bwd_w_grouped_kernel", f"ridge_bwd_w:b0_passes={H.cdiv(B, 8)}",
+    k = {"feature_cache_gather_kernel", "head_ln2_kernel", "ridge_bwd_w_kernel<grouped>", f"ridge_bwd_w:b0_passes={H.cdiv(B, 8)}",
          "head_ln2_bwd_kernel", "head_param_grads_kernel"}
-    k.add(f"ridge_fwd_grouped_mfma_kernel<{E // 128}>" if B <= 16 and E % 128 == 0 and E <= 4096 else "ridge_fwd_grouped_kernel")
+    k.add(f"ridge_fwd_mfma_kernel<{E // 128},grouped>" if B <= 16 and E % 128 == 0 and E <= 4096 else "ridge_fwd_kernel<grouped>")
     if B <= 16 and E % 8 == 0:
-        k |= {"dpred_t_grouped_kernel", "wgrad_mfma_kernel", "head_dz_from16_kernel"}
+        k |= {"dpred_t_kernel<grouped>", "wgrad_mfma_kernel", "head_dz_from16_kernel"}
     else:
-        k |= {"ridge_bwd_z_grouped_kernel", "head_dz_reduce_kernel"}
+        k |= {"ridge_bwd_z_kernel<grouped>", "head_dz_reduce_kernel"}
     return k
 
 
 # ---------------------------------------------------------------------------------------------------- cases
-_SK = ("dpred_t_grouped_kernel", "wgrad_mfma_kernel", "head_dz_from16_kernel")
-_BIG = ("ridge_fwd_grouped_kernel", "ridge_bwd_z_grouped_kernel", "head_dz_reduce_kernel")
+_SK = ("dpred_t_kernel<grouped>", "wgrad_mfma_kernel", "head_dz_from16_kernel")
+_BIG = ("ridge_fwd_kernel<grouped>", "ridge_bwd_z_kernel<grouped>", "head_dz_reduce_kernel")
 
 
 def _case(id, E, B, V, G, subjects, expect=(), **kw):
@@ -92,17 +92,17 @@ def _case(id, E, B, V, G, subjects, expect=(), **kw):
 
 
 CASES = [
-    _case("g3-B5", 512, 5, 40, 3, [2, 0, 2, 1, 0], expect=("ridge_fwd_grouped_mfma_kernel<4>",) + _SK),
+    _case("g3-B5", 512, 5, 40, 3, [2, 0, 2, 1, 0], expect=("ridge_fwd_mfma_kernel<4,grouped>",) + _SK),
     # two absent heads (0 and 2); V = 17: the last tile of every head has one live row
-    _case("g4-absent", 512, 3, 17, 4, [3, 1, 3], expect=("ridge_fwd_grouped_mfma_kernel<4>",) + _SK),
-    _case("g3-V5", 512, 4, 5, 3, [0, 1, 2, 1], expect=("ridge_fwd_grouped_mfma_kernel<4>",) + _SK),      # heads smaller than a tile
+    _case("g4-absent", 512, 3, 17, 4, [3, 1, 3], expect=("ridge_fwd_mfma_kernel<4,grouped>",) + _SK),
+    _case("g3-V5", 512, 4, 5, 3, [0, 1, 2, 1], expect=("ridge_fwd_mfma_kernel<4,grouped>",) + _SK),      # heads smaller than a tile
     _case("g2-B16", 1024, 16, 40, 2, [i % 2 for i in range(16)],
-          expect=("ridge_fwd_grouped_mfma_kernel<8>", "ridge_bwd_w:b0_passes=2") + _SK),
+          expect=("ridge_fwd_mfma_kernel<8,grouped>", "ridge_bwd_w:b0_passes=2") + _SK),
     # the scalar forward and the grouped ridge_bwd_z, three b0 passes, dropout and both scales != 1; a head changes inside a pass
     _case("g3-B17", 1024, 17, 40, 3, [(2 * i + i // 5) % 3 for i in range(17)], drop=True, scales=(0.25, 0.5),
           expect=("ridge_bwd_w:b0_passes=3",) + _BIG),
-    _case("g2-E264", 264, 2, 48, 2, [1, 0], expect=("ridge_fwd_grouped_kernel",) + _SK),               # scalar forward, skinny dz
-    _case("g2-E4096", 4096, 3, 33, 2, [1, 0, 1], expect=("ridge_fwd_grouped_mfma_kernel<32>",) + _SK),  # KSTEPS = 32
+    _case("g2-E264", 264, 2, 48, 2, [1, 0], expect=("ridge_fwd_kernel<grouped>",) + _SK),               # scalar forward, skinny dz
+    _case("g2-E4096", 4096, 3, 33, 2, [1, 0, 1], expect=("ridge_fwd_mfma_kernel<32,grouped>",) + _SK),  # KSTEPS = 32
 ]
 BY_ID = {c["id"]: c for c in CASES}
 LOSS_CASES = ("g3-B5", "g3-B17")           # also run with loss = "cosine" and "pearson"
@@ -195,7 +195,7 @@ def _dpred(pred, y, inp_loss, rs, B, V, gscale, s, dt, bug=None, n_g=None):
 
 
 def ridge_bwd_w(dp, mag_dp, z, W, group, l2coef, dt=F64, bug=None):
-    """ridge_bwd_w_grouped_kernel -> dW [G,V,E], dbias [G,V] (+ their magnitudes, n_g): L.ridge_bwd_w per head"""
+    """ridge_bwd_w_kernel<grouped> -> dW [G,V,E], dbias [G,V] (+ their magnitudes, n_g): L.ridge_bwd_w per head"""
     G = W.shape[0]
     out = dict(dW=[], dbias=[], mag_dW=[], mag_dbias=[], n=[])
     for g, idx in enumerate(clips_of(group, G)):
@@ -332,7 +332,7 @@ def check_stages(bufs, inp, stages=STAGES + LOSS_STAGES):
         ref = ridge_bwd_w(dp, mag, bufs["z"], W, group, l2coef)
         put("ridge_bwd_w", ref, ridge_bwd_w_bars(ref, B, L.C_DP if corr else 2), ("dW", "dbias"))
     if "dz" in stages:
-        if B <= 16 and not corr:        # dpred_t_grouped_kernel's own bf16 rounding of the fp32 d pred, as H.dz forms it
+        if B <= 16 and not corr:        # dpred_t_kernel<grouped>'s own bf16 rounding of the fp32 d pred, as H.dz forms it
             dpz = (torch.tensor(gscale, dtype=F32) * (bufs["pred"].to(F32) - inp["y"].to(F32))).to(BF16).to(F64)
         else:
             dpz = dp

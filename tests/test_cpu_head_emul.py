@@ -64,8 +64,10 @@ def test_dispatch_restates_the_planner():
     import pathlib
     import re
     src = re.sub(r"\s+", " ", (pathlib.Path(__file__).resolve().parent.parent / "phantom_vlb_amd" / "csrc" / "head.hip").read_text())
-    for cond in ("if (B <= 16 && E % 128 == 0 && E <= 4096) {",           # head_fwd_tail: MFMA ridge, else ridge_fwd_kernel
-                 "if (B <= 16 && E % 8 == 0) {",                          # head_bwd_params: skinny wgrad, else ridge_bwd_z
+    for cond in ("bool ridge_fwd_is_mfma(int B, int E) { return B <= 16 && E % 128 == 0 && E <= 4096; }",      # the one MFMA condition ...
+                 "ridge_fwd_launch(ridge_w, ridge_b, z, y, group, pred, lpart, B, E, V, G, ridge_fwd_is_mfma(B, E), st);",   # ... head_fwd_tail asks
+                 "if (mfma) {",                                           # ridge_fwd_launch_as: MFMA ridge, else ridge_fwd_kernel
+                 "if (B <= 16 && E % 8 == 0) {",                          # ridge_bwd_launch: skinny wgrad, else ridge_bwd_z
                  "constexpr int BMAX = 8;", "for (int b0 = 0; b0 < B; b0 += BMAX) {",      # the b0 passes
                  "const int ni = (E + 511) / 512;",
                  "if (ni <= 1) rc = launch_pool<1>(", "else if (ni <= 2) rc = launch_pool<2>(",

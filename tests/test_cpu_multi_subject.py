@@ -342,25 +342,39 @@ def test_bars_reject_planted_bug(bug, cid):
 
 
 def test_grouped_dispatch_restates_the_planner():
-    """the branch conditions GE.dispatch / GE.grouped_fwd_parts / GE.tile_of copy are the ones the grouped entries of head.hip
-    branch on (the library does not report its launches; what can be held fast is the source text)"""
+    """the branch conditions GE.dispatch / GE.grouped_fwd_parts / GE.tile_of copy are the ones head.hip branches on (the
+    library does not report its launches; what can be held fast is the source text).  The plain and the grouped head share
+    one launcher per direction, so each condition is looked for in the ONE place it lives, and the grouped entries are held
+    to calling those bodies with (group, G)."""
     src = re.sub(r"\s+", " ", (pathlib.Path(ROOT) / "phantom_vlb_amd" / "csrc" / "head.hip").read_text())
-    fwd = src[src.index('extern "C" int vlb_head_fwd_grouped('):src.index('extern "C" int vlb_head_bwd_grouped(')]
-    bwd = src[src.index('extern "C" int vlb_head_bwd_grouped('):]
-    bwd = bwd[:bwd.index('extern "C" int vlb_head_pool(')]
-    assert "if (B <= 16 && E % 128 == 0 && E <= 4096) {" in fwd and "ridge_fwd_grouped_mfma_kernel<KS>" in fwd
-    assert "ridge_fwd_grouped_kernel" in fwd and "const int tpg = (V + 15) / 16, ntiles = G * tpg;" in fwd
+    entry_fwd = src[src.index('extern "C" int vlb_head_fwd_grouped('):src.index('extern "C" int vlb_head_bwd_grouped(')]
+    entry_bwd = src[src.index('extern "C" int vlb_head_bwd_grouped('):]
+    entry_bwd = entry_bwd[:entry_bwd.index('extern "C" int vlb_head_pool(')]
+    assert "return head_fwd_tail(" in entry_fwd and "keep_scale, group, ws," in entry_fwd and "B, E, V, G, eps," in entry_fwd
+    assert "return head_bwd_params(" in entry_bwd and "keep_scale, group, pooled_raw," in entry_bwd and "B, E, V, G, l2_lambda," in entry_bwd
+    assert "hipLaunchKernelGGL" not in entry_fwd + entry_bwd               # argument checks and a call: no launch of their own
+    tail = src[src.index("int head_fwd_tail("):src.index("int ridge_bwd_launch(")]
+    assert "ridge_fwd_launch(ridge_w, ridge_b, z, y, group, pred, lpart, B, E, V, G, ridge_fwd_is_mfma(B, E), st);" in tail
+    fwd = src[src.index("int ridge_fwd_launch_as("):src.index("int head_loss_corr_launch(")]
+    assert "if (mfma) {" in fwd and "ridge_fwd_mfma_kernel<KS, GROUPED>" in fwd
+    assert "ridge_fwd_kernel<GROUPED>" in fwd and "const int tpg = (V + 15) / 16, ntiles = G * tpg;" in fwd
+    assert "group ? ridge_fwd_launch_as<true>(" in fwd and ": ridge_fwd_launch_as<false>(" in fwd
+    bwd = src[src.index("int ridge_bwd_launch("):src.index("int head_bwd_params(")]
+    assert "const int GV = G * V;" in bwd
     assert "if (B <= 16 && E % 8 == 0) {" in bwd and "vlb_wgrad_skinny(dpT, 16, ridge_w, E, dz16, wg_ws, GV, 16, E," in bwd
-    assert "ridge_bwd_z_grouped_kernel" in bwd and "ridge_bwd_w_grouped_kernel" in bwd
-    for cond in ("const bool mfma = B <= 16 && E % 128 == 0 && E <= 4096;",
+    assert "ridge_bwd_z_kernel<CORR, GROUPED>" in bwd and "ridge_bwd_w_kernel<CORR, GROUPED>" in bwd and "dpred_t_kernel<CORR, GROUPED>" in bwd
+    for cond in ("bool ridge_fwd_is_mfma(int B, int E) { return B <= 16 && E % 128 == 0 && E <= 4096; }",
                  "return mfma ? (int)(ntiles < 2048 ? ntiles : 2048) : G * ((V + RIDGE_ROWS - 1) / RIDGE_ROWS);",
-                 "const int g = t / tpg, tl = t % tpg;", "constexpr int RIDGE_ROWS = 16;",
+                 "const int g = GROUPED ? t / tpg : 0, tl = GROUPED ? t % tpg : t;", "constexpr int RIDGE_ROWS = 16;",
                  "constexpr int64_t GROUPED_MAX_ROWS = (int64_t)1 << 27;"):
-        assert cond in src, cond
+        assert src.count(cond) == 1, cond
+    # one copy of each: the MFMA condition, the skinny-dz condition, the block cap, the skinny-wgrad call
+    for once in ("B <= 16 && E % 128 == 0 && E <= 4096", "if (B <= 16 && E % 8 == 0) {", "ntiles < 2048 ? ntiles : 2048", "vlb_wgrad_skinny("):
+        assert src.count(once) == 1, once
     assert GE.GROUPED_MAX_ROWS == 1 << 27
-    assert GE.dispatch(16, 4096, 2) >= {"ridge_fwd_grouped_mfma_kernel<32>", "wgrad_mfma_kernel"}
-    assert GE.dispatch(17, 1024, 3) >= {"ridge_fwd_grouped_kernel", "ridge_bwd_z_grouped_kernel", "ridge_bwd_w:b0_passes=3"}
-    assert "ridge_fwd_grouped_kernel" in GE.dispatch(2, 264, 2) and "wgrad_mfma_kernel" in GE.dispatch(2, 264, 2)
+    assert GE.dispatch(16, 4096, 2) >= {"ridge_fwd_mfma_kernel<32,grouped>", "wgrad_mfma_kernel"}
+    assert GE.dispatch(17, 1024, 3) >= {"ridge_fwd_kernel<grouped>", "ridge_bwd_z_kernel<grouped>", "ridge_bwd_w:b0_passes=3"}
+    assert "ridge_fwd_kernel<grouped>" in GE.dispatch(2, 264, 2) and "wgrad_mfma_kernel" in GE.dispatch(2, 264, 2)
     assert GE.grouped_fwd_parts(5, 512, 40, 3) == 9 and GE.grouped_fwd_parts(17, 1024, 40, 3) == 9
     assert GE.grouped_fwd_parts(3, 4096, 65536, 6) == 2048
     assert [GE.tile_of(t, 40) for t in (0, 2, 3, 5)] == [(0, 0), (0, 32), (1, 0), (1, 32)]

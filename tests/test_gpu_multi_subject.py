@@ -89,7 +89,10 @@ def test_grouped_stages(dev, cid, loss):
 @pytest.mark.parametrize("loss", ("mse",) + L.LOSSES)
 def test_one_group_gives_the_ungrouped_bits(dev, case, loss):
     """vlb_head_fwd_grouped / vlb_head_bwd_grouped called with G = 1 against vlb_head_fwd_cached (+ vlb_head_loss_fwd) /
-    vlb_head_bwd_cached[_loss] on the same (pooled_raw, sumw): every output bit-equal"""
+    vlb_head_bwd_cached[_loss] on the same (pooled_raw, sumw): every output bit-equal.  The two sides are the GROUPED = true
+    and GROUPED = false instantiations of ONE kernel template each: a real test of that switch (the (head, row) split, the
+    `group` test, the row offsets), but no anchor for the arithmetic the two share - that is test_gpu_head_ridge_bits.py,
+    which holds both to bits recorded from the library in which they were separate kernels"""
     from phantom_vlb_amd.head import BrainHead
     inp = H.make_inputs(case)
     E, V, B = case["E"], case["V"], case["B"]
