@@ -362,6 +362,40 @@ int vlb_head_bwd_grouped(const void* ln1_w, const void* ln2_w, const void* ridge
                          float* dpooled_ws, const float* rowstat, int B, int E, int V, int G, float eps, float l2_lambda,
                          float loss_scale, float l2_scale, int loss_kind, void* stream);
 
+/* Per-target loss weights and missing-target masks (opt-in; every entry point above keeps its launches and bits).
+ * tw: fp32 [H,V], H = max(1,G), one row per ridge head; every value finite and >= 0, every row with a positive value
+ * (two for pearson) - checked by the caller on the host.  For clip b of head g = group[b] (0 without group):
+ *   w_v = tw[g,v],  W_b = sum_v w_v
+ *   mse    :  m_b = sum_v w_v (p_v - y_v)^2 / W_b;  data term = (1/B) sum_b m_b
+ *   cosine :  u = p, t = y;   pearson: u = p - mu_p, t = y - mu_y with mu_p = sum w p / W_b, mu_y = sum w y / W_b
+ *             S_uu = sum w u^2, S_tt = sum w t^2, S_ut = sum w u t,
+ *             c_b = S_ut / (max(sqrt S_uu, 1e-8) max(sqrt S_tt, 1e-8));  data term = 1 - (1/B) sum_b c_b
+ *   d pred[b,v] = s 2 w_v (p_v - y_v) / (B W_b)            (mse; s = loss_scale)
+ *   d pred[b,v] = w_v (a_b u_v + b_b t_v)                    (cosine / pearson; a_b, b_b as for vlb_head_loss_fwd, on the
+ *                                                             weighted sums, autograd's convention under the clamp)
+ * The penalty is untouched: loss_terms[1] = lambda * sum ||W||^2 over every row, masked ones included.  Where w_v = 0
+ * neither pred nor y enters any arithmetic (a select, not a product): y may hold NaN / Inf there and every result keeps
+ * its bits; d pred is exactly 0 there, so a masked target's dW row is the fp32 product l2_scale*2*lambda*W and its dbias 0.
+ * A 0/1 mask gives the unweighted objective on the kept columns; tw -> c*tw changes nothing.
+ * vlb_head_wloss_fwd: runs on the outputs `pred` and `ws` of vlb_head_fwd (S as handed there, group NULL, G = 1),
+ *   vlb_head_fwd_cached (S = 0, group NULL, G = 1) or vlb_head_fwd_grouped called with VLB_LOSS_MSE (S = 0, group, G), before
+ *   anything else touches ws.  wstat: fp32 [B,8] = {mu_p, mu_y, S_uu, S_tt, S_ut, c_b, W_b, m_b} (mse: slots 0-5 are 0).
+ *   loss_terms = {data term, lambda * sum W^2 re-summed from the forward's partials (the bits the forward wrote), their sum};
+ *   loss_aux = {(1/B) sum_b m_b, (1/B) sum_b c_b}.  The forward's own sum (pred-y)^2 partials are not read.
+ * vlb_head_bwd_wloss: vlb_head_bwd_cached / vlb_head_bwd_grouped (group NULL with G = 1, or group with G heads) for this
+ *   objective: writes dpred fp32 [B,V], then the existing ridge / dropout / LN launches read d pred from it.  The uncached
+ *   route adds vlb_head_dhidden on dpooled_ws, as the grouped one does.  ws: vlb_head_ws_floats or vlb_head_grouped_ws_floats.
+ * Both refuse null pointers (keep_scale and group may be NULL), unknown loss_kind, pearson with V < 2 and bad shapes. */
+int vlb_head_wloss_fwd(const float* pred, const float* y, const float* tw, const int32_t* group, const float* ws, float* wstat,
+                       float* loss_terms, float* loss_aux, int B, int S, int E, int V, int G, int loss_kind, float l2_lambda,
+                       void* stream);
+int vlb_head_bwd_wloss(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* tw,
+                       const float* keep_scale, const int32_t* group, const float* pooled_raw, const float* sumw,
+                       const float* zhat, const float* ln2_rstd, const void* z, const float* pred, const float* wstat,
+                       float* dpred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
+                       float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, int G, float l2_lambda,
+                       float loss_scale, float l2_scale, int loss_kind, void* stream);
+
 /* Reading the head from K chosen decoder layers with a learned convex mix (opt-in; every entry point above keeps its
  * bits).  LN1's affine is per column and the pooling is linear, so the mix is taken on the pooled vectors:
  *   P_k = pooled_raw of tapped layer k (vlb_head_pool),  alpha = softmax(a),  pooled_raw = sum_k alpha_k P_k,

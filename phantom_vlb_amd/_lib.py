@@ -64,6 +64,8 @@ SIGNATURES = {
     "vlb_head_grouped_ws_floats": [I, I, I, I],
     "vlb_head_fwd_grouped": [P] * 22 + [I, I, I, I, I, F, F, I, P],
     "vlb_head_bwd_grouped": [P] * 22 + [I, I, I, I, F, F, F, F, I, P],
+    "vlb_head_wloss_fwd": [P] * 8 + [I, I, I, I, I, I, F, P],
+    "vlb_head_bwd_wloss": [P] * 24 + [I, I, I, I, F, F, F, I, P],
     "vlb_head_pool": [P] * 6 + [I, I, I, F, P, P],
     "vlb_feature_cache_gather": [P] * 5 + [I, I, I, P],
     "vlb_head_mix_fwd": [P] * 4 + [I, I, I, P],

@@ -505,18 +505,162 @@ __device__ __forceinline__ float dpred_corr(const float* __restrict__ coef, int 
   return c[0] * (p - c[2]) + c[1] * (yv - c[3]);
 }
 
+// ================================================================ per-target loss weights and masks
+// tw fp32 [H,V], H = max(1,G), every value finite and >= 0: clip b reads the row of its head, w_v = tw[group[b], v] (group
+// NULL: row 0).  Per clip  W_b = sum w,  m_b = sum w (p-y)^2 / W_b,  and for cosine / pearson  u = p - mu_p, t = y - mu_y with
+// mu = sum w (.) / W_b (0 for cosine),  S_uu = sum w u^2, S_tt = sum w t^2, S_ut = sum w u t,
+// c_b = S_ut / (max(sqrt S_uu, 1e-8) max(sqrt S_tt, 1e-8)).  A target with w_v = 0 is SELECTED away, never multiplied away:
+// pred and y there are loaded but enter no arithmetic, so NaN / Inf in a masked y changes no bit of any result.
+// The row walk is head_rowstat_kernel's (head, f32x4 body, tail; fixed-order block_sum, no atomics) over three rows.
+__device__ __forceinline__ void row_split3(const float* p, const float* q, const float* r, int V, int& head, int& nvec) {
+  const uintptr_t ap = reinterpret_cast<uintptr_t>(p), aq = reinterpret_cast<uintptr_t>(q), ar = reinterpret_cast<uintptr_t>(r);
+  if ((ap & 15) != (aq & 15) || (ap & 15) != (ar & 15)) { head = V; nvec = 0; return; }   // scalar throughout
+  head = (int)(((16 - (ap & 15)) & 15) >> 2);
+  if (head > V) head = V;
+  nvec = (V - head) >> 2;
+}
+
+// f(w, p, y) over one row in the fixed order: head one element per thread, f32x4 body, tail
+template <typename F>
+__device__ __forceinline__ void wrow_walk(const float* __restrict__ wr, const float* __restrict__ pr, const float* __restrict__ yr,
+                                          int V, int head, int nvec, F&& f) {
+  const int tid = threadIdx.x, tail0 = head + 4 * nvec;
+  for (int i = tid; i < head; i += 1024) f(wr[i], pr[i], yr[i]);
+  for (int k = tid; k < nvec; k += 1024) {
+    const f32x4 w = *reinterpret_cast<const f32x4*>(wr + head + 4 * k), a = *reinterpret_cast<const f32x4*>(pr + head + 4 * k),
+                c = *reinterpret_cast<const f32x4*>(yr + head + 4 * k);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f(w[j], a[j], c[j]);
+  }
+  for (int i = tail0 + tid; i < V; i += 1024) f(wr[i], pr[i], yr[i]);
+}
+
+// one block of 1024 per clip -> wstat[b] = {mu_p, mu_y, S_uu, S_tt, S_ut, c_b, W_b, m_b}  (mse: slots 0-5 are 0).
+// pearson takes two passes (W_b and the weighted means, then the centred sums); mse and cosine take one.
+template <int KIND>
+__global__ __launch_bounds__(1024) void head_wrowstat_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                             const float* __restrict__ tw, const int* __restrict__ group,
+                                                             float* __restrict__ wstat, int V) {
+  constexpr bool CENTRE = KIND == VLB_LOSS_PEARSON, CORRK = KIND != VLB_LOSS_MSE;
+  __shared__ float red[16];
+  const int b = blockIdx.x;
+  const float* pr = pred + (int64_t)b * V;
+  const float* yr = y + (int64_t)b * V;
+  const float* wr = tw + (int64_t)(group ? group[b] : 0) * V;
+  int head, nvec;
+  row_split3(pr, yr, wr, V, head, nvec);
+  float sw = 0.f, mp = 0.f, my = 0.f;
+  if constexpr (CENTRE) {
+    float sp = 0.f, sy = 0.f;
+    wrow_walk(wr, pr, yr, V, head, nvec, [&](float w, float p, float yv) {
+      if (w > 0.f) { sw += w; sp += w * p; sy += w * yv; }
+    });
+    sw = block_sum(sw, red);
+    mp = block_sum(sp, red) / sw;
+    my = block_sum(sy, red) / sw;
+  }
+  float suu = 0.f, stt = 0.f, sut = 0.f, sm = 0.f;
+  wrow_walk(wr, pr, yr, V, head, nvec, [&](float w, float p, float yv) {
+    if (w > 0.f) {
+      if constexpr (!CENTRE) sw += w;
+      const float d = p - yv;
+      sm += w * d * d;
+      if constexpr (CORRK) {
+        const float u = p - mp, t = yv - my;
+        suu += w * u * u; stt += w * t * t; sut += w * u * t;
+      }
+    }
+  });
+  if constexpr (!CENTRE) sw = block_sum(sw, red);
+  sm = block_sum(sm, red);
+  if constexpr (CORRK) {
+    suu = block_sum(suu, red);
+    stt = block_sum(stt, red);
+    sut = block_sum(sut, red);
+  }
+  if (threadIdx.x == 0) {
+    float* o = wstat + (int64_t)b * 8;
+    float cb = 0.f;
+    if constexpr (CORRK) {
+      const float nu = fmaxf(sqrtf(suu), 1e-8f), nt = fmaxf(sqrtf(stt), 1e-8f);      // F.cosine_similarity's clamp
+      cb = sut / (nu * nt);
+    }
+    o[0] = mp; o[1] = my; o[2] = suu; o[3] = stt; o[4] = sut; o[5] = cb; o[6] = sw; o[7] = sm / sw;
+  }
+}
+
+// one block: sum W^2 from the ridge forward's partials exactly as loss_finalize_kernel sums it (out[1] keeps the bits the
+// plain forward wrote); the forward's sum (pred-y)^2 partials are NOT read (masked targets may have put NaN there).  The
+// data term from wstat, clips summed in order in double: out[0] = mean_b m_b (corr = 0) or 1 - mean_b c_b; aux = both means.
+__global__ __launch_bounds__(256) void wloss_finalize_kernel(const float* __restrict__ lpart, int nblk, float lambda,
+                                                             const float* __restrict__ wstat, int B, int corr,
+                                                             float* __restrict__ out, float* __restrict__ aux) {
+  __shared__ double sm[256];
+  double w2 = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += 256) w2 += lpart[2 * i + 1];
+  sm[threadIdx.x] = w2;
+  __syncthreads();
+  for (int s2 = 128; s2 > 0; s2 >>= 1) {
+    if ((int)threadIdx.x < s2) sm[threadIdx.x] += sm[threadIdx.x + s2];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double ms = 0.0, cs = 0.0;
+    for (int b = 0; b < B; ++b) { ms += wstat[(int64_t)b * 8 + 7]; cs += wstat[(int64_t)b * 8 + 5]; }
+    ms /= B; cs /= B;
+    out[0] = (float)(corr ? 1.0 - cs : ms);
+    out[1] = (float)(lambda * sm[0]);
+    out[2] = out[0] + out[1];
+    aux[0] = (float)ms;
+    aux[1] = (float)cs;
+  }
+}
+
+// d pred fp32 [B,V] of the weighted objective, grid (ceil(V/256), B):
+//   mse:  s 2 w (p - y) / (B W_b);   cosine / pearson:  w (a_b (p - mu_p) + b_b (y - mu_y)),
+// a_b, b_b the expressions of head_loss_coef_kernel on the weighted sums; exactly 0 where w = 0 (y is not read there).
+template <int KIND>
+__global__ __launch_bounds__(256) void head_wdpred_kernel(const float* __restrict__ pred, const float* __restrict__ y,
+                                                          const float* __restrict__ tw, const int* __restrict__ group,
+                                                          const float* __restrict__ wstat, float* __restrict__ dpred, int B, int V,
+                                                          float loss_scale) {
+  const int b = blockIdx.y, v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= V) return;
+  const float* r = wstat + (int64_t)b * 8;
+  const float w = tw[(int64_t)(group ? group[b] : 0) * V + v];
+  float dp = 0.f;
+  if (w > 0.f) {
+    const float p = pred[(int64_t)b * V + v], yv = y[(int64_t)b * V + v];
+    if constexpr (KIND == VLB_LOSS_MSE) {
+      const float cm = loss_scale * 2.f / ((float)B * r[6]);
+      dp = cm * w * (p - yv);
+    } else {
+      const float ru = sqrtf(r[2]), nu = fmaxf(ru, 1e-8f), nt = fmaxf(sqrtf(r[3]), 1e-8f);
+      const float sb = loss_scale / (float)B;
+      const float ca = ru > 0.f ? sb * r[5] / (nu * ru) : 0.f, cb = -sb / (nu * nt);
+      dp = w * (ca * (p - r[0]) + cb * (yv - r[1]));
+    }
+  }
+  dpred[(int64_t)b * V + v] = dp;
+}
+
 // d pred of clip b at row v of ITS head, the one spelling for both objectives (the other heads' rows see 0 for this clip):
 // gscale * (pred - y), or the correlation form above.
-template <bool CORR>
+// CORR is a three-way mode naming where d pred comes from: DP_MSE and DP_CORR derive it from (pred, y); DP_BUF reads it
+// from a finished fp32 [B,V] buffer handed in where the other two take `pred` (head_wdpred_kernel wrote it; y and coef are
+// not read).
+enum : int { DP_MSE = 0, DP_CORR = 1, DP_BUF = 2 };
+template <int CORR>
 __device__ __forceinline__ float dpred_own(const float* __restrict__ pred, const float* __restrict__ y, int b, int v, int V,
                                            float gscale, const float* __restrict__ coef) {
-  if constexpr (CORR) return dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]);
+  if constexpr (CORR == DP_BUF) return pred[(int64_t)b * V + v];
+  else if constexpr (CORR == DP_CORR) return dpred_corr(coef, b, pred[(int64_t)b * V + v], y[(int64_t)b * V + v]);
   else return gscale * (pred[(int64_t)b * V + v] - y[(int64_t)b * V + v]);
 }
 
 // d pred^T over all GV = G*V rows as the skinny-wgrad G operand: dpT[g*V + v, b] = d pred[b, v] for b < B (and, GROUPED,
 // group[b] == g), else 0 - the columns b < 16 are all written
-template <bool CORR, bool GROUPED>
+template <int CORR, bool GROUPED>
 __global__ void dpred_t_kernel(const float* __restrict__ pred, const float* __restrict__ y, const int* __restrict__ group,
                                bf16* __restrict__ dpT, int B, int V, int64_t GV, float gscale, const float* __restrict__ coef) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -531,7 +675,7 @@ __global__ void dpred_t_kernel(const float* __restrict__ pred, const float* __re
 // ---------------------------------------------------------------- backward 1: dW, dbias   (z staged in LDS)
 // grid G * bpg as ridge_fwd_kernel, one row of dW per (g, v).  A clip of another head adds nothing to the row: it is skipped,
 // so a head without a clip gets the fp32 product l2coef * W and dbias = 0 exactly.
-template <bool CORR, bool GROUPED>
+template <int CORR, bool GROUPED>
 __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict__ W, const bf16* __restrict__ z,
                                                           const float* __restrict__ pred, const float* __restrict__ y,
                                                           const int* __restrict__ group, float* __restrict__ dW,
@@ -595,7 +739,7 @@ __global__ __launch_bounds__(256) void ridge_bwd_w_kernel(const bf16* __restrict
 // ---------------------------------------------------------------- backward 2: dz partials over V splits (B > 16)
 // grid (ceil(E/512), DZ_SPLIT), block 256 (4 waves share a split's rows); out part[split][B][E].  GROUPED: the split's rows of
 // every head are walked in turn, heads ascending; clip b accumulates only over the rows of head group[b], in the plain order.
-template <bool CORR, bool GROUPED>
+template <int CORR, bool GROUPED>
 __global__ __launch_bounds__(256) void ridge_bwd_z_kernel(const bf16* __restrict__ W, const float* __restrict__ pred,
                                                           const float* __restrict__ y, const int* __restrict__ group,
                                                           float* __restrict__ part, int B, int E, int V, int G, float gscale,
@@ -1113,7 +1257,7 @@ int head_fwd_tail(const float* pooled_raw, const float* sumw, const void* ln1_w,
 }
 
 // dW, dbias and the unmasked dz of the ridge layer over GV = G*V rows, one (objective, GROUPED) instantiation per call
-template <bool CORR, bool GROUPED>
+template <int CORR, bool GROUPED>
 int ridge_bwd_launch(const void* ridge_w, const void* z, const float* pred, const float* y, const float* keep_scale,
                      const int* group, float* d_ridge_w, float* d_ridge_b, float* ws, float* dz_ws, const float* coef, int B, int E,
                      int V, int G, float gscale, float l2coef, void* stream) {
@@ -1150,6 +1294,8 @@ int ridge_bwd_launch(const void* ridge_w, const void* z, const float* pred, cons
 
 // Ridge, dropout, LN2 and LN1-affine gradients (dpooled_ws = d loss / d pooled_raw is left for head_dhidden_kernel): every
 // backward entry runs this (the plain ones with group = nullptr, G = 1), so their parameter gradients are the same bits.
+// loss_kind = LOSS_FROM_DPRED (vlb_head_bwd_wloss): `pred` is the finished d pred [B,V]; y, rowstat and loss_scale are not used.
+constexpr int LOSS_FROM_DPRED = -1;
 int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* keep_scale,
                     const int* group, const float* pooled_raw, const float* sumw, const float* zhat, const float* ln2_rstd,
                     const void* z, const float* pred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b,
@@ -1160,13 +1306,14 @@ int head_bwd_params(const void* ln1_w, const void* ln2_w, const void* ridge_w, c
   const float l2coef = l2_scale * 2.f * l2_lambda;
   // correlation objectives: the per-clip coefficients live behind everything the backward keeps in ws
   float* coef = ws + head_bwd_ws_floats(B, E, G * V);
-  const bool corr = loss_kind != VLB_LOSS_MSE;
+  const bool buf = loss_kind == LOSS_FROM_DPRED, corr = !buf && loss_kind != VLB_LOSS_MSE;
   if (corr) {
     hipLaunchKernelGGL(head_loss_coef_kernel, dim3((B + 63) / 64), dim3(64), 0, st, rowstat, coef, B, loss_scale);
     VLB_LAUNCH_CHECK();
   }
-  const auto ridge_bwd = corr ? (group ? &ridge_bwd_launch<true, true> : &ridge_bwd_launch<true, false>)
-                              : (group ? &ridge_bwd_launch<false, true> : &ridge_bwd_launch<false, false>);
+  const auto ridge_bwd = buf    ? (group ? &ridge_bwd_launch<DP_BUF, true> : &ridge_bwd_launch<DP_BUF, false>)
+                         : corr ? (group ? &ridge_bwd_launch<DP_CORR, true> : &ridge_bwd_launch<DP_CORR, false>)
+                                : (group ? &ridge_bwd_launch<DP_MSE, true> : &ridge_bwd_launch<DP_MSE, false>);
   if (int rc = ridge_bwd(ridge_w, z, pred, y, keep_scale, group, d_ridge_w, d_ridge_b, ws, dz_ws, coef, B, E, V, G, gscale, l2coef,
                          stream))
     return rc;
@@ -1480,6 +1627,79 @@ extern "C" int vlb_head_dhidden(const void* hidden, const float* wmask, const fl
     head_dhidden_launch(hidden, wmask, stats, draw, dx, B, S, E, rows, cu_rows, st);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
+}
+
+// ---------------------------------------------------------------- per-target loss weights: entry points
+namespace {
+template <int KIND>
+int head_wloss_launch(const float* pred, const float* y, const float* tw, const int* group, const float* lpart, int parts,
+                      float* wstat, float* loss_terms, float* loss_aux, int B, int V, float l2_lambda, hipStream_t st) {
+  hipLaunchKernelGGL(head_wrowstat_kernel<KIND>, dim3(B), dim3(1024), 0, st, pred, y, tw, group, wstat, V);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wloss_finalize_kernel, dim3(1), dim3(256), 0, st, lpart, parts, l2_lambda, wstat, B,
+                     KIND != VLB_LOSS_MSE ? 1 : 0, loss_terms, loss_aux);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+template <int KIND>
+int head_wdpred_launch(const float* pred, const float* y, const float* tw, const int* group, const float* wstat, float* dpred,
+                       int B, int V, float loss_scale, hipStream_t st) {
+  hipLaunchKernelGGL(head_wdpred_kernel<KIND>, dim3((V + 255) / 256, B), dim3(256), 0, st, pred, y, tw, group, wstat, dpred, B, V,
+                     loss_scale);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+}  // namespace
+
+extern "C" int vlb_head_wloss_fwd(const float* pred, const float* y, const float* tw, const int* group, const float* ws,
+                                  float* wstat, float* loss_terms, float* loss_aux, int B, int S, int E, int V, int G,
+                                  int loss_kind, float l2_lambda, void* stream) {
+  VLB_REQUIRE(pred && y && tw && ws && wstat && loss_terms && loss_aux, "head_wloss_fwd: null argument");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON,
+              "head_wloss_fwd: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(B > 0 && B <= 65535 && S >= 0 && V > 0 && G >= 1 && E % 8 == 0 && E > 0 && E <= 8192,
+              "head_wloss_fwd: bad shape B=%d S=%d E=%d V=%d G=%d", B, S, E, V, G);
+  VLB_REQUIRE(group ? S == 0 : G == 1, "head_wloss_fwd: group goes with S = 0 (the grouped forward), no group with G = 1 (S=%d G=%d)",
+              S, G);
+  VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_wloss_fwd: G*V = %lld rows, at most 2^27", (long long)G * V);
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_wloss_fwd: pearson needs V >= 2 (V=%d)", V);
+  // where the forward left the ridge partials: behind the pooling slabs (vlb_head_fwd), or at ws (cached / grouped)
+  const float* lpart = ws + (S > 0 ? (int64_t)B * vlb_head_partial_rows(S) * (E + 2) : 0);
+  const int parts = ridge_fwd_parts(B, E, V, G, ridge_fwd_is_mfma(B, E));
+  hipStream_t st = as_stream(stream);
+  if (loss_kind == VLB_LOSS_PEARSON)
+    return head_wloss_launch<VLB_LOSS_PEARSON>(pred, y, tw, group, lpart, parts, wstat, loss_terms, loss_aux, B, V, l2_lambda, st);
+  if (loss_kind == VLB_LOSS_COSINE)
+    return head_wloss_launch<VLB_LOSS_COSINE>(pred, y, tw, group, lpart, parts, wstat, loss_terms, loss_aux, B, V, l2_lambda, st);
+  return head_wloss_launch<VLB_LOSS_MSE>(pred, y, tw, group, lpart, parts, wstat, loss_terms, loss_aux, B, V, l2_lambda, st);
+}
+
+extern "C" int vlb_head_bwd_wloss(const void* ln1_w, const void* ln2_w, const void* ridge_w, const float* y, const float* tw,
+                                  const float* keep_scale, const int* group, const float* pooled_raw, const float* sumw,
+                                  const float* zhat, const float* ln2_rstd, const void* z, const float* pred, const float* wstat,
+                                  float* dpred, float* d_ridge_w, float* d_ridge_b, float* d_ln2_w, float* d_ln2_b, float* d_ln1_w,
+                                  float* d_ln1_b, float* ws, float* dz_ws, float* dpooled_ws, int B, int E, int V, int G,
+                                  float l2_lambda, float loss_scale, float l2_scale, int loss_kind, void* stream) {
+  VLB_REQUIRE(ln1_w && ln2_w && ridge_w && y && tw && pooled_raw && sumw && zhat && ln2_rstd && z && pred && wstat && dpred &&
+                  d_ridge_w && d_ridge_b && d_ln2_w && d_ln2_b && d_ln1_w && d_ln1_b && ws && dz_ws && dpooled_ws,
+              "head_bwd_wloss: null argument");
+  VLB_REQUIRE(loss_kind == VLB_LOSS_MSE || loss_kind == VLB_LOSS_COSINE || loss_kind == VLB_LOSS_PEARSON,
+              "head_bwd_wloss: unknown loss_kind %d", loss_kind);
+  VLB_REQUIRE(B > 0 && B <= 65535 && V > 0 && G >= 1 && E % 8 == 0 && E > 0 && E <= 8192,
+              "head_bwd_wloss: bad shape B=%d E=%d V=%d G=%d", B, E, V, G);
+  VLB_REQUIRE(group || G == 1, "head_bwd_wloss: G = %d heads need group", G);
+  VLB_REQUIRE((int64_t)G * V <= GROUPED_MAX_ROWS, "head_bwd_wloss: G*V = %lld rows, at most 2^27", (long long)G * V);
+  VLB_REQUIRE(loss_kind != VLB_LOSS_PEARSON || V >= 2, "head_bwd_wloss: pearson needs V >= 2 (V=%d)", V);
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (loss_kind == VLB_LOSS_PEARSON) rc = head_wdpred_launch<VLB_LOSS_PEARSON>(pred, y, tw, group, wstat, dpred, B, V, loss_scale, st);
+  else if (loss_kind == VLB_LOSS_COSINE) rc = head_wdpred_launch<VLB_LOSS_COSINE>(pred, y, tw, group, wstat, dpred, B, V, loss_scale, st);
+  else rc = head_wdpred_launch<VLB_LOSS_MSE>(pred, y, tw, group, wstat, dpred, B, V, loss_scale, st);
+  if (rc != VLB_OK) return rc;
+  // everything behind d pred: the existing launches, reading the buffer where they re-derived it
+  return head_bwd_params(ln1_w, ln2_w, ridge_w, y, keep_scale, group, pooled_raw, sumw, zhat, ln2_rstd, z, dpred, d_ridge_w, d_ridge_b,
+                         d_ln2_w, d_ln2_b, d_ln1_w, d_ln1_b, ws, dz_ws, dpooled_ws, nullptr, B, E, V, group ? G : 1, l2_lambda,
+                         loss_scale, l2_scale, LOSS_FROM_DPRED, stream);
 }
 
 // ---------------------------------------------------------------- the exported layers on their own

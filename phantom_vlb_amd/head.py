@@ -10,6 +10,8 @@ head runs on the mix; see ``begin`` / ``tap`` / ``forward_tapped`` / ``backward_
 Opt-in, ``subjects``: one ridge head per subject on the shared trunk (``ridge_layer.linear.weight`` [G,V,E]); each clip is
 regressed by its own subject's head, the penalty covers all heads (vlb_head_fwd_grouped / vlb_head_bwd_grouped in place of
 the tail; ``forward`` / ``forward_cached`` / ``forward_tapped`` take ``subject``); see DESIGN §5.3.4.
+Opt-in, ``set_target_weights``: per-target loss weights / missing-target masks, one row per ridge head; every route then ends in
+vlb_head_wloss_fwd / vlb_head_bwd_wloss (targets with weight 0 are never read arithmetically and get no gradient); DESIGN §5.3.8.
 Trainable parameters keep an fp32 master (what AdamW updates) and the bf16 copy the kernels read -
 the reference stores them in bf16 (``dtype=self.config.dtype``), i.e. the kernels see the same values.
 """
@@ -146,6 +148,65 @@ class BrainHead:
         self.grads = {n: torch.zeros_like(t) for n, t in self.master.items()}
         self._cap = None
         self.l2_lambda_rows = None        # set_l2_lambda_rows: one penalty per row of the ridge weight
+        self.tw = None                    # set_target_weights: fp32 [max(1,G), V] loss weights / masks
+
+    # ------------------------------------------------------------------ per-target loss weights and masks (set_target_weights)
+    def set_target_weights(self, tw):
+        """``tw`` fp32 on the device, [V] (every head alike) or [H,V] with H = max(1,G) (one row per ridge head): every value
+        finite and >= 0, every row with at least one positive value (two for ``pearson``).  The data term becomes the
+        weighted one of DESIGN §5.3.8 (a 0/1 row is a mask: the objective on the kept targets alone; targets with weight 0 may
+        hold NaN); every route then ends in vlb_head_wloss_fwd / vlb_head_bwd_wloss.  None: back to the unweighted path."""
+        if tw is None:
+            self.tw = None
+            return
+        H, V = max(1, self.G), self.V
+        if not isinstance(tw, torch.Tensor) or tw.dtype != torch.float32 or tw.device.type != torch.device(self.dev).type or \
+                tuple(tw.shape) not in ((V,), (H, V)):
+            raise ValueError(f"head: set_target_weights needs an fp32 tensor [{V}] or [{H},{V}] on {self.dev}, got "
+                             f"{getattr(tw, 'dtype', type(tw))} {tuple(getattr(tw, 'shape', ()))}")
+        tw = tw.detach().reshape(-1, V).expand(H, V).contiguous().clone()
+        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        bad = torch.nonzero(~(torch.isfinite(tw) & (tw >= 0)))
+        if bad.numel():
+            g, v = (int(i) for i in bad[0])
+            raise ValueError(f"head: set_target_weights: {name(g)}, target {v}: weight {float(tw[g, v])} - every weight must be "
+                             "finite and >= 0")
+        need = 2 if self.loss == "pearson" else 1
+        npos = (tw > 0).sum(1).tolist()
+        for g, n in enumerate(npos):
+            if n < need:
+                raise ValueError(f"head: set_target_weights: {name(g)} has {n} target(s) with a positive weight; loss="
+                                 f"{self.loss!r} needs at least {need}")
+        self.tw = tw
+        self._cap = None                  # the next call allocates wstat / dpred with the other buffers
+
+    def _wloss_fwd(self, y, B, S, group):
+        """loss_terms, loss_aux, wstat <- the weighted objective, on the pred and ridge partials the forward just left (S:
+        where they sit in ws, as for _loss_fwd; group: the grouped forward's, its workspace is gws)"""
+        ws = self.ws if group is None else self.gws
+        check(lib.vlb_head_wloss_fwd(self.pred.data_ptr(), y.data_ptr(), self.tw.data_ptr(),
+                                     None if group is None else group.data_ptr(), ws.data_ptr(), self.wstat.data_ptr(),
+                                     self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, S, self.E, self.V, max(1, self.G),
+                                     self.loss_kind, self._lam(), _stream()), "vlb_head_wloss_fwd")
+
+    def _bwd_wloss(self, y, keep_scale, loss_scale, l2_scale):
+        """parameter gradients and dpooled of the weighted objective (one head, or the stacked heads of the last forward)"""
+        B = y.shape[0]
+        c, gr = self.compute, self.grads
+        group = self._saved_group if self.G else None
+        ws = self.gws if self.G else self.ws
+        check(lib.vlb_head_bwd_wloss(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                                     c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(), self.tw.data_ptr(),
+                                     None if keep_scale is None else keep_scale.data_ptr(),
+                                     None if group is None else group.data_ptr(), self.pooled_raw.data_ptr(),
+                                     self.sumw.data_ptr(), self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(),
+                                     self.pred.data_ptr(), self.wstat.data_ptr(), self.dpred.data_ptr(),
+                                     gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
+                                     gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
+                                     gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(), ws.data_ptr(),
+                                     self.dz.data_ptr(), self.dpooled.data_ptr(), B, self.E, self.V, max(1, self.G), self._lam(),
+                                     float(loss_scale), float(l2_scale), self.loss_kind, _stream()), "vlb_head_bwd_wloss")
+        self._l2_rows_bwd(l2_scale)
 
     # ------------------------------------------------------------------ one l2_lambda per row (set_l2_lambda_rows)
     def set_l2_lambda_rows(self, rows):
@@ -203,6 +264,9 @@ class BrainHead:
             self.loss_aux = torch.zeros(2, dtype=f32, device=d)
             self.dz = torch.empty(B, E, dtype=f32, device=d)
             self.dpooled = torch.empty(B, E, dtype=f32, device=d)
+            if self.tw is not None:       # weighted objective only: per clip (.., c_b, W_b, m_b); d loss / d pred
+                self.wstat = torch.zeros(B, 8, dtype=f32, device=d)
+                self.dpred = torch.empty(B, V, dtype=f32, device=d)
             if self.G:
                 self.gws = torch.empty(max(1, lib.vlb_head_grouped_ws_floats(B, E, V, self.G)), dtype=f32, device=d)
                 self.pool_src = torch.empty(B, E, dtype=f32, device=d)       # vlb_head_pool's output, the grouped tail's "cache"
@@ -242,8 +306,11 @@ class BrainHead:
                                        self.gws.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
                                        self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
                                        self.rowstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, self.E,
-                                       self.V, self.G, n_rows, self.eps, self._lam(), self.loss_kind, _stream()),
+                                       self.V, self.G, n_rows, self.eps, self._lam(),
+                                       self.loss_kind if self.tw is None else LOSS_KINDS["mse"], _stream()),
               "vlb_head_fwd_grouped")
+        if self.tw is not None:
+            self._wloss_fwd(y, B, 0, group)
         self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
@@ -307,7 +374,9 @@ class BrainHead:
                                self.loss_terms.data_ptr(), B, S, self.E, self.V, self.eps, self._lam(),
                                None if cu is None else cu.data_ptr(), _stream()),
               "vlb_head_fwd")
-        if self.loss_kind:
+        if self.tw is not None:
+            self._wloss_fwd(y, B, S, None)
+        elif self.loss_kind:
             self._loss_fwd(y, B, S)
         self._l2_rows_fwd()
         return self.pred, self.loss_terms
@@ -324,8 +393,11 @@ class BrainHead:
         B, S = wmask.shape
         c, gr = self.compute, self.grads
         dh = torch.empty(rows, self.E, dtype=BF16, device=self.dev) if need_dhidden else None
-        if self.G:
-            self._bwd_grouped(loss_scale, l2_scale)
+        if self.G or self.tw is not None:
+            if self.tw is not None:
+                self._bwd_wloss(y, keep_scale, loss_scale, l2_scale)
+            else:
+                self._bwd_grouped(loss_scale, l2_scale)
             if need_dhidden:
                 check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), self.stats.data_ptr(), self.dpooled.data_ptr(),
                                            dh.data_ptr(), B, S, self.E, None if cu is None else cu.data_ptr(), rows, 0,
@@ -382,7 +454,9 @@ class BrainHead:
                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
                                       self.loss_terms.data_ptr(), B, self.E, self.V, cache.n, self.eps, self._lam(),
                                       _stream()), "vlb_head_fwd_cached")
-        if self.loss_kind:
+        if self.tw is not None:
+            self._wloss_fwd(y, B, 0, None)
+        elif self.loss_kind:
             self._loss_fwd(y, B, 0)
         self._l2_rows_fwd()
         return self.pred, self.loss_terms
@@ -447,7 +521,9 @@ class BrainHead:
                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
                                       self.loss_terms.data_ptr(), B, self.E, self.V, B, self.eps, self._lam(),
                                       _stream()), "vlb_head_fwd_cached")
-        if self.loss_kind:
+        if self.tw is not None:
+            self._wloss_fwd(y, B, 0, None)
+        elif self.loss_kind:
             self._loss_fwd(y, B, 0)
         self._l2_rows_fwd()
         return self.pred, self.loss_terms
@@ -479,6 +555,8 @@ class BrainHead:
 
     def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
         """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""
+        if self.tw is not None:
+            return self._bwd_wloss(*self._saved_cached, loss_scale, l2_scale)
         if self.G:
             return self._bwd_grouped(loss_scale, l2_scale)
         y, keep_scale = self._saved_cached
@@ -509,6 +587,9 @@ class BrainHead:
         (its rank among the clips that head has received so far) goes to fold ``(m // block) % K``."""
         if self.loss != "mse":
             raise ValueError(f"head: the closed-form ridge fit minimises the mse objective; this head has loss={self.loss!r}")
+        if self.tw is not None:
+            raise ValueError("head: the closed-form ridge fit does not take target weights (a mask would need NaN-tolerant Gram "
+                             "columns, general weights one factorisation per distinct weight): set_target_weights(None) first")
         H, E, V, d, f64 = max(1, self.G), self.E, self.V, self.dev, torch.float64
         if folds is not None:
             K, blk = int(folds), 1 if block is None else int(block)

@@ -202,6 +202,11 @@ class VLBLitModuleConfig:
     ema_decay: float | None = None
     ema_warmup: bool = True             # the t-th update's decay is min(ema_decay, (1 + t) / (10 + t)); False: ema_decay from the first
     ema_eval: bool = True               # validation and the merged export read the averaged weights (VLBLitModule.averaged_weights)
+    # path of a .npy file of per-target loss weights: [num_target], or [G, num_target] with ``subjects`` (one row
+    # per subject, in that order); with ``subjects`` the path may hold the literal ``{subject}`` instead and name one
+    # [num_target] file per subject.  Finite, >= 0; a 0/1 file is a mask (targets with weight 0 are neither trained on nor
+    # scored, and may be NaN in the data).  None: every target counts alike, as the reference
+    target_weights: str | None = None
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -261,6 +266,17 @@ class VLBLitModuleConfig:
                 raise ValueError(FULLFT_EMA_MESSAGE)
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
+        if self.target_weights is not None:
+            tw = self.target_weights
+            if not isinstance(tw, str) or not tw.endswith(".npy"):
+                raise ValueError(f"target_weights={tw!r}: the path of a .npy file is needed (leave it unset for no weights)")
+            if "{subject}" in tw and self.subjects is None:
+                raise ValueError(f"target_weights={tw!r} holds {{subject}} but `subjects` is unset: one subject takes one file "
+                                 "of [num_target] weights")
+            if self.ridge_fit is not None:
+                raise ValueError("target_weights with ridge_fit='closed_form' is not supported: the closed-form fit and its "
+                                 "cross-validation take every target alike (a mask would need NaN-tolerant Gram columns, "
+                                 "general weights one factorisation per distinct weight); unset one of the two")
         if self.readout_layers is not None:
             if not self.freeze_backbone and not self.use_lora:
                 raise ValueError("readout_layers with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported: "
@@ -268,6 +284,31 @@ class VLBLitModuleConfig:
                                  "freeze_backbone=True or use_lora=True")
             # the geometry name fixes L here already; configure_model checks again against the geometry it builds
             self.readout_layers = check_readout_layers(self.readout_layers, resolve_geometry(self).layers)
+
+
+def load_target_weights(path: str, num_target: int, subjects=None) -> torch.Tensor:
+    """``config.target_weights`` -> fp32 CPU tensor [num_target], or [G, num_target] with ``subjects``.  ``{subject}`` in the path
+    (subjects only) names one [num_target] file per subject.  Shape, finiteness and sign are checked here with the file named;
+    the head checks once more what a row must hold for its objective."""
+    import numpy as np
+
+    def one(p, shapes):
+        if not os.path.isfile(p):
+            raise ValueError(f"target_weights: {p!r} does not exist")
+        a = np.load(p, allow_pickle=False)
+        if a.dtype.kind not in "fiub" or tuple(a.shape) not in shapes:
+            raise ValueError(f"target_weights: {p!r} holds {a.dtype} {tuple(a.shape)}, expected numbers of shape "
+                             f"{' or '.join(str(list(s)) for s in shapes)}")
+        a = a.astype(np.float32)
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"target_weights: {p!r}: every weight must be finite and >= 0")
+        return torch.from_numpy(a)
+    V = int(num_target)
+    if subjects is None:
+        return one(path, ((V,),))
+    if "{subject}" in path:
+        return torch.stack([one(path.replace("{subject}", s), ((V,),)) for s in subjects])
+    return one(path, ((V,), (len(subjects), V)))
 
 
 def check_batch_subjects(batch, subjects, B: int | None = None):
@@ -391,6 +432,14 @@ class VLBLitModule(_Base):
             self.head.l2_lambda = float(self.__dict__["_ridge_cv_lambda"])
         if "_ridge_lambda_rows" in self.__dict__:    # likewise the per-target penalties (ridge_lambda_per_target, §5.3.7)
             self.head.set_l2_lambda_rows(self.__dict__["_ridge_lambda_rows"].to(dev, torch.float32))
+        # per-target loss weights (§5.3.8): the configured file, and / or what a checkpoint loaded before the head existed held
+        tw = self.__dict__.get("_target_weights")
+        if getattr(cfg, "target_weights", None) is not None:
+            filed = load_target_weights(cfg.target_weights, cfg.num_target, getattr(cfg, "subjects", None))
+            self._check_same_weights(filed, tw, cfg.target_weights)
+            tw = filed
+        if tw is not None:
+            self.set_target_weights(tw)
         # reference attribute names
         self.hrf_layer = self.head
         self.ridge_layer = self.head
@@ -406,6 +455,39 @@ class VLBLitModule(_Base):
             lora_sd = None if head_state is None and lora_state is None else {**(head_state or {}), **(lora_state or {})}
             self.lora = LoraState(g, weights, cfg.lora_r, cfg.lora_alpha, cfg.lora_dropout or 0.0, dev, seed=cfg.init_seed,
                                   sd=lora_sd, target_modules=find_all_linear_names(self.backbone))
+
+    # ------------------------------------------------------------------ per-target loss weights and masks
+    def set_target_weights(self, tw) -> None:
+        """``tw``: [num_target], or [G, num_target] with ``subjects`` (a tensor on any device, or anything torch.as_tensor takes);
+        None: no weights.  Goes to ``BrainHead.set_target_weights`` (which checks it) and into checkpoints."""
+        if tw is not None and getattr(self.config, "ridge_fit", None) is not None:
+            raise ValueError("set_target_weights with ridge_fit='closed_form' is not supported: the closed-form fit takes every "
+                             "target alike")
+        t = None if tw is None else torch.as_tensor(tw).detach().to("cpu", torch.float32).clone()
+        head = getattr(self, "head", None)
+        if head is not None:
+            head.set_target_weights(None if t is None else t.to(head.dev))
+            t = None if t is None else head.tw.detach().cpu().clone()       # [max(1,G), num_target], as the head keeps it
+        if t is None:
+            self.__dict__.pop("_target_weights", None)
+        else:
+            self._target_weights = t
+
+    def target_weight_mask(self):
+        """host bool [max(1,G), num_target]: True where a target's weight is positive; None without weights"""
+        t = self.__dict__.get("_target_weights")
+        return None if t is None else (t.reshape(-1, t.shape[-1]) > 0)
+
+    def _check_same_weights(self, filed, other, path) -> None:
+        """a checkpoint's weights against the configured file's: they must be the same numbers"""
+        if filed is None or other is None:
+            return
+        V = filed.shape[-1]
+        a, b = filed.reshape(-1, V), other.reshape(-1, other.shape[-1])
+        n = max(a.shape[0], b.shape[0])
+        if b.shape[-1] != V or a.shape[0] not in (1, n) or b.shape[0] not in (1, n) or not torch.equal(a.expand(n, V), b.expand(n, V)):
+            raise ValueError(f"the checkpoint's vlb_target_weights differ from target_weights={path!r}: resume with the file "
+                             "the run was trained with, or unset target_weights to take the checkpoint's")
 
     def _named_masters(self):
         """(name, fp32 master tensor) of everything AdamW updates: head always; LoRA A/B when use_lora
@@ -939,8 +1021,9 @@ class VLBLitModule(_Base):
             self._micro, self._window_closed = j + 1, last
         self._attach_gradients()
         self.log("train/brain_loss", terms[2])           # the objective being trained (config.loss) + l2
-        if self.head.loss_kind:
-            self.log("train/brain_mse", self.head.loss_aux[0])       # the plain MSE, which the ridge forward sums anyway
+        if self.head.loss_kind or self.head.tw is not None:
+            # the plain MSE, which the ridge forward sums anyway; with target weights the weighted one, mean_b m_b
+            self.log("train/brain_mse", self.head.loss_aux[0])
         if _LP is None:
             return terms[2]          # no Lightning in this process: the plain loss value, as the built-in runner reads it
         # a scalar Lightning's automatic optimisation can call .backward() on (see _ExplicitLoss)
@@ -955,7 +1038,7 @@ class VLBLitModule(_Base):
         self.train(was)
         loss = terms[2].clone()
         self.log("val/brain_loss", loss)
-        if self.head.loss_kind:
+        if self.head.loss_kind or self.head.tw is not None:
             self.log("val/brain_mse", self.head.loss_aux[0].clone())
         out = {"loss": loss, "brain_preds": pred.clone(), "brain_vals": y}
         if "subject" in batch:            # per-subject validation correlations (LogValAccuracyCallback)
@@ -1004,6 +1087,8 @@ class VLBLitModule(_Base):
             checkpoint["vlb_ridge_l2_lambda"] = float(self.__dict__["_ridge_cv_lambda"])
         if "_ridge_lambda_rows" in self.__dict__:    # ridge_lambda_per_target: the penalty of every row (§5.3.7)
             checkpoint["vlb_ridge_l2_lambda_rows"] = self.__dict__["_ridge_lambda_rows"].clone()
+        if "_target_weights" in self.__dict__:       # per-target loss weights / masks (§5.3.8), [max(1,G), num_target]
+            checkpoint["vlb_target_weights"] = self.__dict__["_target_weights"].clone()
 
     def on_load_checkpoint(self, checkpoint: dict) -> None:
         if "vlb_rng" in checkpoint:
@@ -1016,6 +1101,14 @@ class VLBLitModule(_Base):
             self._ridge_lambda_rows = checkpoint["vlb_ridge_l2_lambda_rows"].detach().to("cpu", torch.float32).clone()
             if getattr(self, "head", None) is not None:
                 self.head.set_l2_lambda_rows(self._ridge_lambda_rows.to(self.head.dev))
+        if "vlb_target_weights" in checkpoint:
+            tw = checkpoint["vlb_target_weights"].detach().to("cpu", torch.float32).clone()
+            path = getattr(self.config, "target_weights", None)
+            if path is not None:             # a configured file must hold the numbers the run was trained with
+                have = self.__dict__.get("_target_weights")
+                self._check_same_weights(have if have is not None else load_target_weights(
+                    path, self.config.num_target, getattr(self.config, "subjects", None)), tw, path)
+            self.set_target_weights(tw)
 
     def state_dict(self, *args, **kwargs):
         """Trainables only, upstream / peft names (what a Lightning ModelCheckpoint stores for this module; the reference saves

@@ -100,7 +100,11 @@ class LogValAccuracyCallback(_Callback):
     Multi-subject runs (``outputs["subject"]``: the index of every clip into ``pl_module.config.subjects``): the five sums are
     kept per subject, [G,5,V] with clip counts [G]; logged are ``val_corr_avg/<subject>`` and ``val_corr_ROI_xxxxxx/<subject>``
     for every subject that had validation clips, and ``val_corr_avg`` = the mean of the former over those subjects
-    (`correlations` is then [G,V], NaN rows for subjects without clips).  Without the key nothing changes."""
+    (`correlations` is then [G,V], NaN rows for subjects without clips).  Without the key nothing changes.
+
+    Target weights (``pl_module.set_target_weights``): ``val_corr_avg[/<subject>]`` is the mean over the targets
+    with a positive weight (the subject's own row), ``val_corr_ROI_*`` is logged for those targets only and `correlations` is
+    NaN elsewhere.  Without weights nothing changes."""
 
     def on_validation_epoch_start(self, trainer, pl_module):
         self.n = 0
@@ -153,21 +157,33 @@ class LogValAccuracyCallback(_Callback):
         var = (spp - sp * sp / n) * (syy - sy * sy / n)
         return (cov / var.clamp_min(1e-30).sqrt()).float()
 
+    @staticmethod
+    def _kept_targets(pl_module):
+        """host bool [H,V], True where the module's target weights are positive (``set_target_weights``); None without weights"""
+        fn = getattr(pl_module, "target_weight_mask", None)
+        return None if fn is None else fn()
+
     def _per_subject_epoch_end(self, pl_module):
         names = list(pl_module.config.subjects)
         counts = self.count.cpu().tolist()                   # one small copy: which subjects had clips
         V = self.s.shape[-1]
         self.correlations = torch.full((len(names), V), float("nan"), dtype=torch.float32, device=self.s.device)
         limit = getattr(self, "max_roi_logs", None)
+        keep = self._kept_targets(pl_module)
+        kept = None if keep is None else keep.tolist()
         avgs = []
         for g, name in enumerate(names):
             if counts[g] <= 0:
                 continue
-            self.correlations[g] = self._corr(self.s[g], float(counts[g]))
-            host = self.correlations[g].cpu().tolist()
+            corr = self._corr(self.s[g], float(counts[g]))
+            if keep is not None:                             # target weights: NaN where this subject's weight is 0
+                corr = torch.where(keep[g].to(corr.device), corr, torch.full_like(corr, float("nan")))
+            self.correlations[g] = corr
+            host = corr.cpu().tolist()
             for i in range(V if limit is None else min(V, limit)):
-                pl_module.log(f"val_corr_ROI_{i:0{6}}/{name}", host[i])
-            avgs.append(self.correlations[g].mean())
+                if keep is None or kept[g][i]:
+                    pl_module.log(f"val_corr_ROI_{i:0{6}}/{name}", host[i])
+            avgs.append(corr.mean() if keep is None else corr[keep[g].to(corr.device)].mean())
             pl_module.log(f"val_corr_avg/{name}", avgs[-1])
         if avgs:
             pl_module.log("val_corr_avg", torch.stack(avgs).mean())
@@ -182,10 +198,16 @@ class LogValAccuracyCallback(_Callback):
         cov = spy - sp * sy / n
         var = (spp - sp * sp / n) * (syy - sy * sy / n)
         self.correlations = (cov / var.clamp_min(1e-30).sqrt()).float()
+        keep = self._kept_targets(pl_module)
+        if keep is not None:                                 # target weights: NaN where the weight is 0, the mean over the rest
+            keep = keep[0].to(self.correlations.device)
+            self.correlations = torch.where(keep, self.correlations, torch.full_like(self.correlations, float("nan")))
         # one scalar per target, like the reference (:105-110) - from ONE device->host copy instead of num_target syncs;
         # max_roi_logs caps the count for whole-cortex heads (65,536 log() calls per validation epoch otherwise)
         host = self.correlations.cpu().tolist()
+        kept = None if keep is None else keep.cpu().tolist()
         limit = getattr(self, "max_roi_logs", None)
         for i in range(pl_module.config.num_target if limit is None else min(pl_module.config.num_target, limit)):
-            pl_module.log(f"val_corr_ROI_{i:0{6}}", host[i])
-        pl_module.log("val_corr_avg", self.correlations.mean())
+            if kept is None or kept[i]:
+                pl_module.log(f"val_corr_ROI_{i:0{6}}", host[i])
+        pl_module.log("val_corr_avg", self.correlations.mean() if keep is None else self.correlations[keep].mean())
