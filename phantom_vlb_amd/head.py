@@ -4,14 +4,16 @@
 Mirrors the reference's head modules (``layer_norm1``, ``hrf_layer``, ``layer_norm2``, ``dropout``,
 ``ridge_layer.linear``; src/litmodule/videollama2_vlb_litmodule.py:210-226,245-254 and
 src/utils.py:40-73) but runs as the fused vlb_head_fwd / vlb_head_bwd kernels.
-Opt-in, ``readout_layers``: the head reads K chosen decoder layers instead of the last one - each is pooled on its own
-(vlb_head_pool), the pooled vectors are mixed by softmax(``layer_mix.weight``) (vlb_head_mix_fwd / _bwd) and the rest of the
-head runs on the mix; see ``begin`` / ``tap`` / ``forward_tapped`` / ``backward_tapped`` / ``dhidden`` and DESIGN §5.3.3.
-Opt-in, ``subjects``: one ridge head per subject on the shared trunk (``ridge_layer.linear.weight`` [G,V,E]); each clip is
-regressed by its own subject's head, the penalty covers all heads (vlb_head_fwd_grouped / vlb_head_bwd_grouped in place of
-the tail; ``forward`` / ``forward_cached`` / ``forward_tapped`` take ``subject``); see DESIGN §5.3.4.
-Opt-in, ``set_target_weights``: per-target loss weights / missing-target masks, one row per ridge head; every route then ends in
-vlb_head_wloss_fwd / vlb_head_bwd_wloss (targets with weight 0 are never read arithmetically and get no gradient); DESIGN §5.3.8.
+Every route is a source of (pooled_raw, sumw), then one tail, then one finisher:
+* sources: ``forward`` pools one hidden tensor (fused into vlb_head_fwd for a single head, vlb_head_pool otherwise);
+  ``forward_cached`` reads rows of a feature cache; with ``readout_layers`` (§5.3.3) K decoder layers are pooled one by one
+  (``begin`` / ``tap``) or gathered from K cache slabs and mixed by softmax(``layer_mix.weight``) (``forward_tapped``);
+* ``_tail``: LN2, dropout, the ridge layer and the MSE on that source - vlb_head_fwd_cached, or with ``subjects`` (one ridge
+  head per subject on the shared trunk, ``ridge_layer.linear.weight`` [G,V,E], ``subject`` on every forward; §5.3.4)
+  vlb_head_fwd_grouped;
+* ``_finish``: the objective other than the plain MSE - the correlation objectives of a single head, the weighted one of
+  ``set_target_weights`` (§5.3.8) - and the penalty per row of ``set_l2_lambda_rows`` (§5.3.7).
+``_backward_tail`` mirrors tail and finisher; ``backward`` adds d loss / d hidden, ``backward_tapped`` the mix's gradient.
 Trainable parameters keep an fp32 master (what AdamW updates) and the bf16 copy the kernels read -
 the reference stores them in bf16 (``dtype=self.config.dtype``), i.e. the kernels see the same values.
 """
@@ -22,7 +24,7 @@ import math
 import torch
 
 from ._lib import check, lib
-from .ops import _stream
+from .ops import _p, _stream        # _p: an optional tensor as the ABI takes it, NULL for None
 
 BF16 = torch.bfloat16
 LOSS_KINDS = {"mse": 0, "cosine": 1, "pearson": 2}      # VLB_LOSS_* of include/vlb.h
@@ -155,7 +157,7 @@ class BrainHead:
         """``tw`` fp32 on the device, [V] (every head alike) or [H,V] with H = max(1,G) (one row per ridge head): every value
         finite and >= 0, every row with at least one positive value (two for ``pearson``).  The data term becomes the
         weighted one of DESIGN §5.3.8 (a 0/1 row is a mask: the objective on the kept targets alone; targets with weight 0 may
-        hold NaN); every route then ends in vlb_head_wloss_fwd / vlb_head_bwd_wloss.  None: back to the unweighted path."""
+        hold NaN): what ``_finish`` / ``_backward_tail`` then run.  None: back to the unweighted path."""
         if tw is None:
             self.tw = None
             return
@@ -165,7 +167,7 @@ class BrainHead:
             raise ValueError(f"head: set_target_weights needs an fp32 tensor [{V}] or [{H},{V}] on {self.dev}, got "
                              f"{getattr(tw, 'dtype', type(tw))} {tuple(getattr(tw, 'shape', ()))}")
         tw = tw.detach().reshape(-1, V).expand(H, V).contiguous().clone()
-        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        name = self._head_name
         bad = torch.nonzero(~(torch.isfinite(tw) & (tw >= 0)))
         if bad.numel():
             g, v = (int(i) for i in bad[0])
@@ -180,33 +182,36 @@ class BrainHead:
         self.tw = tw
         self._cap = None                  # the next call allocates wstat / dpred with the other buffers
 
-    def _wloss_fwd(self, y, B, S, group):
-        """loss_terms, loss_aux, wstat <- the weighted objective, on the pred and ridge partials the forward just left (S:
-        where they sit in ws, as for _loss_fwd; group: the grouped forward's, its workspace is gws)"""
-        ws = self.ws if group is None else self.gws
-        check(lib.vlb_head_wloss_fwd(self.pred.data_ptr(), y.data_ptr(), self.tw.data_ptr(),
-                                     None if group is None else group.data_ptr(), ws.data_ptr(), self.wstat.data_ptr(),
-                                     self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, S, self.E, self.V, max(1, self.G),
-                                     self.loss_kind, self._lam(), _stream()), "vlb_head_wloss_fwd")
+    # ------------------------------------------------------------------ the ABI's pointer blocks, each spelled once
+    def _fwd_params(self):
+        """the six parameters every forward entry reads: LN1 (w, b), LN2 (w, b), ridge (w, b).  (Literal tuples here and
+        below: these run on every call of a latency-bound head.)"""
+        c = self.compute
+        return (c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                c["layer_norm2.bias"].data_ptr(), c["ridge_layer.linear.weight"].data_ptr(),
+                c["ridge_layer.linear.bias"].data_ptr())
 
-    def _bwd_wloss(self, y, keep_scale, loss_scale, l2_scale):
-        """parameter gradients and dpooled of the weighted objective (one head, or the stacked heads of the last forward)"""
-        B = y.shape[0]
-        c, gr = self.compute, self.grads
-        group = self._saved_group if self.G else None
-        ws = self.gws if self.G else self.ws
-        check(lib.vlb_head_bwd_wloss(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
-                                     c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(), self.tw.data_ptr(),
-                                     None if keep_scale is None else keep_scale.data_ptr(),
-                                     None if group is None else group.data_ptr(), self.pooled_raw.data_ptr(),
-                                     self.sumw.data_ptr(), self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(),
-                                     self.pred.data_ptr(), self.wstat.data_ptr(), self.dpred.data_ptr(),
-                                     gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
-                                     gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
-                                     gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(), ws.data_ptr(),
-                                     self.dz.data_ptr(), self.dpooled.data_ptr(), B, self.E, self.V, max(1, self.G), self._lam(),
-                                     float(loss_scale), float(l2_scale), self.loss_kind, _stream()), "vlb_head_bwd_wloss")
-        self._l2_rows_bwd(l2_scale)
+    def _bwd_params(self):
+        """the three parameters every backward entry reads"""
+        c = self.compute
+        return (c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
+                c["ridge_layer.linear.weight"].data_ptr())
+
+    def _acts(self):
+        """the activations the forward saves and the backward reads"""
+        return (self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(), self.ln2_rstd.data_ptr(),
+                self.z.data_ptr(), self.pred.data_ptr())
+
+    def _grad_ptrs(self):
+        """the six parameter gradients: ridge (w, b), LN2 (w, b), LN1 (w, b)"""
+        gr = self.grads
+        return (gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
+                gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
+                gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr())
+
+    def _head_name(self, g):
+        """how a message names ridge head g"""
+        return f"head {g} ({self.subjects[g]!r})" if self.G else "the head"
 
     # ------------------------------------------------------------------ one l2_lambda per row (set_l2_lambda_rows)
     def set_l2_lambda_rows(self, rows):
@@ -264,6 +269,7 @@ class BrainHead:
             self.loss_aux = torch.zeros(2, dtype=f32, device=d)
             self.dz = torch.empty(B, E, dtype=f32, device=d)
             self.dpooled = torch.empty(B, E, dtype=f32, device=d)
+            self.identity_rows = torch.arange(B, dtype=torch.int32, device=d)      # "cache rows" of a pooled or mixed source
             if self.tw is not None:       # weighted objective only: per clip (.., c_b, W_b, m_b); d loss / d pred
                 self.wstat = torch.zeros(B, 8, dtype=f32, device=d)
                 self.dpred = torch.empty(B, V, dtype=f32, device=d)
@@ -271,10 +277,9 @@ class BrainHead:
                 self.gws = torch.empty(max(1, lib.vlb_head_grouped_ws_floats(B, E, V, self.G)), dtype=f32, device=d)
                 self.pool_src = torch.empty(B, E, dtype=f32, device=d)       # vlb_head_pool's output, the grouped tail's "cache"
                 self.pool_sumw = torch.empty(B, dtype=f32, device=d)
-                self.rows_id = torch.arange(B, dtype=torch.int32, device=d)
             self._cap = key
 
-    # ------------------------------------------------------------------ per-subject heads (subjects=[...]): the grouped tail
+    # ------------------------------------------------------------------ per-subject heads (subjects=[...])
     def _group(self, subject, B):
         """``subject`` (host ints or a CPU tensor, one head index per clip) checked on the host -> device int32 [B];
         None for a single head.  Nothing is launched before this has passed."""
@@ -292,45 +297,6 @@ class BrainHead:
             raise ValueError(f"head: subject={idx.tolist()!r} has an index outside [0, {self.G}) (subjects={list(self.subjects)!r})")
         return idx.to(torch.int32).to(self.dev)
 
-    def _fwd_grouped(self, src_pooled, src_sumw, rows, n_rows, y, keep_scale, group):
-        """vlb_head_fwd_grouped on (src rows -> pooled_raw, sumw): LN2, dropout, grouped ridge, the objective."""
-        B = y.shape[0]
-        self._saved_cached = (y, keep_scale)
-        self._saved_group = group
-        c = self.compute
-        check(lib.vlb_head_fwd_grouped(src_pooled.data_ptr(), src_sumw.data_ptr(), rows.data_ptr(),
-                                       c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
-                                       c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
-                                       c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
-                                       y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), group.data_ptr(),
-                                       self.gws.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
-                                       self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                       self.rowstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, self.E,
-                                       self.V, self.G, n_rows, self.eps, self._lam(),
-                                       self.loss_kind if self.tw is None else LOSS_KINDS["mse"], _stream()),
-              "vlb_head_fwd_grouped")
-        if self.tw is not None:
-            self._wloss_fwd(y, B, 0, group)
-        self._l2_rows_fwd()
-        return self.pred, self.loss_terms
-
-    def _bwd_grouped(self, loss_scale, l2_scale):
-        y, keep_scale = self._saved_cached
-        B = y.shape[0]
-        c, gr = self.compute, self.grads
-        check(lib.vlb_head_bwd_grouped(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
-                                       c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(),
-                                       None if keep_scale is None else keep_scale.data_ptr(), self._saved_group.data_ptr(),
-                                       self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
-                                       self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                       gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
-                                       gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
-                                       gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(),
-                                       self.gws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(), self.rowstat.data_ptr(),
-                                       B, self.E, self.V, self.G, self.eps, self._lam(), float(loss_scale), float(l2_scale),
-                                       self.loss_kind, _stream()), "vlb_head_bwd_grouped")
-        self._l2_rows_bwd(l2_scale)
-
     def subject_state_dict(self, name_or_index):
         """One subject's head in the reference's shapes ([V,E], [V], the shared LN tensors; fp32 masters): what a
         per-subject reference module loads."""
@@ -345,79 +311,151 @@ class BrainHead:
             raise ValueError(f"head: subject index {name_or_index!r} outside [0, {self.G})")
         return {n: (t[g] if n.startswith("ridge_layer.") else t).detach().clone() for n, t in self.master.items()}
 
-    def forward(self, hidden, wmask, y, keep_scale=None, layout=None, subject=None):
-        """hidden bf16 [B*S,E] (or [B,S,E]; packed rows with a packed ``layout``), wmask f32 [B,S] (always
-        dense), y f32 [B,V] -> (pred f32 [B,V], loss_terms f32[3]).  ``subject``: the head index of every clip, for a head
-        built with ``subjects`` (then: vlb_head_pool, the grouped tail on identity rows; backward adds vlb_head_dhidden)."""
+    # ------------------------------------------------------------------ sources of (pooled_raw, sumw)
+    def _rows_of(self, hidden, wmask, layout):
+        """-> (cu, rows) of a hidden tensor under a [B,S] mask: (None, B*S) dense, the layout's own when it is packed"""
         B, S = wmask.shape
-        group = self._group(subject, B)
         packed = layout is not None and layout.packed
         rows = layout.rows if packed else B * S
         if hidden.numel() != rows * self.E or (packed and (layout.B, layout.S) != (B, S)):
             raise ValueError(f"head: hidden has {hidden.numel() // self.E} rows, layout expects {rows}")
-        cu = layout.cu if packed else None
-        self._buffers(B, S)
-        self._saved = (hidden, wmask, y, keep_scale, cu, rows)
-        c = self.compute
-        if group is not None:
-            check(lib.vlb_head_pool(hidden.data_ptr(), wmask.data_ptr(), self.ws.data_ptr(), self.stats.data_ptr(),
-                                    self.pool_src.data_ptr(), self.pool_sumw.data_ptr(), B, S, self.E, self.eps,
-                                    None if cu is None else cu.data_ptr(), _stream()), "vlb_head_pool")
-            return self._fwd_grouped(self.pool_src, self.pool_sumw, self.rows_id, B, y, keep_scale, group)
-        check(lib.vlb_head_fwd(hidden.data_ptr(), wmask.data_ptr(), c["layer_norm1.weight"].data_ptr(),
-                               c["layer_norm1.bias"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
-                               c["layer_norm2.bias"].data_ptr(), c["ridge_layer.linear.weight"].data_ptr(),
-                               c["ridge_layer.linear.bias"].data_ptr(), y.data_ptr(),
-                               None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
-                               self.stats.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
-                               self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                               self.loss_terms.data_ptr(), B, S, self.E, self.V, self.eps, self._lam(),
-                               None if cu is None else cu.data_ptr(), _stream()),
-              "vlb_head_fwd")
-        if self.tw is not None:
-            self._wloss_fwd(y, B, S, None)
-        elif self.loss_kind:
+        return (layout.cu if packed else None), rows
+
+    def _pool(self, hidden, wmask, cu, stats, pooled, sumw):
+        """LN1 statistics and the pooled vector of one hidden tensor: the pooling half of vlb_head_fwd"""
+        B, S = wmask.shape
+        check(lib.vlb_head_pool(hidden.data_ptr(), wmask.data_ptr(), self.ws.data_ptr(), stats.data_ptr(), pooled.data_ptr(),
+                                sumw.data_ptr(), B, S, self.E, self.eps, _p(cu), _stream()), "vlb_head_pool")
+
+    def _cached_buffers(self, B):
+        if self._cap is None or self._cap[0] != B:
+            self._buffers(B, 1)           # no pooling workspace needed; buffers of an uncached step of this B serve as they are
+
+    def _gather_taps(self, cache, rows, B):
+        """p_stack, tap_sumw <- the K slabs of ``cache`` at ``rows``: the taps' pooled vectors, as ``tap`` leaves them"""
+        if cache.layers != self.K:
+            raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for {self.K} tapped layer(s)")
+        self.begin(B, self._cap[1] if self._cap is not None and self._cap[0] == B else 1)
+        for k in range(self.K):
+            check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
+                                               self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
+                                               _stream()), "vlb_feature_cache_gather")
+
+    def _mix(self, B):
+        """alpha = softmax(layer_mix.weight), mixed = sum_k alpha_k P_k"""
+        check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), self.compute[LAYER_MIX].data_ptr() if self.K > 1 else None,
+                                   self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
+              "vlb_head_mix_fwd")
+
+    # ------------------------------------------------------------------ one tail, one finisher, one backward tail
+    def _tail(self, src_pooled, src_sumw, rows, n_rows, y, keep_scale, group):
+        """(src rows -> pooled_raw, sumw), LN2, dropout, the ridge layer of one head (``group`` None) or of every clip's own
+        (DESIGN §5.3.4), the objective -> (pred f32 [B,V], loss_terms f32[3])"""
+        B = y.shape[0]
+        self._saved_tail = (y, keep_scale, group)
+        if group is None:
+            check(lib.vlb_head_fwd_cached(src_pooled.data_ptr(), src_sumw.data_ptr(), rows.data_ptr(), *self._fwd_params(),
+                                          y.data_ptr(), _p(keep_scale), self.ws.data_ptr(), *self._acts(),
+                                          self.loss_terms.data_ptr(), B, self.E, self.V, n_rows, self.eps, self._lam(),
+                                          _stream()), "vlb_head_fwd_cached")
+        else:       # the entry finishes a correlation objective itself; the weighted one starts from its MSE partials
+            check(lib.vlb_head_fwd_grouped(src_pooled.data_ptr(), src_sumw.data_ptr(), rows.data_ptr(), *self._fwd_params(),
+                                           y.data_ptr(), _p(keep_scale), group.data_ptr(), self.gws.data_ptr(), *self._acts(),
+                                           self.rowstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B,
+                                           self.E, self.V, self.G, n_rows, self.eps, self._lam(),
+                                           self.loss_kind if self.tw is None else LOSS_KINDS["mse"], _stream()),
+                  "vlb_head_fwd_grouped")
+        return self._finish(y, B, 0, group)
+
+    def _finish(self, y, B, S, group):
+        """The objective, on the pred and ridge partials the forward just left (S: where they sit in the workspace - behind
+        the pooling slabs of vlb_head_fwd, 0 after the tail; group: the grouped tail's, its workspace is gws), then the
+        penalty per row -> (pred, loss_terms)."""
+        if self.tw is not None:           # loss_terms, loss_aux, wstat <- the weighted objective
+            ws = self.ws if group is None else self.gws
+            check(lib.vlb_head_wloss_fwd(self.pred.data_ptr(), y.data_ptr(), self.tw.data_ptr(), _p(group), ws.data_ptr(),
+                                         self.wstat.data_ptr(), self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, S,
+                                         self.E, self.V, max(1, self.G), self.loss_kind, self._lam(), _stream()),
+                  "vlb_head_wloss_fwd")
+        elif self.loss_kind and group is None:
             self._loss_fwd(y, B, S)
         self._l2_rows_fwd()
         return self.pred, self.loss_terms
 
     def _loss_fwd(self, y, B, S):
-        """loss_terms[0], [2] <- the chosen objective (S: where the forward left its ridge partials in ws; 0 = cached)"""
+        """loss_terms[0], [2] <- the chosen correlation objective of a single head"""
         check(lib.vlb_head_loss_fwd(self.pred.data_ptr(), y.data_ptr(), self.ws.data_ptr(), self.rowstat.data_ptr(),
                                     self.loss_terms.data_ptr(), self.loss_aux.data_ptr(), B, S, self.E, self.V,
                                     self.loss_kind, self._lam(), _stream()), "vlb_head_loss_fwd")
+
+    def _backward_tail(self, loss_scale, l2_scale):
+        """Parameter gradients (self.grads, overwritten) and dpooled = d loss / d pooled_raw of the last tail or forward."""
+        y, keep_scale, group = self._saved_tail
+        B = y.shape[0]
+        if self.tw is not None:
+            ws = self.ws if group is None else self.gws
+            check(lib.vlb_head_bwd_wloss(*self._bwd_params(), y.data_ptr(), self.tw.data_ptr(), _p(keep_scale), _p(group),
+                                         *self._acts(), self.wstat.data_ptr(), self.dpred.data_ptr(), *self._grad_ptrs(),
+                                         ws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(), B, self.E, self.V,
+                                         max(1, self.G), self._lam(), float(loss_scale), float(l2_scale), self.loss_kind,
+                                         _stream()), "vlb_head_bwd_wloss")
+        elif group is not None:
+            check(lib.vlb_head_bwd_grouped(*self._bwd_params(), y.data_ptr(), _p(keep_scale), group.data_ptr(), *self._acts(),
+                                           *self._grad_ptrs(), self.gws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(),
+                                           self.rowstat.data_ptr(), B, self.E, self.V, self.G, self.eps, self._lam(),
+                                           float(loss_scale), float(l2_scale), self.loss_kind, _stream()), "vlb_head_bwd_grouped")
+        else:
+            fn, tail, what = lib.vlb_head_bwd_cached, (), "vlb_head_bwd_cached"
+            if self.loss_kind:
+                fn, tail, what = lib.vlb_head_bwd_cached_loss, (self.loss_kind, self.rowstat.data_ptr()), "vlb_head_bwd_cached_loss"
+            check(fn(*self._bwd_params(), y.data_ptr(), _p(keep_scale), *self._acts(), *self._grad_ptrs(), self.ws.data_ptr(),
+                     self.dz.data_ptr(), self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self._lam(), float(loss_scale),
+                     float(l2_scale), _stream(), *tail), what)
+        self._l2_rows_bwd(l2_scale)
+
+    def _dhidden(self, hidden, wmask, stats, dpooled, dx, cu, rows, add):
+        """dx (bf16 [rows,E]) <- or += one hidden tensor's term of d loss / d hidden: vlb_head_bwd's last launch"""
+        B, S = wmask.shape
+        check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), stats.data_ptr(), dpooled.data_ptr(), dx.data_ptr(), B, S,
+                                   self.E, _p(cu), rows, add, _stream()), "vlb_head_dhidden")
+
+    # ------------------------------------------------------------------ one hidden tensor
+    def forward(self, hidden, wmask, y, keep_scale=None, layout=None, subject=None):
+        """hidden bf16 [B*S,E] (or [B,S,E]; packed rows with a packed ``layout``), wmask f32 [B,S] (always
+        dense), y f32 [B,V] -> (pred f32 [B,V], loss_terms f32[3]).  ``subject``: the head index of every clip, for a head
+        built with ``subjects`` (then: vlb_head_pool, the tail on identity rows; backward adds vlb_head_dhidden)."""
+        B, S = wmask.shape
+        group = self._group(subject, B)
+        cu, rows = self._rows_of(hidden, wmask, layout)
+        self._buffers(B, S)
+        self._saved = (hidden, wmask, y, keep_scale, cu, rows)
+        if group is not None:
+            self._pool(hidden, wmask, cu, self.stats, self.pool_src, self.pool_sumw)
+            return self._tail(self.pool_src, self.pool_sumw, self.identity_rows, B, y, keep_scale, group)
+        self._saved_tail = (y, keep_scale, None)
+        check(lib.vlb_head_fwd(hidden.data_ptr(), wmask.data_ptr(), *self._fwd_params(), y.data_ptr(), _p(keep_scale),
+                               self.ws.data_ptr(), self.stats.data_ptr(), *self._acts(), self.loss_terms.data_ptr(), B, S,
+                               self.E, self.V, self.eps, self._lam(), _p(cu), _stream()), "vlb_head_fwd")
+        return self._finish(y, B, S, None)
 
     def backward(self, need_dhidden: bool, loss_scale: float = 1.0, l2_scale: float = 1.0):
         """Fills self.grads (fp32, overwritten) and returns d loss / d hidden (bf16) or None."""
         hidden, wmask, y, keep_scale, cu, rows = self._saved
         B, S = wmask.shape
-        c, gr = self.compute, self.grads
         dh = torch.empty(rows, self.E, dtype=BF16, device=self.dev) if need_dhidden else None
         if self.G or self.tw is not None:
-            if self.tw is not None:
-                self._bwd_wloss(y, keep_scale, loss_scale, l2_scale)
-            else:
-                self._bwd_grouped(loss_scale, l2_scale)
+            self._backward_tail(loss_scale, l2_scale)
             if need_dhidden:
-                check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), self.stats.data_ptr(), self.dpooled.data_ptr(),
-                                           dh.data_ptr(), B, S, self.E, None if cu is None else cu.data_ptr(), rows, 0,
-                                           _stream()), "vlb_head_dhidden")
+                self._dhidden(hidden, wmask, self.stats, self.dpooled, dh, cu, rows, 0)
             return dh
+        # one head, no weights: the fused entry (it refuses a wrong row count before its first launch)
         fn, tail, what = lib.vlb_head_bwd, (), "vlb_head_bwd"
         if self.loss_kind:
             fn, tail, what = lib.vlb_head_bwd_loss, (self.loss_kind, self.rowstat.data_ptr()), "vlb_head_bwd_loss"
-        check(fn(hidden.data_ptr(), wmask.data_ptr(), c["layer_norm1.weight"].data_ptr(),
-                 c["layer_norm2.weight"].data_ptr(), c["ridge_layer.linear.weight"].data_ptr(),
-                 y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(),
-                 self.stats.data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
-                 self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                 gr["ridge_layer.linear.weight"].data_ptr(), gr["ridge_layer.linear.bias"].data_ptr(),
-                 gr["layer_norm2.weight"].data_ptr(), gr["layer_norm2.bias"].data_ptr(),
-                 gr["layer_norm1.weight"].data_ptr(), gr["layer_norm1.bias"].data_ptr(),
-                 self.ws.data_ptr(), self.dz.data_ptr(), self.dpooled.data_ptr(),
-                 None if dh is None else dh.data_ptr(), B, S, self.E, self.V, self.eps, self._lam(),
-                 float(loss_scale), float(l2_scale), None if cu is None else cu.data_ptr(), rows,
-                 _stream(), *tail), what)
+        check(fn(hidden.data_ptr(), wmask.data_ptr(), *self._bwd_params(), y.data_ptr(), _p(keep_scale),
+                 self.stats.data_ptr(), *self._acts(), *self._grad_ptrs(), self.ws.data_ptr(), self.dz.data_ptr(),
+                 self.dpooled.data_ptr(), _p(dh), B, S, self.E, self.V, self.eps, self._lam(), float(loss_scale),
+                 float(l2_scale), _p(cu), rows, _stream(), *tail), what)
         self._l2_rows_bwd(l2_scale)
         return dh
 
@@ -431,35 +469,14 @@ class BrainHead:
         if rows.numel() != B:
             raise ValueError(f"head: {rows.numel()} cache rows for a batch of {B}")
         if self.K:                        # K slabs per clip -> the taps' pooled vectors, then the tapped forward as uncached
-            if cache.layers != self.K:
-                raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for {self.K} tapped layer(s)")
-            self.begin(B, self._cap[1] if self._cap is not None and self._cap[0] == B else 1)
-            for k in range(self.K):
-                check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
-                                                   self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
-                                                   _stream()), "vlb_feature_cache_gather")
+            self._gather_taps(cache, rows, B)
             return self.forward_tapped(y, keep_scale, subject)
-        if self._cap is None or self._cap[0] != B:
-            self._buffers(B, 1)           # no pooling workspace needed; buffers of an uncached step of this B serve as they are
-        if group is not None:
-            return self._fwd_grouped(cache.pooled, cache.sumw, rows, cache.n, y, keep_scale, group)
-        self._saved_cached = (y, keep_scale)
-        c = self.compute
-        check(lib.vlb_head_fwd_cached(cache.pooled.data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
-                                      c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
-                                      c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
-                                      c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
-                                      y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
-                                      self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
-                                      self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                      self.loss_terms.data_ptr(), B, self.E, self.V, cache.n, self.eps, self._lam(),
-                                      _stream()), "vlb_head_fwd_cached")
-        if self.tw is not None:
-            self._wloss_fwd(y, B, 0, None)
-        elif self.loss_kind:
-            self._loss_fwd(y, B, 0)
-        self._l2_rows_fwd()
-        return self.pred, self.loss_terms
+        self._cached_buffers(B)
+        return self._tail(cache.pooled, cache.sumw, rows, cache.n, y, keep_scale, group)
+
+    def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
+        """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""
+        self._backward_tail(loss_scale, l2_scale)
 
     # ------------------------------------------------------------------ readout from chosen decoder layers (readout_layers)
     # Per step: begin(B, S); tap(i, hidden_i, wmask, layout) as each tapped layer's output exists (only its LN1 statistics
@@ -480,7 +497,6 @@ class BrainHead:
             self.draw_stack = torch.empty(K, B, E, dtype=f32, device=d)        # alpha_k * d loss / d pooled_raw
             self.mix_ws = torch.empty(max(1, lib.vlb_head_mix_ws_floats(K, B, E)), dtype=f32, device=d)
             self._d_a1 = torch.empty(1, dtype=f32, device=d)                   # K = 1: no logit, its (zero) gradient lands here
-            self.identity_rows = torch.arange(B, dtype=torch.int32, device=d)
             self._tap_cap = (B, S)
         self._tap_meta = None
 
@@ -488,51 +504,25 @@ class BrainHead:
         """LN1 statistics and pooled vector of tap i (0-based position in ``readout_layers``) from its hidden tensor
         (bf16 rows x E, dense [B*S] or packed by ``layout``): the pooling half of vlb_head_fwd."""
         B, S = wmask.shape
-        packed = layout is not None and layout.packed
-        rows = layout.rows if packed else B * S
-        if hidden.numel() != rows * self.E or (packed and (layout.B, layout.S) != (B, S)):
-            raise ValueError(f"head: hidden has {hidden.numel() // self.E} rows, layout expects {rows}")
+        cu, rows = self._rows_of(hidden, wmask, layout)
         if self._tap_cap != (B, S) or not 0 <= i < self.K:
             raise ValueError(f"head: tap({i}) of a [{B},{S}] mask after begin{self._tap_cap} with {self.K} tap(s)")
-        cu = layout.cu if packed else None
         self._tap_meta = (wmask, cu, rows)
-        check(lib.vlb_head_pool(hidden.data_ptr(), wmask.data_ptr(), self.ws.data_ptr(), self.tap_stats[i].data_ptr(),
-                                self.p_stack[i].data_ptr(), self.tap_sumw.data_ptr(), B, S, self.E, self.eps,
-                                None if cu is None else cu.data_ptr(), _stream()), "vlb_head_pool")
+        self._pool(hidden, wmask, cu, self.tap_stats[i], self.p_stack[i], self.tap_sumw)
 
     def forward_tapped(self, y, keep_scale=None, subject=None):
-        """alpha = softmax(layer_mix.weight), pooled_raw = sum_k alpha_k P_k, then the tail of the head as
-        vlb_head_fwd_cached runs it on (pooled_raw, sumw) -> (pred f32 [B,V], loss_terms f32[3])."""
+        """alpha = softmax(layer_mix.weight), pooled_raw = sum_k alpha_k P_k, then the tail of the head on
+        (pooled_raw, sumw) -> (pred f32 [B,V], loss_terms f32[3])."""
         B = y.shape[0]
         group = self._group(subject, B)
-        c = self.compute
-        check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), c[LAYER_MIX].data_ptr() if self.K > 1 else None,
-                                   self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
-              "vlb_head_mix_fwd")
-        if group is not None:
-            return self._fwd_grouped(self.mixed, self.tap_sumw, self.identity_rows, B, y, keep_scale, group)
-        self._saved_cached = (y, keep_scale)
-        check(lib.vlb_head_fwd_cached(self.mixed.data_ptr(), self.tap_sumw.data_ptr(), self.identity_rows.data_ptr(),
-                                      c["layer_norm1.weight"].data_ptr(), c["layer_norm1.bias"].data_ptr(),
-                                      c["layer_norm2.weight"].data_ptr(), c["layer_norm2.bias"].data_ptr(),
-                                      c["ridge_layer.linear.weight"].data_ptr(), c["ridge_layer.linear.bias"].data_ptr(),
-                                      y.data_ptr(), None if keep_scale is None else keep_scale.data_ptr(), self.ws.data_ptr(),
-                                      self.pooled_raw.data_ptr(), self.sumw.data_ptr(), self.zhat.data_ptr(),
-                                      self.ln2_rstd.data_ptr(), self.z.data_ptr(), self.pred.data_ptr(),
-                                      self.loss_terms.data_ptr(), B, self.E, self.V, B, self.eps, self._lam(),
-                                      _stream()), "vlb_head_fwd_cached")
-        if self.tw is not None:
-            self._wloss_fwd(y, B, 0, None)
-        elif self.loss_kind:
-            self._loss_fwd(y, B, 0)
-        self._l2_rows_fwd()
-        return self.pred, self.loss_terms
+        self._mix(B)
+        return self._tail(self.mixed, self.tap_sumw, self.identity_rows, B, y, keep_scale, group)
 
     def backward_tapped(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
-        """Head gradients on the mixed pooled vector (vlb_head_bwd_cached: fills self.grads), then the mix's own:
+        """Head gradients on the mixed pooled vector (fills self.grads), then the mix's own:
         grads['layer_mix.weight'] (K > 1; written) and draw_stack[k] = alpha_k * d loss / d pooled_raw for dhidden()."""
-        self.backward_cached(loss_scale, l2_scale)
-        B = self._saved_cached[0].shape[0]
+        self._backward_tail(loss_scale, l2_scale)
+        B = self._saved_tail[0].shape[0]
         d_a = self.grads[LAYER_MIX] if self.K > 1 else self._d_a1
         check(lib.vlb_head_mix_bwd(self.p_stack.data_ptr(), self.dpooled.data_ptr(), self.alpha.data_ptr(), d_a.data_ptr(),
                                    self.draw_stack.data_ptr(), self.mix_ws.data_ptr(), self.K, B, self.E, _stream()),
@@ -543,39 +533,11 @@ class BrainHead:
         ``into`` None: a fresh tensor, zero-weight rows zeroed (vlb_head_bwd's last launch).  ``into`` = dx: added to dx
         in place on the rows with a non-zero weight; the others are not touched."""
         wmask, cu, rows = self._tap_meta
-        B, S = wmask.shape
         if hidden.numel() != rows * self.E or (into is not None and (into.numel() != rows * self.E or into.dtype != BF16)):
             raise ValueError(f"head: dhidden({i}) needs bf16 [{rows},{self.E}] tensors")
         dx = torch.empty(rows, self.E, dtype=BF16, device=self.dev) if into is None else into
-        check(lib.vlb_head_dhidden(hidden.data_ptr(), wmask.data_ptr(), self.tap_stats[i].data_ptr(),
-                                   self.draw_stack[i].data_ptr(), dx.data_ptr(), B, S, self.E,
-                                   None if cu is None else cu.data_ptr(), rows, 0 if into is None else 1, _stream()),
-              "vlb_head_dhidden")
+        self._dhidden(hidden, wmask, self.tap_stats[i], self.draw_stack[i], dx, cu, rows, 0 if into is None else 1)
         return dx
-
-    def backward_cached(self, loss_scale: float = 1.0, l2_scale: float = 1.0):
-        """Parameter gradients after forward_cached (fills self.grads, overwritten; no gradient wrt hidden)."""
-        if self.tw is not None:
-            return self._bwd_wloss(*self._saved_cached, loss_scale, l2_scale)
-        if self.G:
-            return self._bwd_grouped(loss_scale, l2_scale)
-        y, keep_scale = self._saved_cached
-        B = y.shape[0]
-        c, gr = self.compute, self.grads
-        fn, tail, what = lib.vlb_head_bwd_cached, (), "vlb_head_bwd_cached"
-        if self.loss_kind:
-            fn, tail, what = lib.vlb_head_bwd_cached_loss, (self.loss_kind, self.rowstat.data_ptr()), "vlb_head_bwd_cached_loss"
-        check(fn(c["layer_norm1.weight"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
-                 c["ridge_layer.linear.weight"].data_ptr(), y.data_ptr(),
-                 None if keep_scale is None else keep_scale.data_ptr(), self.pooled_raw.data_ptr(),
-                 self.sumw.data_ptr(), self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(),
-                 self.pred.data_ptr(), gr["ridge_layer.linear.weight"].data_ptr(),
-                 gr["ridge_layer.linear.bias"].data_ptr(), gr["layer_norm2.weight"].data_ptr(),
-                 gr["layer_norm2.bias"].data_ptr(), gr["layer_norm1.weight"].data_ptr(),
-                 gr["layer_norm1.bias"].data_ptr(), self.ws.data_ptr(), self.dz.data_ptr(),
-                 self.dpooled.data_ptr(), B, self.E, self.V, self.eps, self._lam(), float(loss_scale),
-                 float(l2_scale), _stream(), *tail), what)
-        self._l2_rows_bwd(l2_scale)
 
     # ------------------------------------------------------------------ closed-form ridge fit (ridge_fit="closed_form")
     # With loss="mse", the LN parameters (and the mix) held fixed and dropout off, the objective over N clips is a ridge
@@ -613,30 +575,18 @@ class BrainHead:
         head's own ``z`` buffer: the next call overwrites it."""
         rows = cache.rows(indices)
         B = rows.numel()
-        c = self.compute
         if self.K:
-            if cache.layers != self.K:
-                raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for {self.K} tapped layer(s)")
-            self.begin(B, self._cap[1] if self._cap is not None and self._cap[0] == B else 1)
-            for k in range(self.K):
-                check(lib.vlb_feature_cache_gather(cache.pooled[k].data_ptr(), cache.sumw.data_ptr(), rows.data_ptr(),
-                                                   self.p_stack[k].data_ptr(), self.tap_sumw.data_ptr(), B, self.E, cache.n,
-                                                   _stream()), "vlb_feature_cache_gather")
-            check(lib.vlb_head_mix_fwd(self.p_stack.data_ptr(), c[LAYER_MIX].data_ptr() if self.K > 1 else None,
-                                       self.alpha.data_ptr(), self.mixed.data_ptr(), self.K, B, self.E, _stream()),
-                  "vlb_head_mix_fwd")
+            self._gather_taps(cache, rows, B)
+            self._mix(B)
             src, sw, rows, n_rows = self.mixed, self.tap_sumw, self.identity_rows, B
         else:
             if cache.layers is not None:
                 raise ValueError(f"head: a feature cache of {cache.layers} slab(s) per clip for a head without readout_layers")
-            if self._cap is None or self._cap[0] != B:
-                self._buffers(B, 1)
+            self._cached_buffers(B)
             src, sw, n_rows = cache.pooled, cache.sumw, cache.n
-        check(lib.vlb_head_features_cached(src.data_ptr(), sw.data_ptr(), rows.data_ptr(), c["layer_norm1.weight"].data_ptr(),
-                                           c["layer_norm1.bias"].data_ptr(), c["layer_norm2.weight"].data_ptr(),
-                                           c["layer_norm2.bias"].data_ptr(), self.pooled_raw.data_ptr(), self.sumw.data_ptr(),
-                                           self.zhat.data_ptr(), self.ln2_rstd.data_ptr(), self.z.data_ptr(), B, self.E, n_rows,
-                                           self.eps, _stream()), "vlb_head_features_cached")
+        check(lib.vlb_head_features_cached(src.data_ptr(), sw.data_ptr(), rows.data_ptr(), *self._fwd_params()[:4],
+                                           *self._acts()[:5], B, self.E, n_rows, self.eps, _stream()),
+              "vlb_head_features_cached")
         return self.z
 
     def ridge_stats_add(self, cache, indices, y, subject=None):
@@ -663,12 +613,34 @@ class BrainHead:
         if "folds" in st:
             return self._ridge_stats_add_folds(st, cache, parts)
         for g, ids, yy in parts:
-            z = self.features_cached(cache, ids)
-            m = ids.numel()
-            check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), yy.data_ptr(), self.V, st["G"][g].data_ptr(), st["C"][g].data_ptr(),
-                                                st["sz"][g].data_ptr(), st["sy"][g].data_ptr(), m, self.E, self.V, _stream()),
-                  "vlb_ridge_gram_accumulate")
-            st["n"][g] += m
+            self._ridge_accumulate(st, g, cache, ids, yy)
+            st["n"][g] += ids.numel()
+
+    def _ridge_accumulate(self, st, at, cache, ids, y):
+        """the sums at ``at`` (a head, or a (head, fold)) += the cached clips ``ids`` with targets ``y``"""
+        z = self.features_cached(cache, ids)
+        check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), y.data_ptr(), self.V, st["G"][at].data_ptr(), st["C"][at].data_ptr(),
+                                            st["sz"][at].data_ptr(), st["sy"][at].data_ptr(), ids.numel(), self.E, self.V,
+                                            _stream()), "vlb_ridge_gram_accumulate")
+
+    def _head_totals(self, st, g):
+        """(G, C, sz, sy) of head g; with folds its folds' sums added in ascending order (skip = -1)"""
+        return self._ridge_fold_sums(st, g, -1) if "folds" in st else (st["G"][g], st["C"][g], st["sz"][g], st["sy"][g])
+
+    @staticmethod
+    def _ridge_grid(what, grid):
+        grid = [float(x) for x in grid]
+        if not grid or not all(math.isfinite(x) and x > 0 for x in grid):
+            raise ValueError(f"head: {what}: grid={grid!r}: one or more positive values are needed")
+        return grid
+
+    def _write_ridge(self, W, b):
+        """the fitted (W, b) into the fp32 masters and their bf16 copies"""
+        wn, bn = "ridge_layer.linear.weight", "ridge_layer.linear.bias"
+        self.master[wn].copy_(W.view(self.master[wn].shape))
+        self.master[bn].copy_(b.view(self.master[bn].shape))
+        self.compute[wn].copy_(self.master[wn])         # fp32 -> bf16, round to nearest even: what AdamW's rewrite gives too
+        self.compute[bn].copy_(self.master[bn])
 
     def ridge_solve(self, l2_lambda=None):
         """Minimise the mse objective over the accumulated clips in (weight, bias), per head: one fp64 Cholesky factorisation
@@ -682,7 +654,7 @@ class BrainHead:
             raise RuntimeError("head: ridge_solve() before ridge_stats_begin()")
         lam = self.l2_lambda if l2_lambda is None else float(l2_lambda)
         H, E, V, d = max(1, self.G), self.E, self.V, self.dev
-        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        name = self._head_name
         if lam < 0:
             raise ValueError(f"head: ridge_solve: l2_lambda = {lam} is negative")
         for g in range(H):
@@ -697,8 +669,7 @@ class BrainHead:
         b = torch.empty(H, V, dtype=torch.float32, device=d)
         info = torch.zeros(H, dtype=torch.int32, device=d)
         for g in range(H):
-            # with folds the head's totals are the folds' sums added in ascending order (skip = -1)
-            Gs, Cs, szs, sys_ = self._ridge_fold_sums(st, g, -1) if "folds" in st else (st["G"][g], st["C"][g], st["sz"][g], st["sy"][g])
+            Gs, Cs, szs, sys_ = self._head_totals(st, g)
             check(lib.vlb_ridge_solve(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(),
                                       st["n"][g], lam, A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(), b[g].data_ptr(),
                                       info[g:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
@@ -711,11 +682,7 @@ class BrainHead:
             if infos[g]:
                 raise ValueError(f"head: ridge_solve: {name(g)}: pivot {infos[g]} of {E} is not positive (info = {infos[g]}, "
                                  f"N = {st['n'][g]}, l2_lambda = {lam}): a larger l2_lambda, or NaN in the targets")
-        wn, bn = "ridge_layer.linear.weight", "ridge_layer.linear.bias"
-        self.master[wn].copy_(W.view(self.master[wn].shape))
-        self.master[bn].copy_(b.view(self.master[bn].shape))
-        self.compute[wn].copy_(self.master[wn])         # fp32 -> bf16, round to nearest even: what AdamW's rewrite gives too
-        self.compute[bn].copy_(self.master[bn])
+        self._write_ridge(W, b)
         return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": infos[g], "l2_lambda": lam}
                 for g in range(H)]
 
@@ -734,10 +701,7 @@ class BrainHead:
                 if not mk:
                     continue
                 yk = yy if mk == m else yy.index_select(0, sel.to(yy.device)).contiguous()
-                z = self.features_cached(cache, ids[sel])
-                check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), yk.data_ptr(), self.V, st["G"][g, k].data_ptr(),
-                                                    st["C"][g, k].data_ptr(), st["sz"][g, k].data_ptr(), st["sy"][g, k].data_ptr(),
-                                                    mk, self.E, self.V, _stream()), "vlb_ridge_gram_accumulate")
+                self._ridge_accumulate(st, (g, k), cache, ids[sel], yk)
                 check(lib.vlb_ridge_sumsq_accumulate(yk.data_ptr(), self.V, st["syy"][g, k].data_ptr(), mk, self.V, _stream()),
                       "vlb_ridge_sumsq_accumulate")
                 st["n_fold"][g][k] += mk
@@ -775,11 +739,9 @@ class BrainHead:
         st = getattr(self, "_ridge", None)
         if st is None or "folds" not in st:
             raise RuntimeError("head: ridge_cv() needs ridge_stats_begin(folds=K) and the clips added")
-        grid = [float(x) for x in grid]
-        if not grid or not all(math.isfinite(x) and x > 0 for x in grid):
-            raise ValueError(f"head: ridge_cv: grid={grid!r}: one or more positive values are needed")
+        grid = self._ridge_grid("ridge_cv", grid)
         H, K, L, E, V, d = max(1, self.G), st["folds"], len(grid), self.E, self.V, self.dev
-        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
+        name = self._head_name
         for g in range(H):
             for k in range(K):
                 if st["n_fold"][g][k] < 2:
@@ -855,11 +817,9 @@ class BrainHead:
         st = getattr(self, "_ridge", None)
         if st is None:
             raise RuntimeError("head: ridge_solve_rows() before ridge_stats_begin()")
-        grid = [float(x) for x in grid]
+        grid = self._ridge_grid("ridge_solve_rows", grid)
         H, E, V, L, d = max(1, self.G), self.E, self.V, len(grid), self.dev
-        name = (lambda g: f"head {g} ({self.subjects[g]!r})") if self.G else (lambda g: "the head")
-        if not grid or not all(math.isfinite(x) and x > 0 for x in grid):
-            raise ValueError(f"head: ridge_solve_rows: grid={grid!r}: one or more positive values are needed")
+        name = self._head_name
         if not isinstance(choice, torch.Tensor) or choice.dtype != torch.int32 or choice.numel() != H * V or \
                 choice.device.type != torch.device(d).type:
             raise ValueError(f"head: ridge_solve_rows needs choice int32 [{H},{V}] on {d}")
@@ -878,8 +838,7 @@ class BrainHead:
         used = [(g, i) for g in range(H) for i in range(L) if counts[g][i]]
         info = torch.zeros(len(used), dtype=torch.int32, device=d)
         for j, (g, i) in enumerate(used):
-            # with folds the head's totals are the folds' sums added in ascending order (skip = -1)
-            Gs, Cs, szs, sys_ = self._ridge_fold_sums(st, g, -1) if "folds" in st else (st["G"][g], st["C"][g], st["sz"][g], st["sy"][g])
+            Gs, Cs, szs, sys_ = self._head_totals(st, g)
             check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g], grid[i],
                                            A.data_ptr(), X.data_ptr(), W[g].data_ptr(), b[g].data_ptr(), info[j:].data_ptr(), E, V,
                                            choice[g].data_ptr(), i, _stream()), "vlb_ridge_solve_rows")
@@ -892,10 +851,6 @@ class BrainHead:
             if infos[j]:
                 raise ValueError(f"head: ridge_solve_rows: {name(g)}, l2_lambda = {grid[i]!r} (grid point {i}): pivot {infos[j]} "
                                  f"of {E} is not positive (info = {infos[j]}, N = {st['n'][g]}); the parameters are unchanged")
-        wn, bn = "ridge_layer.linear.weight", "ridge_layer.linear.bias"
-        self.master[wn].copy_(W.view(self.master[wn].shape))
-        self.master[bn].copy_(b.view(self.master[bn].shape))
-        self.compute[wn].copy_(self.master[wn])         # fp32 -> bf16, round to nearest even, as ridge_solve
-        self.compute[bn].copy_(self.master[bn])
+        self._write_ridge(W, b)
         return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": 0, "lambda_counts": counts[g]}
                 for g in range(H)]

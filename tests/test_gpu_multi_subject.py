@@ -103,15 +103,15 @@ def test_one_group_gives_the_ungrouped_bits(dev, case, loss):
     ref = {k: v.clone() for k, v in _tensors(plain).items()}
     # the grouped entries driven by hand on the same head: G = 1, group all zero, rows = identity
     g = plain
-    g.G, g._saved_group = 1, torch.zeros(B, dtype=torch.int32, device=dev)
+    g.G, group = 1, torch.zeros(B, dtype=torch.int32, device=dev)
     from phantom_vlb_amd._lib import lib
     g.gws = torch.empty(lib.vlb_head_grouped_ws_floats(B, E, V, 1), dtype=torch.float32, device=dev)
     src, srcw = plain.pooled_raw.clone(), plain.sumw.clone()
     rows = torch.arange(B, dtype=torch.int32, device=dev)
     for t in _tensors(g).values():
         t.fill_(float("nan"))
-    g._fwd_grouped(src, srcw, rows, B, y, keep, g._saved_group)
-    g._bwd_grouped(inp["loss_scale"], inp["l2_scale"])
+    g._tail(src, srcw, rows, B, y, keep, group)
+    g._backward_tail(inp["loss_scale"], inp["l2_scale"])
     torch.cuda.synchronize()
     for k, v in _tensors(g).items():
         assert torch.equal(v, ref[k]), (case["id"], loss, k)

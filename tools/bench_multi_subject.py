@@ -67,8 +67,8 @@ def make_head(dev, V, G, grouped):
         group = torch.zeros(B, dtype=torch.int32, device=dev)
 
         def fn():
-            head._fwd_grouped(cache.pooled, cache.sumw, rows, B, y, None, group)
-            head._bwd_grouped(1.0, 1.0)
+            head._tail(cache.pooled, cache.sumw, rows, B, y, None, group)      # a group: the grouped entries, with G = 1
+            head._backward_tail(1.0, 1.0)
     elif grouped:
         def fn():
             head.forward_cached(cache, idx, y, None, subject=subject)
