@@ -745,6 +745,26 @@ int64_t vlb_head_l2_rows_ws_doubles(int R);
 int vlb_head_l2_rows_fwd(const void* ridge_w, const float* lam, double* ws, float* loss_terms, int R, int E, void* stream);
 int vlb_head_l2_rows_bwd(const void* ridge_w, const float* lam, float* d_ridge_w, int R, int E, float coef, void* stream);
 
+/* The closed-form fit and its cross-validation under target weights (opt-in, ridge_fit_weighted; every entry
+ * point above keeps its bits).  With w = the head's weight row and Ws = sum_v w_v,
+ *   J(W, b) = (1/N) sum_n sum_v w_v (W_v z_n + b_v - y_nv)^2 / Ws + sum_v lambda_v ||W_v||^2
+ * decouples per target: for w_v > 0 row v is row v of vlb_ridge_solve's minimiser with l2_lambda = lambda_v Ws / (V w_v) (one
+ * factorisation per distinct weight, through vlb_ridge_solve_rows), for w_v = 0 it is W_v = 0, b_v = 0.  What is new is that a
+ * masked target column may hold NaN / Inf and must reach no sum.  keep: fp32 [V], the weight row, 4-byte aligned, never read at
+ * an index >= V; y[r,v] is read through a select on keep[v] > 0 (else +0.0f), never multiplied by it.
+ * vlb_ridge_gram_accumulate_masked (src/utils.py:59-73): vlb_ridge_gram_accumulate's four launches with that select in both
+ *   staging paths of the y slab and in the column sum: G, sz and the kept rows of C / entries of sy have the bits the unmasked
+ *   entry gives, masked rows of C and masked sy get +0.0 added whatever bits y holds there.
+ * vlb_ridge_sumsq_accumulate_masked (src/utils.py:59-73: the layer's targets): the same select for syy.
+ * vlb_ridge_cv_score_rows (src/utils.py:59-73: the layer's prediction, never formed): vlb_ridge_cv_score's launches; r_out[v]
+ *   is written only where choice[v] == want (want >= 0) with vlb_ridge_cv_score's bits, every other entry keeps its bytes; a
+ *   non-zero *info writes nothing. */
+int vlb_ridge_gram_accumulate_masked(const void* z, const float* y, int ldy, const float* keep, double* G, double* C, double* sz,
+                                     double* sy, int n, int E, int V, void* stream);
+int vlb_ridge_sumsq_accumulate_masked(const float* y, int ldy, const float* keep, double* syy, int n, int V, void* stream);
+int vlb_ridge_cv_score_rows(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws, double* r_out,
+                            const int* info, int E, int V, const int* choice, int want, void* stream);
+
 /* head dropout mask (litmodule :226,251 nn.Dropout(p) in training): out[i] = keep_i / (1-p), keep_i from a
  * counter-based hash of (seed, i) with 16 random bits per element (same mixer as the LoRA masks).  The result is
  * what vlb_head_fwd / vlb_head_bwd take as `keep_scale`. */

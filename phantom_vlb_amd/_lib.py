@@ -147,6 +147,9 @@ SIGNATURES = {
     "vlb_ridge_cv_score": [P, P, P, P, P, P, P, I, I, P],
     "vlb_ridge_cv_select": [P, P, P, P, P, P, I, I, I, P],
     "vlb_ridge_solve_rows": [P, P, P, P, L, D, P, P, P, P, P, I, I, P, I, P],
+    "vlb_ridge_gram_accumulate_masked": [P, P, I, P, P, P, P, P, I, I, I, P],
+    "vlb_ridge_sumsq_accumulate_masked": [P, I, P, P, I, I, P],
+    "vlb_ridge_cv_score_rows": [P, P, P, P, P, P, P, I, I, P, I, P],
     "vlb_head_l2_rows_ws_doubles": [I],
     "vlb_head_l2_rows_fwd": [P, P, P, P, I, I, P],
     "vlb_head_l2_rows_bwd": [P, P, P, I, I, F, P],

@@ -29,11 +29,23 @@ constexpr int LP = NB + 1;    // LDS row pitch (doubles) of a 64 x 64 block: col
 __device__ __forceinline__ double widen(bf16 x) { return (double)(float)x; }
 __device__ __forceinline__ double widen(float x) { return (double)x; }
 
-template <typename T>
-__device__ __forceinline__ void stage_slab(const T* __restrict__ src, int64_t ld, int r0, int n, int c0, int ncols, T* lds) {
+// MASK (the target-weighted fit; T = float): column c0 + j of src is read through a select on keep[c0 + j] > 0,
+// else +0.0f - never a product, so a NaN / Inf in a masked column stays out of the slab.  A thread's columns are the same in
+// every step of the chunk loop (256 % (TS / PER) == 0), so its PER flags are read once; keep is not read at c0 + j >= ncols.
+template <typename T, bool MASK = false>
+__device__ __forceinline__ void stage_slab(const T* __restrict__ src, int64_t ld, int r0, int n, int c0, int ncols, T* lds,
+                                           const float* __restrict__ keep = nullptr) {
   constexpr int PER = 16 / (int)sizeof(T);                 // elements of one 16-byte access
   constexpr int CHUNKS = GK * TS / PER;                    // 256 (bf16) or 512 (fp32)
+  static_assert(256 % (TS / PER) == 0, "a thread keeps its columns over the chunk loop");
   const bool vec = ld % PER == 0 && ((uintptr_t)src & 15) == 0 && c0 + TS <= ncols;      // block-uniform
+  [[maybe_unused]] bool kp[PER];
+  if constexpr (MASK) {
+    static_assert(sizeof(T) == 4, "the masked slab is the fp32 target slab");
+    const int kc = c0 + ((int)threadIdx.x % (TS / PER)) * PER;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) kp[i] = kc + i < ncols && keep[kc + i] > 0.f;
+  }
 #pragma unroll
   for (int c = threadIdx.x; c < CHUNKS; c += 256) {
     const int r = c / (TS / PER), col = (c % (TS / PER)) * PER;
@@ -41,18 +53,26 @@ __device__ __forceinline__ void stage_slab(const T* __restrict__ src, int64_t ld
     if (vec) {
       u32x4 v = {0u, 0u, 0u, 0u};
       if (r0 + r < n) v = *reinterpret_cast<const u32x4*>(src + (int64_t)(r0 + r) * ld + c0 + col);
+      if constexpr (MASK) {
+#pragma unroll
+        for (int i = 0; i < PER; ++i) v[i] = kp[i] ? v[i] : 0u;
+      }
       *reinterpret_cast<u32x4*>(dst) = v;
     } else {
 #pragma unroll
-      for (int i = 0; i < PER; ++i)
-        dst[i] = (r0 + r < n && c0 + col + i < ncols) ? src[(int64_t)(r0 + r) * ld + c0 + col + i] : (T)0.f;
+      for (int i = 0; i < PER; ++i) {
+        bool in = r0 + r < n && c0 + col + i < ncols;
+        if constexpr (MASK) in = in && kp[i];
+        dst[i] = in ? src[(int64_t)(r0 + r) * ld + c0 + col + i] : (T)0.f;
+      }
     }
   }
 }
 
-template <typename TA>
-__global__ __launch_bounds__(256) void gram_tile_kernel(const TA* __restrict__ A, int64_t lda, const bf16* __restrict__ Bz,
-                                                        int64_t ldb, double* __restrict__ D, int64_t ldd, int n, int M, int N) {
+template <typename TA, bool MASK>
+__device__ __forceinline__ void gram_tile_body(const TA* __restrict__ A, int64_t lda, const bf16* __restrict__ Bz, int64_t ldb,
+                                               double* __restrict__ D, int64_t ldd, int n, int M, int N,
+                                               const float* __restrict__ keep) {
   __shared__ __attribute__((aligned(16))) TA As[GK * TS];
   __shared__ __attribute__((aligned(16))) bf16 Bs[GK * TS];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
@@ -60,7 +80,7 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const TA* __restrict__ A
   double acc[4][4] = {};
   for (int r0 = 0; r0 < n; r0 += GK) {
     __syncthreads();
-    stage_slab<TA>(A, lda, r0, n, i0, M, As);
+    stage_slab<TA, MASK>(A, lda, r0, n, i0, M, As, keep);
     stage_slab<bf16>(Bz, ldb, r0, n, j0, N, Bs);
     __syncthreads();
 #pragma unroll 8
@@ -96,15 +116,48 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const TA* __restrict__ A
   }
 }
 
-// s[c] += sum over the n rows (ascending) of x[r, c]: one thread per column, lanes on consecutive columns
+template <typename TA>
+__global__ __launch_bounds__(256) void gram_tile_kernel(const TA* __restrict__ A, int64_t lda, const bf16* __restrict__ Bz,
+                                                        int64_t ldb, double* __restrict__ D, int64_t ldd, int n, int M, int N) {
+  gram_tile_body<TA, false>(A, lda, Bz, ldb, D, ldd, n, M, N, nullptr);
+}
+// C [V,E] += y^T z with the rows of C (the columns of y) read through keep: a masked row of C gets +0.0 added
+__global__ __launch_bounds__(256) void gram_tile_masked_kernel(const float* __restrict__ A, int64_t lda, const bf16* __restrict__ Bz,
+                                                               int64_t ldb, double* __restrict__ D, int64_t ldd, int n, int M, int N,
+                                                               const float* __restrict__ keep) {
+  gram_tile_body<float, true>(A, lda, Bz, ldb, D, ldd, n, M, N, keep);
+}
+
+// s[c] += sum over the n rows (ascending) of x[r, c]: one thread per column, lanes on consecutive columns.
+// MASK: x[r, c] through the select on keep[c] > 0 (else +0.0f, the element is not loaded); SQ: the squares (an fp32 square is
+// exact in fp64), colsumsq_f64_kernel's loop
+template <typename T, bool MASK, bool SQ>
+__device__ __forceinline__ void colsum_f64_body(const T* __restrict__ x, int64_t ld, double* __restrict__ s, int n, int ncols,
+                                                const float* __restrict__ keep) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= ncols) return;
+  [[maybe_unused]] bool kp = true;
+  if constexpr (MASK) kp = keep[c] > 0.f;
+  double t = 0.0;
+  for (int r = 0; r < n; ++r) {
+    T xv;
+    if constexpr (MASK) xv = kp ? x[(int64_t)r * ld + c] : (T)0.f;
+    else xv = x[(int64_t)r * ld + c];
+    const double w = widen(xv);
+    if constexpr (SQ) t = fma(w, w, t);
+    else t += w;
+  }
+  s[c] += t;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_f64_kernel(const T* __restrict__ x, int64_t ld, double* __restrict__ s, int n,
                                                          int ncols) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncols) return;
-  double t = 0.0;
-  for (int r = 0; r < n; ++r) t += widen(x[(int64_t)r * ld + c]);
-  s[c] += t;
+  colsum_f64_body<T, false, false>(x, ld, s, n, ncols, nullptr);
+}
+template <bool SQ>
+__global__ __launch_bounds__(256) void colsum_masked_f64_kernel(const float* __restrict__ x, int64_t ld, double* __restrict__ s,
+                                                                int n, int ncols, const float* __restrict__ keep) {
+  colsum_f64_body<float, true, SQ>(x, ld, s, n, ncols, keep);
 }
 
 // ---------------------------------------------------------------- fp64 tile kernel: D[M,N] -= P Q^T  (or P Q, QT)
@@ -359,14 +412,7 @@ __global__ __launch_bounds__(256) void ridge_finish_kernel(const double* __restr
 // s[c] += sum over the n rows (ascending) of y[r, c]^2: colsum_f64_kernel's twin (an fp32 square is exact in fp64)
 __global__ __launch_bounds__(256) void colsumsq_f64_kernel(const float* __restrict__ y, int64_t ld, double* __restrict__ s, int n,
                                                            int ncols) {
-  const int c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= ncols) return;
-  double t = 0.0;
-  for (int r = 0; r < n; ++r) {
-    const double w = widen(y[(int64_t)r * ld + c]);
-    t = fma(w, w, t);
-  }
-  s[c] += t;
+  colsum_f64_body<float, false, true>(y, ld, s, n, ncols, nullptr);
 }
 // out[i] = sum over j != skip (ascending) of parts[j * stride + i]: one thread per element, lanes on consecutive elements
 __global__ __launch_bounds__(256) void sum_except_f64_kernel(const double* __restrict__ parts, int64_t stride, int count, int skip,
@@ -462,13 +508,19 @@ __global__ __launch_bounds__(256) void cv_quad_tile_kernel(const double* __restr
 // r[v] = cov / sqrt(vp vy) clipped to [-1, 1], 0 unless vp > 0 and vy > 0:  vp = the nct partials of ws in ascending order,
 // cov = X[v,:] . Rc[v,:] summed as ridge_finish_kernel sums (per thread over e = t, t + 256, ..., then the 256 threads in
 // ascending order).  One block per v.  No-op on *info != 0.
-__global__ __launch_bounds__(256) void cv_finish_kernel(const double* __restrict__ X, const double* __restrict__ Rc,
-                                                        const double* __restrict__ vy, const double* __restrict__ ws,
-                                                        double* __restrict__ r_out, int E, int nct,
-                                                        const int* __restrict__ info) {
+// ROWS (vlb_ridge_cv_score_rows): only the blocks with choice[v] == want run, by the same arithmetic; every
+// other r_out[v] keeps its bytes - ridge_finish_kernel's pattern.
+template <bool ROWS>
+__device__ __forceinline__ void cv_finish_body(const double* __restrict__ X, const double* __restrict__ Rc,
+                                               const double* __restrict__ vy, const double* __restrict__ ws,
+                                               double* __restrict__ r_out, int E, int nct, const int* __restrict__ info,
+                                               const int* __restrict__ choice, int want) {
   __shared__ double part[256];
   if (*info != 0) return;
   const int v = blockIdx.x;
+  if constexpr (ROWS) {
+    if (choice[v] != want) return;                      // block-uniform
+  }
   double t = 0.0;
   for (int e = threadIdx.x; e < E; e += 256) t = fma(X[(int64_t)v * E + e], Rc[(int64_t)v * E + e], t);
   part[threadIdx.x] = t;
@@ -485,6 +537,19 @@ __global__ __launch_bounds__(256) void cv_finish_kernel(const double* __restrict
     }
     r_out[v] = r;
   }
+}
+__global__ __launch_bounds__(256) void cv_finish_kernel(const double* __restrict__ X, const double* __restrict__ Rc,
+                                                        const double* __restrict__ vy, const double* __restrict__ ws,
+                                                        double* __restrict__ r_out, int E, int nct,
+                                                        const int* __restrict__ info) {
+  cv_finish_body<false>(X, Rc, vy, ws, r_out, E, nct, info, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void cv_finish_rows_kernel(const double* __restrict__ X, const double* __restrict__ Rc,
+                                                             const double* __restrict__ vy, const double* __restrict__ ws,
+                                                             double* __restrict__ r_out, int E, int nct,
+                                                             const int* __restrict__ info, const int* __restrict__ choice,
+                                                             int want) {
+  cv_finish_body<true>(X, Rc, vy, ws, r_out, E, nct, info, choice, want);
 }
 
 // ---------------------------------------------------------------- l2_lambda per target
@@ -531,6 +596,26 @@ extern "C" int vlb_ridge_gram_accumulate(const void* z, const float* y, int ldy,
   hipLaunchKernelGGL(colsum_f64_kernel<bf16>, dim3((E + 255) / 256), dim3(256), 0, st, zz, (int64_t)E, sz, n, E);
   VLB_LAUNCH_CHECK();
   hipLaunchKernelGGL(colsum_f64_kernel<float>, dim3((V + 255) / 256), dim3(256), 0, st, y, (int64_t)ldy, sy, n, V);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// the target-weighted fit: vlb_ridge_gram_accumulate's four launches, y read through keep
+extern "C" int vlb_ridge_gram_accumulate_masked(const void* z, const float* y, int ldy, const float* keep, double* G, double* C,
+                                                double* sz, double* sy, int n, int E, int V, void* stream) {
+  VLB_REQUIRE(z && y && keep && G && C && sz && sy, "ridge_gram_accumulate_masked: null argument");
+  VLB_REQUIRE(n >= 1 && E >= 1 && V >= 1 && ldy >= V, "ridge_gram_accumulate_masked: bad shape n=%d E=%d V=%d ldy=%d", n, E, V, ldy);
+  VLB_REQUIRE(((uintptr_t)keep & 3) == 0, "ridge_gram_accumulate_masked: keep is not 4-byte aligned");
+  hipStream_t st = as_stream(stream);
+  const bf16* zz = (const bf16*)z;
+  hipLaunchKernelGGL(gram_tile_kernel<bf16>, tiles(E, E), dim3(256), 0, st, zz, (int64_t)E, zz, (int64_t)E, G, (int64_t)E, n, E, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gram_tile_masked_kernel, tiles(V, E), dim3(256), 0, st, y, (int64_t)ldy, zz, (int64_t)E, C, (int64_t)E, n, V, E,
+                     keep);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(colsum_f64_kernel<bf16>, dim3((E + 255) / 256), dim3(256), 0, st, zz, (int64_t)E, sz, n, E);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(colsum_masked_f64_kernel<false>, dim3((V + 255) / 256), dim3(256), 0, st, y, (int64_t)ldy, sy, n, V, keep);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }
@@ -649,6 +734,17 @@ extern "C" int vlb_ridge_sumsq_accumulate(const float* y, int ldy, double* syy, 
   return VLB_OK;
 }
 
+extern "C" int vlb_ridge_sumsq_accumulate_masked(const float* y, int ldy, const float* keep, double* syy, int n, int V,
+                                                 void* stream) {
+  VLB_REQUIRE(y && keep && syy, "ridge_sumsq_accumulate_masked: null argument");
+  VLB_REQUIRE(n >= 1 && V >= 1 && ldy >= V, "ridge_sumsq_accumulate_masked: bad shape n=%d V=%d ldy=%d", n, V, ldy);
+  VLB_REQUIRE(((uintptr_t)keep & 3) == 0, "ridge_sumsq_accumulate_masked: keep is not 4-byte aligned");
+  hipLaunchKernelGGL(colsum_masked_f64_kernel<true>, dim3((V + 255) / 256), dim3(256), 0, as_stream(stream), y, (int64_t)ldy, syy, n,
+                     V, keep);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
 extern "C" int vlb_f64_sum_except(const double* parts, int64_t stride, int count, int skip, double* out, int64_t numel,
                                   void* stream) {
   VLB_REQUIRE(parts && out, "f64_sum_except: null argument");
@@ -690,6 +786,21 @@ extern "C" int vlb_ridge_cv_score(const double* X, const double* Gc, const doubl
   hipLaunchKernelGGL(cv_quad_tile_kernel, tiles(V, E), dim3(256), 0, st, X, Gc, ws, E, V, info);
   VLB_LAUNCH_CHECK();
   hipLaunchKernelGGL(cv_finish_kernel, dim3(V), dim3(256), 0, st, X, Rc, vy, ws, r_out, E, nct, info);
+  VLB_LAUNCH_CHECK();
+  return VLB_OK;
+}
+
+// vlb_ridge_cv_score's two launches; r_out[v] is written only where choice[v] == want
+extern "C" int vlb_ridge_cv_score_rows(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws,
+                                       double* r_out, const int* info, int E, int V, const int* choice, int want, void* stream) {
+  VLB_REQUIRE(X && Gc && Rc && vy && ws && r_out && info && choice, "ridge_cv_score_rows: null argument");
+  VLB_REQUIRE(E >= 1 && V >= 1, "ridge_cv_score_rows: bad shape E=%d V=%d", E, V);
+  VLB_REQUIRE(want >= 0, "ridge_cv_score_rows: want=%d is negative", want);
+  hipStream_t st = as_stream(stream);
+  const int nct = (E + TS - 1) / TS;
+  hipLaunchKernelGGL(cv_quad_tile_kernel, tiles(V, E), dim3(256), 0, st, X, Gc, ws, E, V, info);
+  VLB_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cv_finish_rows_kernel, dim3(V), dim3(256), 0, st, X, Rc, vy, ws, r_out, E, nct, info, choice, want);
   VLB_LAUNCH_CHECK();
   return VLB_OK;
 }

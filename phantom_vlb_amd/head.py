@@ -57,6 +57,31 @@ def check_subjects(subjects):
     return out
 
 
+MAX_WEIGHT_LEVELS = 8                # distinct positive weights per head in the weighted closed-form fit: one factorisation each
+
+
+def target_weight_levels(tw, name=None):
+    """The levels of the weighted closed-form fit.  ``tw`` fp32 [H,V] (finite, >= 0) -> {"lvl": [H][V] (the
+    rank of a target's weight among its head's distinct positive fp32 values, ascending; -1: masked), "scale": [H][D_h] (fp64,
+    Ws / (V w_d) with Ws the exactly rounded sum of the row: what multiplies l2_lambda in that level's solve; 1.0 exactly for a
+    constant row), "levels": [H] (D_h)}.  More than ``MAX_WEIGHT_LEVELS`` levels in a head raises with the head named."""
+    rows = tw.detach().to("cpu", torch.float32).reshape(-1, tw.shape[-1]).tolist()         # fp32 values, exact as Python floats
+    V = len(rows[0])
+    out = {"lvl": [], "scale": [], "levels": []}
+    for g, row in enumerate(rows):
+        vals = sorted({w for w in row if w > 0})
+        if len(vals) > MAX_WEIGHT_LEVELS:
+            who = name(g) if name is not None else f"head {g}"
+            raise ValueError(f"target weights: {who} holds {len(vals)} distinct positive weights; the weighted closed-form fit "
+                             f"(ridge_fit_weighted) factors once per distinct weight and takes at most {MAX_WEIGHT_LEVELS}")
+        rank = {w: d for d, w in enumerate(vals)}
+        ws = math.fsum(row)
+        out["lvl"].append([rank[w] if w > 0 else -1 for w in row])
+        out["scale"].append([ws / (V * w) for w in vals])
+        out["levels"].append(len(vals))
+    return out
+
+
 LAYER_MIX = "layer_mix.weight"       # logits of the learned mix over the tapped layers (K > 1 only), fp32 master [K]
 MAX_TAPS = 64                        # MIX_KMAX of head.hip
 
@@ -543,16 +568,28 @@ class BrainHead:
     # With loss="mse", the LN parameters (and the mix) held fixed and dropout off, the objective over N clips is a ridge
     # regression in (ridge_layer.linear.weight, .bias); DESIGN §5.3.5.  ridge_stats_begin(); ridge_stats_add(...) per chunk of
     # cached clips; ridge_solve() -> the minimiser, written into the fp32 masters and their bf16 copies.  All fp64 on the device.
-    def ridge_stats_begin(self, folds=None, block=None):
+    def ridge_stats_begin(self, folds=None, block=None, weighted=False):
         """Allocate and zero the fp64 sums (G [E,E], C [V,E], sz [E], sy [V]), one set per head.  ``folds=K`` (with
         ``block``): one set per (head, fold) plus syy [V] = sum y^2, for ``ridge_cv``; a head's m-th clip
-        (its rank among the clips that head has received so far) goes to fold ``(m // block) % K``."""
+        (its rank among the clips that head has received so far) goes to fold ``(m // block) % K``.
+        ``weighted=True`` takes ``self.tw`` as it is at this call: the sums skip the masked targets (which may
+        hold NaN) and ``ridge_solve`` / ``ridge_cv`` / ``ridge_solve_rows`` minimise the weighted objective of §5.3.8, one
+        factorisation per distinct positive weight of a head (at most ``MAX_WEIGHT_LEVELS``).  Without weights set it changes
+        nothing."""
         if self.loss != "mse":
             raise ValueError(f"head: the closed-form ridge fit minimises the mse objective; this head has loss={self.loss!r}")
-        if self.tw is not None:
+        if self.tw is not None and not weighted:
             raise ValueError("head: the closed-form ridge fit does not take target weights (a mask would need NaN-tolerant Gram "
-                             "columns, general weights one factorisation per distinct weight): set_target_weights(None) first")
+                             "columns, general weights one factorisation per distinct weight) unless it is begun with "
+                             "weighted=True (ridge_fit_weighted): set_target_weights(None) first, or opt in")
         H, E, V, d, f64 = max(1, self.G), self.E, self.V, self.dev, torch.float64
+        wst = {}
+        if self.tw is not None:
+            lv = target_weight_levels(self.tw, self._head_name)
+            keep = self.tw > 0
+            wst = {"tw": self.tw.clone(), "lvl": torch.tensor(lv["lvl"], dtype=torch.int32, device=d), "scale": lv["scale"],
+                   "keep": keep, "kept": [int(n) for n in keep.sum(1).tolist()],
+                   "kept_idx": [torch.nonzero(keep[g]).flatten() for g in range(H)]}
         if folds is not None:
             K, blk = int(folds), 1 if block is None else int(block)
             if K < 2 or blk < 1:
@@ -560,10 +597,11 @@ class BrainHead:
             self._ridge = {"G": torch.zeros(H, K, E, E, dtype=f64, device=d), "C": torch.zeros(H, K, V, E, dtype=f64, device=d),
                            "sz": torch.zeros(H, K, E, dtype=f64, device=d), "sy": torch.zeros(H, K, V, dtype=f64, device=d),
                            "syy": torch.zeros(H, K, V, dtype=f64, device=d), "n": [0] * H, "n_fold": [[0] * K for _ in range(H)],
-                           "folds": K, "block": blk}
+                           "folds": K, "block": blk, **wst}
             return
         self._ridge = {"G": torch.zeros(H, E, E, dtype=f64, device=d), "C": torch.zeros(H, V, E, dtype=f64, device=d),
-                       "sz": torch.zeros(H, E, dtype=f64, device=d), "sy": torch.zeros(H, V, dtype=f64, device=d), "n": [0] * H}
+                       "sz": torch.zeros(H, E, dtype=f64, device=d), "sy": torch.zeros(H, V, dtype=f64, device=d), "n": [0] * H,
+                       **wst}
 
     def ridge_stats_end(self):
         """Free the sums (and the last solve's workspaces)."""
@@ -619,6 +657,13 @@ class BrainHead:
     def _ridge_accumulate(self, st, at, cache, ids, y):
         """the sums at ``at`` (a head, or a (head, fold)) += the cached clips ``ids`` with targets ``y``"""
         z = self.features_cached(cache, ids)
+        if "tw" in st:          # weighted stats (§5.3.9): y through a select on the head's own weight row
+            g = at[0] if isinstance(at, tuple) else at
+            check(lib.vlb_ridge_gram_accumulate_masked(z.data_ptr(), y.data_ptr(), self.V, st["tw"][g].data_ptr(),
+                                                       st["G"][at].data_ptr(), st["C"][at].data_ptr(), st["sz"][at].data_ptr(),
+                                                       st["sy"][at].data_ptr(), ids.numel(), self.E, self.V, _stream()),
+                  "vlb_ridge_gram_accumulate_masked")
+            return
         check(lib.vlb_ridge_gram_accumulate(z.data_ptr(), y.data_ptr(), self.V, st["G"][at].data_ptr(), st["C"][at].data_ptr(),
                                             st["sz"][at].data_ptr(), st["sy"][at].data_ptr(), ids.numel(), self.E, self.V,
                                             _stream()), "vlb_ridge_gram_accumulate")
@@ -648,7 +693,9 @@ class BrainHead:
         first; a head without clips, a singular system (``l2_lambda`` 0 with n <= E) or a failed pivot (``info`` != 0) raises
         with the head and the pivot named and leaves every parameter as it was.  Otherwise the fp32 masters and their bf16
         copies are written.  The sums are only read: another ``l2_lambda`` solves again from them.  With folds active the
-        head's sums are its folds' added in ascending order."""
+        head's sums are its folds' added in ascending order.  With weighted stats the weighted objective is
+        minimised: per head and level one vlb_ridge_solve_rows with ``l2_lambda * scale`` writes that level's rows, masked rows
+        are exactly 0, and the dicts gain "kept" (targets with a positive weight) and "levels"."""
         st = getattr(self, "_ridge", None)
         if st is None:
             raise RuntimeError("head: ridge_solve() before ridge_stats_begin()")
@@ -665,16 +712,25 @@ class BrainHead:
                                  "centred Gram matrix is singular; set l2_lambda > 0")
         A = torch.empty(E, E, dtype=torch.float64, device=d)
         X = torch.empty(H, V, E, dtype=torch.float64, device=d)
-        W = torch.empty(H, V, E, dtype=torch.float32, device=d)
-        b = torch.empty(H, V, dtype=torch.float32, device=d)
-        info = torch.zeros(H, dtype=torch.int32, device=d)
-        for g in range(H):
+        wt = "tw" in st         # weighted stats (§5.3.9): one row-select solve per (head, level) into zeroed scratch
+        jobs = [(g, lv) for g in range(H) for lv in range(len(st["scale"][g]))] if wt else [(g, None) for g in range(H)]
+        W = (torch.zeros if wt else torch.empty)(H, V, E, dtype=torch.float32, device=d)
+        b = (torch.zeros if wt else torch.empty)(H, V, dtype=torch.float32, device=d)
+        info = torch.zeros(len(jobs), dtype=torch.int32, device=d)
+        for j, (g, lv) in enumerate(jobs):
             Gs, Cs, szs, sys_ = self._head_totals(st, g)
-            check(lib.vlb_ridge_solve(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(),
-                                      st["n"][g], lam, A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(), b[g].data_ptr(),
-                                      info[g:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
-        infos = info.tolist()                           # the one device read of the solve
-        st["X"] = X                                     # the fp64 solutions, for inspection
+            if lv is None:
+                check(lib.vlb_ridge_solve(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(),
+                                          st["n"][g], lam, A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(), b[g].data_ptr(),
+                                          info[g:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
+            else:
+                check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g],
+                                               lam * st["scale"][g][lv], A.data_ptr(), X[g].data_ptr(), W[g].data_ptr(),
+                                               b[g].data_ptr(), info[j:].data_ptr(), E, V, st["lvl"][g].data_ptr(), lv, _stream()),
+                      "vlb_ridge_solve_rows")
+        by_job = info.tolist()                          # the one device read of the solve
+        infos = [next((v for (gg, _), v in zip(jobs, by_job) if gg == g and v), 0) for g in range(H)]
+        st["X"] = X                                     # the fp64 solutions, for inspection (weighted: the last level's)
         for g in range(H):
             if infos[g] < 0:
                 raise ValueError(f"head: ridge_solve: {name(g)}: target column {-infos[g] - 1} holds a NaN or Inf (info = "
@@ -683,8 +739,12 @@ class BrainHead:
                 raise ValueError(f"head: ridge_solve: {name(g)}: pivot {infos[g]} of {E} is not positive (info = {infos[g]}, "
                                  f"N = {st['n'][g]}, l2_lambda = {lam}): a larger l2_lambda, or NaN in the targets")
         self._write_ridge(W, b)
-        return [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": infos[g], "l2_lambda": lam}
-                for g in range(H)]
+        out = [{"subject": self.subjects[g] if self.G else None, "n": st["n"][g], "info": infos[g], "l2_lambda": lam}
+               for g in range(H)]
+        if wt:
+            for g in range(H):
+                out[g].update(kept=st["kept"][g], levels=len(st["scale"][g]))
+        return out
 
     # ------------------------------------------------------------------ l2_lambda by blocked K-fold CV (ridge_lambda_grid)
     # DESIGN §5.3.6.  ridge_stats_begin(folds=K, block=b) keeps the sums per (head, fold); ridge_cv(grid) solves every fold's
@@ -702,8 +762,13 @@ class BrainHead:
                     continue
                 yk = yy if mk == m else yy.index_select(0, sel.to(yy.device)).contiguous()
                 self._ridge_accumulate(st, (g, k), cache, ids[sel], yk)
-                check(lib.vlb_ridge_sumsq_accumulate(yk.data_ptr(), self.V, st["syy"][g, k].data_ptr(), mk, self.V, _stream()),
-                      "vlb_ridge_sumsq_accumulate")
+                if "tw" in st:
+                    check(lib.vlb_ridge_sumsq_accumulate_masked(yk.data_ptr(), self.V, st["tw"][g].data_ptr(),
+                                                                st["syy"][g, k].data_ptr(), mk, self.V, _stream()),
+                          "vlb_ridge_sumsq_accumulate_masked")
+                else:
+                    check(lib.vlb_ridge_sumsq_accumulate(yk.data_ptr(), self.V, st["syy"][g, k].data_ptr(), mk, self.V, _stream()),
+                          "vlb_ridge_sumsq_accumulate")
                 st["n_fold"][g][k] += mk
             st["n"][g] += m
 
@@ -734,7 +799,11 @@ class BrainHead:
         the same exclusions, a tie to the larger lambda) and adds "choice" [H,V] (device int32), "lambda_rows" [H,V] (device
         fp32, grid[choice]), "lambda_counts" [H][L] (one more device read) and "score_per_target", the mean over heads and
         targets of the winning fold-mean r - selected on the same folds it is scored on, so optimistic; everything else,
-        "best_index" and "best_lambda" included, is what the call returns without it."""
+        "best_index" and "best_lambda" included, is what the call returns without it.
+        With weighted stats every grid point is solved once per level with ``grid[i] * scale`` and scored into
+        that level's targets (vlb_ridge_cv_score_rows); masked targets stay NaN in the table, every mean over targets is the plain
+        mean over the kept ones, "infos" holds the first non-zero over the levels, and ``per_target`` chooses for kept targets
+        only ("choice" -1 and "lambda_rows" = best_lambda at masked ones, "lambda_counts" counts kept targets)."""
         import warnings
         st = getattr(self, "_ridge", None)
         if st is None or "folds" not in st:
@@ -758,7 +827,9 @@ class BrainHead:
         vy = torch.empty(V, dtype=f64, device=d)
         ws = torch.empty(lib.vlb_ridge_cv_ws_doubles(E, V), dtype=f64, device=d)
         table = torch.full((H, K, L, V), float("nan"), dtype=f64, device=d)
-        info = torch.zeros(H, K, L, dtype=torch.int32, device=d)
+        wt = "tw" in st         # weighted stats (§5.3.9): per level one solve and a row-select score; masked targets stay NaN
+        D = max(len(s) for s in st["scale"]) if wt else 1
+        info = torch.zeros(H, K, L, D, dtype=torch.int32, device=d) if wt else torch.zeros(H, K, L, dtype=torch.int32, device=d)
         for g in range(H):
             for k in range(K):
                 nk = st["n_fold"][g][k]
@@ -767,6 +838,16 @@ class BrainHead:
                                               st["sy"][g, k].data_ptr(), st["syy"][g, k].data_ptr(), nk, Gc.data_ptr(), Rc.data_ptr(),
                                               vy.data_ptr(), E, V, _stream()), "vlb_ridge_cv_center")
                 for i, lam in enumerate(grid):
+                    if wt:
+                        for lv, scale in enumerate(st["scale"][g]):
+                            check(lib.vlb_ridge_solve(Tg.data_ptr(), Tc.data_ptr(), Tsz.data_ptr(), Tsy.data_ptr(), st["n"][g] - nk,
+                                                      lam * scale, A.data_ptr(), X.data_ptr(), W.data_ptr(), b.data_ptr(),
+                                                      info[g, k, i, lv:].data_ptr(), E, V, _stream()), "vlb_ridge_solve")
+                            check(lib.vlb_ridge_cv_score_rows(X.data_ptr(), Gc.data_ptr(), Rc.data_ptr(), vy.data_ptr(),
+                                                              ws.data_ptr(), table[g, k, i].data_ptr(),
+                                                              info[g, k, i, lv:].data_ptr(), E, V, st["lvl"][g].data_ptr(), lv,
+                                                              _stream()), "vlb_ridge_cv_score_rows")
+                        continue
                     check(lib.vlb_ridge_solve(Tg.data_ptr(), Tc.data_ptr(), Tsz.data_ptr(), Tsy.data_ptr(), st["n"][g] - nk, lam,
                                               A.data_ptr(), X.data_ptr(), W.data_ptr(), b.data_ptr(), info[g, k, i:].data_ptr(), E, V,
                                               _stream()), "vlb_ridge_solve")
@@ -774,7 +855,12 @@ class BrainHead:
                                                  table[g, k, i].data_ptr(), info[g, k, i:].data_ptr(), E, V, _stream()),
                           "vlb_ridge_cv_score")
         infos = info.cpu()                              # the two device reads of the sweep
-        means = table.mean(-1).cpu()                    # [H,K,L]; NaN where the solve failed
+        if wt:      # [H,K,L]: the first non-zero over the levels; a level that failed leaves its targets NaN, so the mean is NaN
+            first = (infos != 0).to(torch.int64).argmax(-1, keepdim=True)
+            infos = infos.gather(-1, first).squeeze(-1)
+            means = torch.stack([table[g].index_select(-1, st["kept_idx"][g]).mean(-1) for g in range(H)]).cpu()     # kept targets
+        else:
+            means = table.mean(-1).cpu()                # [H,K,L]; NaN where the solve failed
         ok = [not bool(infos[:, :, i].any()) for i in range(L)]
         for i in range(L):
             if not ok[i]:
@@ -799,11 +885,22 @@ class BrainHead:
             for g in range(H):
                 check(lib.vlb_ridge_cv_select(table[g].data_ptr(), grid_d.data_ptr(), ok_d.data_ptr(), rmean[g].data_ptr(),
                                               choice[g].data_ptr(), rbest[g].data_ptr(), K, L, V, _stream()), "vlb_ridge_cv_select")
-            idx = choice.to(torch.int64)
-            counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx))
-            packed = torch.cat([counts.to(f64).flatten(), rbest.mean().reshape(1)]).cpu()       # the one device read
+            if wt:      # the choice is made for kept targets only: a masked one gets -1 / NaN and best_lambda in lambda_rows
+                keep = st["keep"]
+                choice = torch.where(keep, choice, torch.full_like(choice, -1))
+                rbest = torch.where(keep, rbest, torch.full_like(rbest, float("nan")))
+                idx = choice.to(torch.int64).clamp_(min=0)
+                counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, keep.to(torch.int64))
+                packed = torch.cat([counts.to(f64).flatten(), rbest[keep].mean().reshape(1)]).cpu()  # the one device read
+                lam_rows = torch.where(keep, grid_d.to(torch.float32)[idx],
+                                       torch.full((), grid[best], dtype=f64, device=d).to(torch.float32))
+            else:
+                idx = choice.to(torch.int64)
+                counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx))
+                packed = torch.cat([counts.to(f64).flatten(), rbest.mean().reshape(1)]).cpu()       # the one device read
+                lam_rows = grid_d.to(torch.float32)[idx]
             st["cv_rmean"] = rmean                      # [H,L,V], for inspection
-            out.update(choice=choice, lambda_rows=grid_d.to(torch.float32)[idx], score_per_target=float(packed[-1]),
+            out.update(choice=choice, lambda_rows=lam_rows, score_per_target=float(packed[-1]),
                        lambda_counts=[[int(c) for c in row] for row in packed[:-1].reshape(H, L)])
         return out
 
@@ -813,7 +910,9 @@ class BrainHead:
         head chose, the head's totals are solved once with that lambda (vlb_ridge_solve_rows) and the rows that chose it are
         written into scratch; the infos are read once; a failed solve raises with the head, the grid point and the pivot named
         and leaves every parameter as it was.  Otherwise the fp32 masters and their bf16 copies are written as ``ridge_solve``
-        writes them.  -> ``ridge_solve``'s list with "lambda_counts" [L] in place of "l2_lambda"."""
+        writes them.  -> ``ridge_solve``'s list with "lambda_counts" [L] in place of "l2_lambda".
+        With weighted stats ``choice`` may hold -1 at masked targets only; a kept target's code is
+        choice * D + level, every used (grid point, level) is solved once with ``grid[i] * scale`` and masked rows are 0."""
         st = getattr(self, "_ridge", None)
         if st is None:
             raise RuntimeError("head: ridge_solve_rows() before ridge_stats_begin()")
@@ -828,20 +927,45 @@ class BrainHead:
             if st["n"][g] == 0:
                 raise ValueError(f"head: ridge_solve_rows: {name(g)} has no clips (N = 0): nothing to fit it to")
         idx = choice.to(torch.int64)
-        if bool(((idx < 0) | (idx >= L)).any()):
-            raise ValueError(f"head: ridge_solve_rows: choice holds an index outside [0, {L})")
-        counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx)).tolist()
         A = torch.empty(E, E, dtype=torch.float64, device=d)
         X = torch.empty(V, E, dtype=torch.float64, device=d)
-        W = torch.empty(H, V, E, dtype=torch.float32, device=d)
-        b = torch.empty(H, V, dtype=torch.float32, device=d)
-        used = [(g, i) for g in range(H) for i in range(L) if counts[g][i]]
-        info = torch.zeros(len(used), dtype=torch.int32, device=d)
-        for j, (g, i) in enumerate(used):
-            Gs, Cs, szs, sys_ = self._head_totals(st, g)
-            check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g], grid[i],
-                                           A.data_ptr(), X.data_ptr(), W[g].data_ptr(), b[g].data_ptr(), info[j:].data_ptr(), E, V,
-                                           choice[g].data_ptr(), i, _stream()), "vlb_ridge_solve_rows")
+        if "tw" in st:
+            # weighted stats (§5.3.9): -1 at masked targets only; a kept target's code is choice * D + level, each used
+            # (grid point, level) is solved once with grid[i] * scale and writes its rows into zeroed scratch
+            keep, Dh = st["keep"], [len(s) for s in st["scale"]]
+            if bool((keep & ((idx < 0) | (idx >= L))).any()) or bool((~keep & ((idx < -1) | (idx >= L))).any()):
+                raise ValueError(f"head: ridge_solve_rows: choice holds an index outside [0, {L}) at a target with a positive "
+                                 "weight (-1 is taken at masked targets only)")
+            Dd = torch.tensor(Dh, dtype=torch.int32, device=d)[:, None]
+            code = torch.where(keep, choice * Dd + st["lvl"], torch.full_like(choice, -1)).contiguous()
+            Dmax = max(Dh)
+            per = torch.zeros(H, L * Dmax + 1, dtype=torch.int64, device=d).scatter_add_(
+                1, (code.to(torch.int64) + 1), torch.ones_like(idx))[:, 1:].tolist()
+            counts = [[sum(per[g][i * Dh[g]:(i + 1) * Dh[g]]) for i in range(L)] for g in range(H)]
+            used = [(g, i, lv) for g in range(H) for i in range(L) for lv in range(Dh[g]) if per[g][i * Dh[g] + lv]]
+            W = torch.zeros(H, V, E, dtype=torch.float32, device=d)
+            b = torch.zeros(H, V, dtype=torch.float32, device=d)
+            info = torch.zeros(len(used), dtype=torch.int32, device=d)
+            for j, (g, i, lv) in enumerate(used):
+                Gs, Cs, szs, sys_ = self._head_totals(st, g)
+                check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g],
+                                               grid[i] * st["scale"][g][lv], A.data_ptr(), X.data_ptr(), W[g].data_ptr(),
+                                               b[g].data_ptr(), info[j:].data_ptr(), E, V, code[g].data_ptr(), i * Dh[g] + lv,
+                                               _stream()), "vlb_ridge_solve_rows")
+            used = [(g, i) for g, i, _ in used]
+        else:
+            if bool(((idx < 0) | (idx >= L)).any()):
+                raise ValueError(f"head: ridge_solve_rows: choice holds an index outside [0, {L})")
+            counts = torch.zeros(H, L, dtype=torch.int64, device=d).scatter_add_(1, idx, torch.ones_like(idx)).tolist()
+            W = torch.empty(H, V, E, dtype=torch.float32, device=d)
+            b = torch.empty(H, V, dtype=torch.float32, device=d)
+            used = [(g, i) for g in range(H) for i in range(L) if counts[g][i]]
+            info = torch.zeros(len(used), dtype=torch.int32, device=d)
+            for j, (g, i) in enumerate(used):
+                Gs, Cs, szs, sys_ = self._head_totals(st, g)
+                check(lib.vlb_ridge_solve_rows(Gs.data_ptr(), Cs.data_ptr(), szs.data_ptr(), sys_.data_ptr(), st["n"][g], grid[i],
+                                               A.data_ptr(), X.data_ptr(), W[g].data_ptr(), b[g].data_ptr(), info[j:].data_ptr(), E, V,
+                                               choice[g].data_ptr(), i, _stream()), "vlb_ridge_solve_rows")
         infos = info.tolist()                           # the one device read of the solves
         for j, (g, i) in enumerate(used):
             if infos[j] < 0:

@@ -25,7 +25,7 @@ import torch
 from . import ops
 from .backbone import Backbone, Weights, destack_decoder_layer
 from .geometry import Geometry, geometry_7b, geometry_mini
-from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers, check_subjects
+from .head import HEAD_PARAMS, LAYER_MIX, BrainHead, check_loss, check_readout_layers, check_subjects, target_weight_levels
 from .optim import FULLFT_EMA_MESSAGE, VlbAdamW
 from .optim_groups import assign_groups, group_specs, normalize_optimizer_groups
 
@@ -192,6 +192,11 @@ class VLBLitModuleConfig:
     # weight is solved with its own l2_lambda and every later step's penalty is sum_v lambda_v ||W_v||^2;
     # head.l2_lambda keeps the one global choice, for reporting.  False: one l2_lambda for the whole head
     ridge_lambda_per_target: bool = False
+    # ridge_fit="closed_form" only.  True: the fit and its cross-validation accept ``target_weights`` / ``set_target_weights``
+    # and minimise the weighted objective of DESIGN §5.3.8 in closed form (§5.3.9): masked targets (weight 0, NaN allowed in
+    # the data) reach no sum and get W_v = 0, b_v = 0; a head may hold at most 8 distinct positive weights (one factorisation
+    # each).  Without weights it changes nothing.  False: weights and the closed-form fit refuse each other
+    ridge_fit_weighted: bool = False
     # learning rate / weight decay per group of trainables: up to 7 entries {params: [fnmatch pattern, ...],
     # lr_scale: float = 1.0, weight_decay: float | None = None} over the names trainable_named_parameters() yields; the first
     # entry with a matching pattern takes a tensor, what no entry matches keeps lr / weight_decay; lr_scale multiplies lr (the
@@ -252,6 +257,11 @@ class VLBLitModuleConfig:
         if self.ridge_lambda_per_target and self.ridge_lambda_grid is None:
             raise ValueError("ridge_lambda_per_target=True chooses each target's l2_lambda from ridge_lambda_grid: set "
                              "ridge_lambda_grid (or leave ridge_lambda_per_target unset)")
+        if not isinstance(self.ridge_fit_weighted, bool):
+            raise ValueError(f"ridge_fit_weighted={self.ridge_fit_weighted!r}: true or false is needed")
+        if self.ridge_fit_weighted and self.ridge_fit != "closed_form":
+            raise ValueError("ridge_fit_weighted=True is the closed-form fit under target weights: set ridge_fit='closed_form' "
+                             "(or leave ridge_fit_weighted unset)")
         self.optimizer_groups = normalize_optimizer_groups(self.optimizer_groups)      # names are checked by configure_optimizers
         if self.ema_decay is not None:
             d = self.ema_decay
@@ -273,10 +283,11 @@ class VLBLitModuleConfig:
             if "{subject}" in tw and self.subjects is None:
                 raise ValueError(f"target_weights={tw!r} holds {{subject}} but `subjects` is unset: one subject takes one file "
                                  "of [num_target] weights")
-            if self.ridge_fit is not None:
-                raise ValueError("target_weights with ridge_fit='closed_form' is not supported: the closed-form fit and its "
-                                 "cross-validation take every target alike (a mask would need NaN-tolerant Gram columns, "
-                                 "general weights one factorisation per distinct weight); unset one of the two")
+            if self.ridge_fit is not None and not self.ridge_fit_weighted:
+                raise ValueError("target_weights with ridge_fit='closed_form' needs ridge_fit_weighted=True: without it the "
+                                 "closed-form fit and its cross-validation take every target alike (a mask needs NaN-tolerant "
+                                 "Gram columns, general weights one factorisation per distinct weight); set "
+                                 "ridge_fit_weighted=True or unset one of the two")
         if self.readout_layers is not None:
             if not self.freeze_backbone and not self.use_lora:
                 raise ValueError("readout_layers with the full fine-tune (freeze_backbone=False, use_lora=False) is not supported: "
@@ -459,11 +470,20 @@ class VLBLitModule(_Base):
     # ------------------------------------------------------------------ per-target loss weights and masks
     def set_target_weights(self, tw) -> None:
         """``tw``: [num_target], or [G, num_target] with ``subjects`` (a tensor on any device, or anything torch.as_tensor takes);
-        None: no weights.  Goes to ``BrainHead.set_target_weights`` (which checks it) and into checkpoints."""
-        if tw is not None and getattr(self.config, "ridge_fit", None) is not None:
-            raise ValueError("set_target_weights with ridge_fit='closed_form' is not supported: the closed-form fit takes every "
-                             "target alike")
+        None: no weights.  Goes to ``BrainHead.set_target_weights`` (which checks it) and into checkpoints.  With
+        ``ridge_fit_weighted`` the closed-form fit takes the weights in force when it runs and a head may hold at
+        most 8 distinct positive ones; weights set after a completed fit do not refit: the parameters stay the minimiser of the
+        objective they were fitted to and only the steps and scores from then on use the new weights."""
+        weighted_fit = bool(getattr(self.config, "ridge_fit_weighted", False))
+        if tw is not None and getattr(self.config, "ridge_fit", None) is not None and not weighted_fit:
+            raise ValueError("set_target_weights with ridge_fit='closed_form' needs ridge_fit_weighted=True: without it the "
+                             "closed-form fit takes every target alike")
         t = None if tw is None else torch.as_tensor(tw).detach().to("cpu", torch.float32).clone()
+        if t is not None and weighted_fit and t.dim() in (1, 2) and bool((torch.isfinite(t) & (t >= 0)).all()):
+            subs = getattr(self.config, "subjects", None)       # more than 8 levels: refused here, before epoch 1
+            target_weight_levels(t.reshape(-1, t.shape[-1]),
+                                 (lambda g: f"head {g} ({subs[g]!r})") if subs is not None and t.dim() == 2 and t.shape[0] > 1
+                                 else (lambda g: "the head"))
         head = getattr(self, "head", None)
         if head is not None:
             head.set_target_weights(None if t is None else t.to(head.dev))
@@ -812,7 +832,10 @@ class VLBLitModule(_Base):
         With ``ridge_lambda_per_target`` as well, ``ridge_cv(grid, per_target=True)`` chooses per (head, target),
         ``ridge_solve_rows`` solves each row with its own l2_lambda and ``head.set_l2_lambda_rows`` puts the vector in force
         (DESIGN §5.3.7); ``ridge_fit/cv_score_per_target`` and ``/lambda_count_<i>`` are logged too.  An explicit
-        ``l2_lambda`` skips the grid and clears the vector."""
+        ``l2_lambda`` skips the grid and clears the vector.
+        With ``ridge_fit_weighted`` and target weights set the same walk and the same calls minimise the
+        weighted objective (NaN in a masked target is ignored); ``train_mse_before`` / ``_after`` are then its weighted data
+        term and ``ridge_fit/kept_targets`` and ``/weight_levels`` (summed over heads) are logged too."""
         cfg = self.config
         if not cfg.cache_features or cfg.loss != "mse":
             raise ValueError("fit_ridge_closed_form needs cache_features=True and loss='mse'")
@@ -833,10 +856,13 @@ class VLBLitModule(_Base):
         # ridge_lambda_grid (and no explicit l2_lambda): the same one walk keeps the sums per fold, ridge_cv chooses (§5.3.6)
         grid = cfg.ridge_lambda_grid if l2_lambda is None else None
         try:
+            weighted = bool(getattr(cfg, "ridge_fit_weighted", False))
             if grid is not None:
-                self.head.ridge_stats_begin(folds=cfg.ridge_cv_folds, block=cfg.ridge_cv_block)
+                self.head.ridge_stats_begin(folds=cfg.ridge_cv_folds, block=cfg.ridge_cv_block, weighted=weighted)
             else:
-                self.head.ridge_stats_begin()
+                self.head.ridge_stats_begin(weighted=weighted)
+            wst = self.head._ridge if "tw" in self.head._ridge else None         # the weights this fit takes (§5.3.9)
+            kept_levels = None if wst is None else (float(sum(wst["kept"])), float(sum(len(s) for s in wst["scale"])))
             for lo in range(0, len(ds), chunk):
                 items = [ds[i] for i in range(lo, min(lo + chunk, len(ds)))]
                 batch = {k: torch.stack([torch.as_tensor(it[k]) for it in items]) for k in items[0]}
@@ -875,6 +901,9 @@ class VLBLitModule(_Base):
         self.log("ridge_fit/l2_lambda", float(out[0]["l2_lambda"]) if "l2_lambda" in out[0] else float(cv["best_lambda"]))
         self.log("ridge_fit/train_mse_before", mse[0])
         self.log("ridge_fit/train_mse_after", mse[1])
+        if kept_levels is not None:
+            self.log("ridge_fit/kept_targets", kept_levels[0])
+            self.log("ridge_fit/weight_levels", kept_levels[1])
         if cv is not None:
             self.log("ridge_fit/cv_score", float(cv["score"][cv["best_index"]]))
             for i, s in enumerate(cv["score"]):
