@@ -112,6 +112,10 @@ __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.f + 
 // row = &C[m][0], n = the column of this lane's piece of fragment j (16-byte aligned for even fq).
 // MX (OCP microscaling) block quantisation helpers shared by gemm_fp8.hip and the producer kernels that emit fp8 next to bf16:
 // shared exponent of a 32-element block = ceil(log2(amax / 448)) clamped to [-127, 127]; scale byte = E + 127.
+// Non-finite inputs: a NaN or Inf element never becomes a finite fp8 value - its byte is 0x7F / 0xFF (fmaxf drops a NaN from
+// amax; Inf times any power of two, or times zero, stays non-finite; v_cvt_pk_fp8_f32 turns NaN and Inf into the NaN code,
+// e4m3 having no Inf); the scale byte and the finite neighbours of that block are unspecified, every other block is
+// unaffected (tests/test_gpu_mx_quant.py).
 __device__ __forceinline__ int mx_shared_exp(float amax) {
   int E = -127;
   if (amax > 0.f) {
