@@ -12,6 +12,9 @@ equals the reference bit for bit on every route, and one missing, repeated or mi
   * ``device_pre`` + ``confirm_rows``: the same pre-activation from torch's fp32 matmul on the device (exact for the same
     reason), confirmed against CPU fp64 on ``row_subsample``
   * ``assert_bits_equal`` (with the 256 cap) and ``assert_within_ulp`` (non-linear epilogues only)
+  * the fractional grid (``grid_scale`` / ``grid_operands`` / ``grid_gate_up`` / ``assert_grid_case``): ternary A, ternary
+    W times a power of two, bias and residual on multiples of 1/8 - still exact in fp32 in any order, but with the
+    pre-activations where the activations bend (|x| <= 4) instead of in saturation
 """
 from __future__ import annotations
 
@@ -95,6 +98,60 @@ def residual_ints(M, N, seed, device=None):
 def gate_up_ints(M, ff2, seed, device=None):
     """Saved [gate | up] pre-activations in [-3, 3]."""
     return small_ints((M, ff2), -3, 3, seed, device)
+
+
+# ------------------------------------------------------------------ the fractional grid
+GRID_SD = 1.4          # target standard deviation of a grid pre-activation (before the bias)
+GRID_X = 4.0           # the range in which quick_gelu / gelu / silu differ from their asymptotes and from each other
+GRID_SHARE = 0.90      # a grid case with a smaller share of its pre-activations in |x| <= GRID_X is refused
+
+
+def grid_scale(K, K2=0):
+    """The largest power of two s with s * sqrt(4 (K + K2) / 9) <= GRID_SD: a sum of K + K2 products of two ternary
+    operands has variance 4 (K + K2) / 9, so s times it has a standard deviation in (GRID_SD / 2, GRID_SD]."""
+    sd = (4.0 * (K + K2) / 9.0) ** 0.5
+    s = 1.0
+    while s * sd > GRID_SD:
+        s /= 2
+    while 2 * s * sd <= GRID_SD:
+        s *= 2
+    return s
+
+
+def eighths(shape, lo, hi, seed, device=None):
+    """Uniform multiples of 1/8 in [lo, hi] (bf16 holds them exactly up to 16)."""
+    return (small_ints(shape, int(8 * lo), int(8 * hi), seed, device, dtype=torch.float32) / 8).to(BF16)
+
+
+def grid_operands(M, N, K, K2, seed, device=None):
+    """(a, w, a2, w2, bias, residual) for act(A.W^T + A2.W2^T + bias) + residual on a fractional grid: A / A2 ternary,
+    W / W2 ternary times ``grid_scale(K, K2)``, bias multiples of 1/8 in [-1, 1], residual multiples of 1/8 in [-4, 4].
+    Every product and partial sum is a multiple of s below (K + K2) s, far below 2^24 s: fp32 accumulation is exact in
+    any order (split-K included), adding the bias (a multiple of min(s, 1/8)) is exact too, and the pre-activation is
+    known exactly.  a2 / w2 are None when K2 == 0.  Seeds: seed .. seed + 5, as the integer cases draw them."""
+    s = grid_scale(K, K2)
+    a, w = ternary((M, K), seed, device), (ternary((N, K), seed + 1, device).float() * s).to(BF16)
+    a2 = w2 = None
+    if K2:
+        a2, w2 = ternary((M, K2), seed + 2, device), (ternary((N, K2), seed + 3, device).float() * s).to(BF16)
+    return a, w, a2, w2, eighths(N, -1, 1, seed + 4, device), eighths((M, N), -4, 4, seed + 5, device)
+
+
+def grid_gate_up(M, ff2, seed, device=None):
+    """Saved [gate | up] pre-activations on multiples of 1/8 in [-4, 4]."""
+    return eighths((M, ff2), -4, 4, seed, device)
+
+
+def grid_share(x):
+    """Share of pre-activations with |x| <= GRID_X."""
+    return float((x.abs() <= GRID_X).double().mean())
+
+
+def assert_grid_case(x):
+    """Refuses a grid case whose pre-activations ``x`` do not sample the activation where it bends: a condition on the
+    inputs (like the 256 cap of ``assert_bits_equal``), never on what a kernel returned."""
+    share = grid_share(x)
+    assert share >= GRID_SHARE, f"case refused: only {100 * share:.1f} % of the pre-activations lie in |x| <= {GRID_X:.0f}"
 
 
 # ------------------------------------------------------------------ references
@@ -228,21 +285,38 @@ def assert_bits_equal(got, ref64, cap=True):
     raise AssertionError("not bit-equal: " + _describe(got, want, bad))
 
 
-def ulp_bar(ref64, x):
-    """|got - ref| <= 2^-8 |ref| + 2^-20 (1 + |x|): one bf16 rounding (half an ulp is at most 2^-8 |ref|, including the flip
-    to the neighbour when the fp32 value sits next to a tie) plus the fp32 evaluation of exp / erf at pre-activation x."""
-    return 2.0 ** -8 * ref64.abs() + 2.0 ** -20 * (1 + x.abs())
+def ulp_bar(ref64, x, gain=1.0):
+    """|got - ref| <= 2^-8 |ref| + 2^-20 (1 + |x|) gain: one bf16 rounding (half an ulp is at most 2^-8 |ref|, including the
+    flip to the neighbour when the fp32 value sits next to a tie) plus the fp32 evaluation of exp / erf at pre-activation x.
+
+    The second term is an ABSOLUTE bound on the error of act(x): with u = 2^-24 the kernels' sigmoid (``__expf`` then
+    ``__builtin_amdgcn_rcpf``: an ulp each, a rounding of 1 + e, and |x| u from rounding the exponent's argument) is within
+    (3 + |x|) u relative, so x * sigmoid(x) is within |x| (3 + |x|) u <= 16 (1 + |x|) u = 2^-20 (1 + |x|) for |x| <= 14
+    (quick_gelu's argument 1.702 x: |x| (3.5 + 1.702 |x|) u, for |x| <= 8; erf GELU: 0.5 x (1 + erff) with erff and the
+    roundings a few u absolute, |x| times a few u).
+
+    ``gain`` (default 1: nothing changes) is for epilogues that MULTIPLY the activation by something after evaluating it; it
+    is what the absolute error of the activation is multiplied by, derived from the epilogue's formula and never from
+    kernel output:
+      * SwiGLU h = silu(g) * up, x = g:  gain = max(1, |up|).
+      * SwiGLU backward, x = d_h:  d up = d_h * (g s) and d gate = d_h * up * F, F = s (1 + g (1 - s)), s = sigmoid(g).  With
+        delta_s <= s (3 + |g|) u:  delta(g s) <= (|g| (3 + |g|) + 2) u and delta_F <= ((3 + |g|) (1.1 + |g|) + 2) u (the error
+        of s enters 1 - s absolutely and is multiplied by g); both are <= 16 (1 + |g|) u for |g| <= 12.  So gain =
+        1 + |g| for d up and (1 + |g|) max(1, |up|) for d gate."""
+    return 2.0 ** -8 * ref64.abs() + 2.0 ** -20 * (1 + x.abs()) * gain
 
 
-def assert_within_ulp(got, ref64, x):
-    """For the non-linear epilogues: ``x`` is the exact (integer) pre-activation, ``ref64`` the fp64 value of the epilogue on
-    it; only the activation is inexact.  Element-wise, derived bar (``ulp_bar``)."""
+def assert_within_ulp(got, ref64, x, gain=1.0):
+    """For the non-linear epilogues: ``x`` is the exact pre-activation, ``ref64`` the fp64 value of the epilogue on it; only
+    the activation is inexact.  Element-wise, derived bar (``ulp_bar``; ``gain``: see there)."""
     assert tuple(got.shape) == tuple(ref64.shape) == tuple(x.shape), (tuple(got.shape), tuple(ref64.shape), tuple(x.shape))
     dev = got.device
     ref64, x = ref64.to(dev).double(), x.to(dev).double()
+    if torch.is_tensor(gain):
+        gain = gain.to(dev).double()
     g = got.double()
     err = (g - ref64).abs()
-    bar = ulp_bar(ref64, x)
+    bar = ulp_bar(ref64, x, gain)
     bad = ~(err <= bar)                      # NaN fails
     if not bool(bad.any()):
         return

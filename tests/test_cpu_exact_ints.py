@@ -1,14 +1,20 @@
 """tests/exact_ints.py can detect what it claims to detect (no GPU): the 256 cap holds for every K the GPU file uses, one
 changed operand element or mask bit changes a reference bit, each planted reference-side bug makes assert_bits_equal
-raise, and the fp32-matmul reference of the large shapes equals the fp64 one."""
+raise, and the fp32-matmul reference of the large shapes equals the fp64 one.  For the fractional grid of
+tests/test_gpu_gemm_epilogues.py: the scale rule and the 90 % condition hold for every (K, K2) used there, a correct fp32
+epilogue stays within ulp_bar of the fp64 reference, and each planted epilogue bug leaves it."""
 import numpy as np
 import pytest
 import torch
 
 import exact_ints as E
 import test_gpu_exact_contractions as G
+import test_gpu_gemm_epilogues as P
 
 BF = torch.bfloat16
+# every (K, K2) a bf16-output case of either GPU file contracts over; cases without a bias only lower the magnitudes, and a
+# grid case is its integer case times a power of two (its [gate | up] is checked bit for bit under the same cap)
+ALL_K_K2 = sorted(set(G.ALL_K_K2) | set(P.INT_K_K2) | set(P.GRID_K_K2))
 
 
 def _bf(ref64):
@@ -25,7 +31,7 @@ def _sum_pmf(K):
     return np.fft.fftshift(np.fft.irfft(np.fft.rfft(p) ** K, n))
 
 
-@pytest.mark.parametrize("Ktot", sorted({k + k2 for k, k2 in G.ALL_K_K2}))
+@pytest.mark.parametrize("Ktot", sorted({k + k2 for k, k2 in ALL_K_K2}))
 def test_cap_holds_analytically(Ktot):
     """P(|sum of K + K2 ternary products| + 8 > 256) <= 1 %: bias and residual add at most 4 each."""
     pmf = _sum_pmf(Ktot)
@@ -36,7 +42,7 @@ def test_cap_holds_analytically(Ktot):
         assert 0.0005 < frac < 0.003          # sigma = 80: about 0.15 % (two-sided tail beyond 3.1 sigma)
 
 
-@pytest.mark.parametrize("K,K2", list(dict.fromkeys(sorted(G.ALL_K_K2, key=lambda t: (t[0] + t[1], t[1]))[-3:] + [(4096, 64)])))
+@pytest.mark.parametrize("K,K2", list(dict.fromkeys(sorted(ALL_K_K2, key=lambda t: (t[0] + t[1], t[1]))[-3:] + [(4096, 64)])))
 def test_cap_holds_on_generated_data(K, K2):
     """The generators themselves (not only the model of them): plain form with bias and residual, and the masked-pair form
     with 1/(1-p) = 2, at the largest K of the GPU file."""
@@ -220,3 +226,184 @@ def test_ulp_bar_accepts_one_rounding_and_rejects_two_ulps():
         E.assert_within_ulp(_bf(ref + 2 * ulp * (x == 37)), ref, x)
     with pytest.raises(AssertionError, match="outside the ulp bar"):
         E.assert_within_ulp(_bf(E.ACTS["silu"](x + (x == -3)) + res), ref, x)       # pre-activation off by one
+
+
+# ------------------------------------------------------------------ the fractional grid (tests/test_gpu_gemm_epilogues.py)
+GRID_K_K2 = sorted(set(P.GRID_K_K2) | {(64, 0), (128, 0), (4096, 0), (4096, 64), (14336, 64)})
+ACT32 = {                                                                  # the kernels' activations restated in fp32 torch
+    "quick_gelu": lambda v: v * torch.sigmoid(1.702 * v),
+    "gelu": lambda v: 0.5 * v * (1 + torch.erf(v * 0.70710678118654752)),
+    "silu": lambda v: v * torch.sigmoid(v),
+    "gelu_tanh": lambda v: 0.5 * v * (1 + torch.tanh(0.7978845608028654 * (v + 0.044715 * v ** 3))),
+}
+_grid_cache = {}
+
+
+def _grid(K, K2, M=256, N=256):
+    """(a, w, a2, w2, bias, res, exact fp64 pre-activation with the bias) - generated once per (K, K2), never modified."""
+    if (K, K2) not in _grid_cache:
+        ops_in = E.grid_operands(M, N, K, K2, 100 + K + 3 * K2)
+        _grid_cache[(K, K2)] = (*ops_in, E.exact_pre(*ops_in[:5]))
+    return _grid_cache[(K, K2)]
+
+
+def _epilogue32(pre64, bias, res, act, with_bias, with_res):
+    """(what a correct kernel returns, the fp64 reference, the exact pre-activation): bias add, activation and residual add
+    in fp32 on the exact accumulator, one rounding to bf16."""
+    x = pre64 if with_bias else pre64 - bias.double()[None, :]
+    v = (pre64 - bias.double()[None, :]).float()                           # the accumulator: exact in fp32
+    assert torch.equal(v.double(), pre64 - bias.double()[None, :])
+    if with_bias:
+        v = v + bias.float()[None, :]
+    v = ACT32[act](v)
+    ref = E.ACTS["gelu" if act == "gelu_tanh" else act](x)
+    if with_res:
+        v, ref = v + res.float(), ref + res.double()
+    return v.to(BF), ref, x
+
+
+@pytest.mark.parametrize("K,K2", GRID_K_K2)
+def test_grid_scale_rule_share_and_fp32_exactness(K, K2):
+    s = E.grid_scale(K, K2)
+    sd = (4 * (K + K2) / 9) ** 0.5
+    assert s == 2.0 ** round(np.log2(s)) and s * sd <= E.GRID_SD < 2 * s * sd
+    a, w, a2, w2, bias, res, pre = _grid(K, K2)
+    assert (a2 is None) == (K2 == 0)
+    assert set(a.unique().tolist()) == {-1.0, 0.0, 1.0} and set(w.unique().tolist()) == {-s, 0.0, s}
+    assert set(bias.unique().tolist()) <= {i / 8 for i in range(-8, 9)} and set(res.unique().tolist()) == {i / 8 for i in range(-32, 33)}
+    nb = pre - bias.double()[None, :]
+    for x in (pre, nb):
+        E.assert_grid_case(x)
+        assert E.grid_share(x) >= 0.99                                     # sd <= 1.4 (+ a bias of sd 0.6): |x| <= 4 is 2.6 sigma
+    assert 0.45 * E.GRID_SD < float(nb.std()) < 1.1 * E.GRID_SD
+    assert bool((nb / s == (nb / s).round()).all()) and E.cap_fraction(nb / s) <= E.CAP_FRACTION
+    pre32 = E.device_pre(a, w, a2, w2, bias)                               # torch's fp32 matmul, any blocking
+    assert pre32.dtype == torch.float32 and torch.equal(pre32.double(), pre)
+    E.confirm_rows(pre32, a, w, a2, w2, bias)
+
+
+def test_grid_scale_table():
+    assert [E.grid_scale(k) for k in (64, 128, 4096, 4160, 14400)] == [1 / 4, 1 / 8, 1 / 32, 1 / 32, 1 / 64]
+    assert E.grid_scale(4096, 64) == E.grid_scale(4160) and E.grid_scale(72) == 1 / 8 and E.grid_scale(1) == 2.0
+
+
+def test_grid_condition_refuses_saturated_pre_activations():
+    a, w = E.ternary((64, 4096), 1), E.ternary((64, 4096), 2)              # integer operands: sd 43
+    with pytest.raises(AssertionError, match="case refused"):
+        E.assert_grid_case(E.exact_pre(a, w))
+    x = torch.zeros(10, 10, dtype=torch.float64)
+    x.view(-1)[:10] = 5.0
+    E.assert_grid_case(x)                                                  # exactly 90 % inside
+    x.view(-1)[10] = -4.125
+    with pytest.raises(AssertionError, match="case refused"):
+        E.assert_grid_case(x)
+
+
+@pytest.mark.parametrize("with_bias,with_res", P.PRESENCES)
+@pytest.mark.parametrize("act", P.ACT_NAMES)
+@pytest.mark.parametrize("K,K2", GRID_K_K2)
+def test_correct_fp32_epilogue_is_within_the_bar_on_the_grid(K, K2, act, with_bias, with_res):
+    """The bar is held by the reference alone: worst |err| / bar is about 0.995 (a bf16 tie next to a power of two)."""
+    a, w, a2, w2, bias, res, pre = _grid(K, K2)
+    got, ref, x = _epilogue32(pre, bias, res, act, with_bias, with_res)
+    E.assert_within_ulp(got, ref, x)
+
+
+GRID_PLANTED = ["residual_dropped", "bias_dropped", "quick_gelu_for_silu", "gelu_for_quick_gelu", "tanh_gelu_for_erf_gelu",
+                "residual_row_shifted", "fragment_from_neighbour"]
+
+
+@pytest.mark.parametrize("K,K2", [(128, 0), (4096, 64)])
+@pytest.mark.parametrize("bug", GRID_PLANTED)
+def test_planted_epilogue_bugs_leave_the_bar(bug, K, K2):
+    """Each is what a subtly wrong epilogue would return on the grid; at least one element must leave the bar."""
+    a, w, a2, w2, bias, res, pre = _grid(K, K2)
+    act = {"gelu_for_quick_gelu": "quick_gelu", "tanh_gelu_for_erf_gelu": "gelu"}.get(bug, "silu")
+    true, ref, x = _epilogue32(pre, bias, res, act, True, True)
+    E.assert_within_ulp(true, ref, x)                                      # the correct epilogue passes
+    if bug == "residual_dropped":
+        wrong = _epilogue32(pre, bias, res, act, True, False)[0]
+    elif bug == "bias_dropped":
+        wrong = _epilogue32(pre, bias, res, act, False, True)[0]
+    elif bug == "quick_gelu_for_silu":
+        wrong = _epilogue32(pre, bias, res, "quick_gelu", True, True)[0]
+    elif bug == "gelu_for_quick_gelu":
+        wrong = _epilogue32(pre, bias, res, "gelu", True, True)[0]
+    elif bug == "tanh_gelu_for_erf_gelu":
+        wrong = _epilogue32(pre, bias, res, "gelu_tanh", True, True)[0]
+    elif bug == "residual_row_shifted":
+        wrong = _epilogue32(pre, bias, torch.roll(res, 1, dims=0), act, True, True)[0]
+    else:
+        wrong = true.clone()
+        wrong[:, 16:32] = true[:, 32:48]
+    with pytest.raises(AssertionError, match="outside the ulp bar") as info:
+        E.assert_within_ulp(wrong, ref, x)
+    assert "256x256 tile" in str(info.value)
+    if bug == "fragment_from_neighbour":
+        assert "tile cols 16..31" in str(info.value)
+
+
+def test_planted_residual_only_bugs_are_not_bit_equal():
+    """EPI_RESIDUAL on the integer operands: the residual read 16 columns off, or dropped on the last rows only."""
+    a, w, a2, w2, bias, res = _case(M=300, N=256)
+    pre = E.exact_pre(a, w, a2, w2)
+    true = pre + res.double()
+    E.assert_bits_equal(_bf(true), true)
+    shifted = res.double().clone()
+    shifted[:, 16:32] = res.double()[:, 0:16]                              # rp for rp + 16
+    tail = res.double().clone()
+    tail[256:] = 0                                                         # dropped on the tail tile
+    for wrong in (pre + shifted, pre + tail, pre):
+        with pytest.raises(AssertionError, match="not bit-equal"):
+            E.assert_bits_equal(_bf(wrong), true)
+
+
+def test_ulp_bar_gain_defaults_to_the_plain_bar():
+    ref, x = torch.linspace(-5, 5, 41, dtype=torch.float64)[None, :], torch.linspace(-9, 9, 41, dtype=torch.float64)[None, :]
+    assert torch.equal(E.ulp_bar(ref, x), E.ulp_bar(ref, x, 1.0))
+    assert torch.equal(E.ulp_bar(ref, x), 2.0 ** -8 * ref.abs() + 2.0 ** -20 * (1 + x.abs()))
+    assert torch.equal(E.ulp_bar(0 * ref, x, 3.0), 3.0 * E.ulp_bar(0 * ref, x))          # only the activation term scales
+    assert torch.equal(E.ulp_bar(ref, 0 * x, 1 + x.abs()), E.ulp_bar(ref, x))
+
+
+@pytest.mark.parametrize("K,K2", sorted({(c[3], c[4]) for c in P.SWIGLU_GRID}))
+def test_swiglu_product_on_the_grid_passes_and_planted_bugs_fail(K, K2):
+    """h = silu(gate) * up in fp32 with one rounding stays within the bar with gain max(1, |up|); up taken from the
+    neighbouring fragment, or a sigmoid for the SiLU, leaves it."""
+    M, ff, s = 256, 128, E.grid_scale(K, K2)
+    a, t = E.ternary((M, K), 1), E.ternary((M, K2), 2)
+    w, b = (E.ternary((2 * ff, K), 3).float() * s).to(BF), (E.ternary((2 * ff, K2), 4).float() * s).to(BF)
+    pre = E.exact_pre(a, w, t, b)
+    assert torch.equal(E.device_pre(a, w, t, b).double(), pre) and torch.equal(_bf(pre).double(), pre)
+    g, u = pre[:, :ff], pre[:, ff:]
+    E.assert_grid_case(g)
+    ref, gain = E.ACTS["silu"](g) * u, u.abs().clamp_min(1.0)
+    g32, u32 = g.float(), u.float()
+    E.assert_within_ulp((ACT32["silu"](g32) * u32).to(BF), ref, g, gain)
+    for wrong in (ACT32["silu"](g32) * torch.roll(u32, 16, dims=1), torch.sigmoid(g32) * u32):
+        with pytest.raises(AssertionError, match="outside the ulp bar"):
+            E.assert_within_ulp(wrong.to(BF), ref, g, gain)
+
+
+def test_swiglu_backward_on_the_grid_passes_and_planted_bugs_fail():
+    """[d gate | d up] in fp32 as the kernel spells it, one rounding each: within the bar with ulp_bar's gains at gate / up
+    on multiples of 1/8 in [-4, 4]; the SiLU derivative without its g (1 - s) term, or gate and up swapped, leaves it."""
+    M, ff = 300, 256
+    gu = E.grid_gate_up(M, 2 * ff, 5)
+    assert set(gu.unique().tolist()) == {i / 8 for i in range(-32, 33)}
+    dh = E.exact_pre(E.ternary((M, 4096), 1), E.ternary((ff, 4096), 2), E.ternary((M, 64), 3), E.ternary((ff, 64), 4),
+                     keep=E.keep_mask(9, M, ff, 0.5), pair_scale=2.0)
+    g, up = gu[:, :ff].double(), gu[:, ff:].double()
+    sg = torch.sigmoid(g)
+    ref = torch.cat([dh * up * sg * (1 + g * (1 - sg)), dh * g * sg], 1)
+    x = torch.cat([dh, dh], 1)
+    gain = torch.cat([(1 + g.abs()) * up.abs().clamp_min(1.0), 1 + g.abs()], 1)
+    v, g32, u32 = dh.float(), g.float(), up.float()
+    s32 = torch.sigmoid(g32)
+    got = torch.cat([(v * u32 * (s32 * (1 + g32 * (1 - s32)))).to(BF), (v * (g32 * s32)).to(BF)], 1)
+    E.assert_within_ulp(got, ref, x, gain)
+    no_term = torch.cat([(v * u32 * s32).to(BF), (v * (g32 * s32)).to(BF)], 1)
+    swapped = torch.cat([(v * g32 * (s32 * (1 + g32 * (1 - s32)))).to(BF), (v * (u32 * s32)).to(BF)], 1)
+    for wrong in (no_term, swapped):
+        with pytest.raises(AssertionError, match="outside the ulp bar"):
+            E.assert_within_ulp(wrong, ref, x, gain)

@@ -5,7 +5,10 @@ Operands are ternary, so fp32 accumulation is exact in any order and the outputs
 linear epilogues are checked with ``assert_bits_equal`` (no tolerance), the non-linear ones with the derived element-wise
 bar of ``assert_within_ulp``.  Every case names the route it is meant to enter and asserts the library's own decision
 first (``vlb_gemm_kernel_choice`` / ``vlb_gemm_plan``: encodings of plan_route, the planner the dispatch runs, with the
-alignment facts taken as met), so a planner change fails loudly instead of silently testing another kernel.  What the
+alignment facts taken as met), so a planner change fails loudly instead of silently testing another kernel.  Every plain
+route runs act NONE with all four (bias, residual) presences - the EPI_PLAIN, EPI_RESIDUAL and EPI_GENERIC + NONE nests of
+the four-wave and split-K reduce kernels; tests/test_gpu_gemm_epilogues.py holds the table of epilogue kinds against
+kernel instantiations and the activations on a fractional grid.  What the
 library does not export - pick_order's tile order and the facts plan_route takes from the call itself (the 16-byte-store
 rule, the pointer rules of the generic kernel) - is named next to the case that turns on it.
 
@@ -171,26 +174,42 @@ def _plain_operands(M, N, K, K2, dev, how=""):
 
 
 def _run_plain(dev, a, w, a2, w2, bias, res, pre, how="", act_silu=True):
-    """act NONE with integer bias and residual: bit-equal.  act SILU: within the ulp bar of silu(exact integers) + residual."""
+    """act NONE with integer bias and residual: bit-equal.  act SILU: within the ulp bar of silu(exact integers) + residual.
+    Then act NONE with each other (bias, residual) presence - the four-wave and reduce kernels' EPI_RESIDUAL, EPI_PLAIN and
+    EPI_GENERIC + NONE with a null residual, the null sides of ``if (p.bias)`` / ``if (p.residual)`` elsewhere - from the same
+    operands and the same ``pre``: bit-equal to ``pre - bias`` (+ residual) where the bias is absent."""
     from phantom_vlb_amd import ops
     M, N = pre.shape
     exact = pre.double() + res.double()
     off = {"c+1": 1, "c+4": 4}.get(how, 0)
-    for act in (ops.ACT_NONE, ops.ACT_SILU) if act_silu else (ops.ACT_NONE,):
-        buf = None
-        residual = res
+
+    def output(with_res):
         if off:
             out, buf = _offset_out(M, N, off, dev)
             assert out.data_ptr() % 16 == (2 * off) % 16
-        elif how == "alias":
-            out = residual = res.clone()            # residual aliases C
-        else:
-            out = torch.full((M, N), 7.0, dtype=BF, device=dev)
+            return out, res, buf
+        if how == "alias" and with_res:
+            out = res.clone()                       # residual aliases C
+            return out, out, None
+        return torch.full((M, N), 7.0, dtype=BF, device=dev), res, None
+
+    for act in (ops.ACT_NONE, ops.ACT_SILU) if act_silu else (ops.ACT_NONE,):
+        out, residual, buf = output(True)
         got = ops.gemm(a, w, bias=bias, residual=residual, act=act, a2=a2, w2=w2, out=out)
         if act == ops.ACT_NONE:
             E.assert_bits_equal(got, exact)
         else:
             E.assert_within_ulp(got, E.ACTS["silu"](pre.double()) + res.double(), pre)
+        if buf is not None:
+            _assert_guards(buf, M, N, off)
+    pre_nb = pre.double() - bias.double()[None, :]                                  # exact: integers
+    for with_bias, with_res in ((False, False), (False, True), (True, False)):
+        out, residual, buf = output(with_res)
+        got = ops.gemm(a, w, bias=bias if with_bias else None, residual=residual if with_res else None, a2=a2, w2=w2, out=out)
+        try:
+            E.assert_bits_equal(got, (pre.double() if with_bias else pre_nb) + (res.double() if with_res else 0))
+        except AssertionError as e:
+            raise AssertionError(f"act NONE, bias {with_bias}, residual {with_res}: {e}") from None
         if buf is not None:
             _assert_guards(buf, M, N, off)
 
