@@ -765,6 +765,35 @@ int vlb_ridge_sumsq_accumulate_masked(const float* y, int ldy, const float* keep
 int vlb_ridge_cv_score_rows(const double* X, const double* Gc, const double* Rc, const double* vy, double* ws, double* r_out,
                             const int* info, int E, int V, const int* choice, int want, void* stream);
 
+/* Scoring a held-out split per target (opt-in, TargetScores / Trainer.test; every entry point above keeps its
+ * bits).  The five running sums of the reference's validation callback, (p, y, p^2, y^2, p y) per target, are kept on the
+ * device per block of consecutive clips: sums fp64 [n_slots,5,V], slot = head * nb + block.  fp64 throughout, no atomics, one
+ * owning thread and one summation order per output element, lanes on consecutive targets, 64-bit indices, no contraction (a
+ * host loop in the same order gives the same bits).  keep: fp32, a target counts where keep > 0 (a select, never a product:
+ * NaN / Inf in a masked column of pred or y is harmless); NULL: every target counts.
+ * vlb_score_accumulate (src/utils.py:85-110: the callback's five sums): for b = 0..B-1 in order, sums[slot[b], :, v] +=
+ *   (p, y, p p, y y, p y) with p = (double)pred[b,v], y = (double)y[b,v] (pitches ldp, ldy >= V; the products are exact);
+ *   keep fp32 [H,V] with H = n_slots / nb, clip b reading row slot[b] / nb; a masked target adds +0.0.  slot int32 [B] on the
+ *   device, checked by the caller on the host (an entry outside [0, n_slots) is skipped).  The caller zeroes sums once.
+ * vlb_score_finish (src/utils.py:85-110: the callback's correlation, one head per call): T = sum_j sums_h[j] over j = 0..nb-1
+ *   ascending, n = sum_j n_j;  cov = Tpy - Tp Ty / n, vp = Tpp - Tp^2 / n, vy = Tyy - Ty^2 / n, sse = Tpp - 2 Tpy + Tyy;
+ *   out fp64 [4,V]: r = cov / sqrt(vp vy) clipped to [-1, 1] and 0 unless vp > 0 and vy > 0 (vlb_ridge_cv_score's rule),
+ *   R^2 = 1 - sse / vy or 0 unless vy > 0, mse = sse / n, n; masked targets get NaN in the first three.  avg fp64 [3]: the
+ *   means of r, R^2 and mse over the kept targets, summed by one block (thread t over v = t, t + 256, ... ascending, then the
+ *   256 partials ascending).  keep_h fp32 [V] or NULL.
+ * vlb_score_bootstrap (src/utils.py:85-110: the callback's correlation, resampled over blocks of clips): draws int32 [R,nb] on
+ *   the device, values in [0, nb) (checked by the caller on the host; an entry outside is clamped).  For rho = 0..R-1 in order
+ *   T = sum_{k=0..nb-1} sums_h[draws[rho,k]] and n = sum_k n_j[draws[rho,k]] by additions in index order, r*_rho by
+ *   vlb_score_finish's rule.  out fp64 [3,V]: mean r*, its standard deviation with ddof = 1 (sqrt(max(0, .)); both from the sums
+ *   of d = r* - r*_0 and d^2 in rho order, so equal r* give exactly 0) and p = (1 + #{rho: r*_rho <= 0}) / (R + 1); masked
+ *   targets get NaN.  R >= 2, nb >= 1. */
+int vlb_score_accumulate(const float* pred, int ldp, const float* y, int ldy, const int* slot, const float* keep, double* sums,
+                         int B, int V, int nb, int n_slots, void* stream);
+int vlb_score_finish(const double* sums_h, const double* n_j, int nb, const float* keep_h, double* out, double* avg, int V,
+                     void* stream);
+int vlb_score_bootstrap(const double* sums_h, const double* n_j, int nb, const int* draws, int R, const float* keep_h,
+                        double* out, int V, void* stream);
+
 /* head dropout mask (litmodule :226,251 nn.Dropout(p) in training): out[i] = keep_i / (1-p), keep_i from a
  * counter-based hash of (seed, i) with 16 random bits per element (same mixer as the LoRA masks).  The result is
  * what vlb_head_fwd / vlb_head_bwd take as `keep_scale`. */

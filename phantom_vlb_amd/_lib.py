@@ -153,6 +153,9 @@ SIGNATURES = {
     "vlb_head_l2_rows_ws_doubles": [I],
     "vlb_head_l2_rows_fwd": [P, P, P, P, I, I, P],
     "vlb_head_l2_rows_bwd": [P, P, P, I, I, F, P],
+    "vlb_score_accumulate": [P, I, P, I, P, P, P, I, I, I, I, P],
+    "vlb_score_finish": [P, P, I, P, P, P, I, P],
+    "vlb_score_bootstrap": [P, P, I, P, I, P, P, I, P],
     "vlb_allreduce_scalar": [P, P, I, P],
     "vlb_cast_f32_to_bf16": [P, P, L, P],
     "vlb_cast_bf16_to_f32": [P, P, L, P],

@@ -61,9 +61,23 @@ class VLBDataModuleConfig:
     # N files per subject), the subjects' datasets are concatenated in this order and every item carries "subject", its index
     # into this list (litmodule.config.subjects must be the same list).  None: one subject, ``subject``, as the reference
     subjects: list | None = None
+    # the held-out test split: the same grammar as ``lazyload_path``, ``{subject}`` included; every matching
+    # file of ``test_seasons`` (required with real files, expanded as ``seasons`` are) goes to ``datasets.test``, there is no
+    # split; ``synthetic:NxM``: N files per subject with the seeds random_state + 5003 + k + 1009 g.  None: no test split
+    test_lazyload_path: str | None = None
+    test_seasons: list | None = None
 
     def __post_init__(self):
         from .head import check_subjects
+        tp = self.test_lazyload_path
+        if tp is not None:
+            if not isinstance(tp, str) or not tp:
+                raise ValueError(f"test_lazyload_path={tp!r}: a path pattern or synthetic:NxM is needed (leave it unset for no test split)")
+            if not tp.startswith("synthetic:") and not self.test_seasons:
+                raise ValueError(f"test_lazyload_path={tp!r} needs test_seasons, the seasons whose files form the test split")
+            if self.subjects is not None and not tp.startswith("synthetic:") and "{subject}" not in tp:
+                raise ValueError(f"subjects={list(self.subjects)!r} needs the literal {{subject}} in test_lazyload_path (it is expanded "
+                                 f"per subject); got {tp!r}")
         if self.subjects is not None:
             self.subjects = list(check_subjects(self.subjects))
             if not self.lazyload_path.startswith("synthetic:") and "{subject}" not in self.lazyload_path:
@@ -166,20 +180,54 @@ class VLBDatasets:
     test: VLB_Dataset | None = None
 
     SUBJECT_SEED_STRIDE = 1009       # synthetic files of subject g: seeds random_state + k + 1009 g (subject 0: the single-subject run's)
+    TEST_SEED_OFFSET = 5003          # synthetic test files: seeds random_state + 5003 + k + 1009 g
+
+    def _expand(self, lazyload_path, seasons, seed_offset=0, prefix="synthetic"):
+        """One subject's file list -> (files, their names): ``synthetic:NxM`` gives N seeded (seed, M) specs, anything else is
+        globbed per season as the reference does"""
+        c = self.config
+        if lazyload_path.startswith("synthetic:"):
+            n_files, n_samples = (int(x) for x in lazyload_path.split(":", 1)[1].split("x"))
+            return [(c.random_state + k + seed_offset, n_samples) for k in range(n_files)], [f"{prefix}_{k}" for k in range(n_files)]
+        f_list = []
+        for s in seasons:
+            f_list += sorted(glob.glob(
+                lazyload_path.replace("$SCRATCH_PATH", os.environ.get("SCRATCH_PATH", ".")).replace("s*", f"{s}")))
+        return f_list, [os.path.basename(x) for x in f_list]
+
+    def _build_test(self, used):
+        """``datasets.test`` from ``test_lazyload_path``: every matching file, no split; ``used``: the train and val files"""
+        c = self.config
+        path = getattr(c, "test_lazyload_path", None)
+        self.test_names = {}
+        if path is None:
+            return
+        subjects = getattr(c, "subjects", None)
+        files, of, self.test_names = [], [], {}
+        for g, name in enumerate(subjects or [None]):
+            f, names = self._expand(path if name is None else path.replace("{subject}", name), c.test_seasons or [],
+                                    self.TEST_SEED_OFFSET + self.SUBJECT_SEED_STRIDE * g, "synthetic_test")
+            if not f:
+                raise FileNotFoundError(f"no lazy-load files match test_lazyload_path={path!r}" + ("" if name is None else f" for {name!r}"))
+            files, of = files + f, of + [g] * len(f)
+            if name is None:
+                self.test_names = {"test_set": names}
+            else:
+                self.test_names[name] = {"test_set": names}
+
+        def key(x):         # a synthetic file is its seed, a real one its resolved path
+            return ("seed", x[0]) if isinstance(x, tuple) else ("path", os.path.realpath(x))
+        seen = {key(x) for x in used}
+        both = [x for x in files if key(x) in seen]
+        if both or len({key(x) for x in files}) != len(files):
+            raise ValueError(f"test_lazyload_path={path!r}: {both or files!r} also belong to the train or validation split (or are "
+                             "listed twice): a held-out split shares no file with them")
+        self.test = VLB_Dataset(files, c.geometry, c.num_target, subject_of=None if subjects is None else of)
 
     def _split(self, lazyload_path, seed_offset=0):
         """One subject's file list, split as the reference does -> (val files, train files, their names as ``dset_names``)"""
         c = self.config
-        if lazyload_path.startswith("synthetic:"):
-            n_files, n_samples = (int(x) for x in lazyload_path.split(":", 1)[1].split("x"))
-            f_list = [(c.random_state + k + seed_offset, n_samples) for k in range(n_files)]
-            names = [f"synthetic_{k}" for k in range(n_files)]
-        else:
-            f_list = []
-            for s in c.seasons:
-                f_list += sorted(glob.glob(
-                    lazyload_path.replace("$SCRATCH_PATH", os.environ.get("SCRATCH_PATH", ".")).replace("s*", f"{s}")))
-            names = [os.path.basename(x) for x in f_list]
+        f_list, names = self._expand(lazyload_path, c.seasons, seed_offset)
         if not f_list:
             raise FileNotFoundError(f"no lazy-load files match {lazyload_path!r}")
         r = np.random.RandomState(c.random_state)
@@ -195,6 +243,7 @@ class VLBDatasets:
             val_file, train_files, self.dset_names = self._split(c.lazyload_path)
             self.val = VLB_Dataset(val_file, c.geometry, c.num_target)
             self.train = VLB_Dataset(train_files, c.geometry, c.num_target)
+            self._build_test(val_file + train_files)
             return
         # one list and one split (one validation file, drawn with RandomState(random_state)) per subject, concatenated in order
         val, train, val_of, train_of, self.dset_names = [], [], [], [], {}
@@ -204,6 +253,7 @@ class VLBDatasets:
             val_of, train_of = val_of + [g] * len(v), train_of + [g] * len(t)
         self.val = VLB_Dataset(val, c.geometry, c.num_target, subject_of=val_of)
         self.train = VLB_Dataset(train, c.geometry, c.num_target, subject_of=train_of)
+        self._build_test(val + train)
 
 
 class VLBDataModule(_Base):
@@ -231,6 +281,12 @@ class VLBDataModule(_Base):
 
     def val_dataloader(self):
         return self.x_dataloader(dataset=self.datasets.val, shuffle=self.config.shuffle_val_data)
+
+    def test_dataloader(self):
+        """The held-out split in dataset order (never shuffled: a clip's bootstrap block is its rank in its head's clips)."""
+        if self.datasets.test is None:
+            raise ValueError("test_dataloader(): no test split - set datamodule.config.test_lazyload_path (and test_seasons)")
+        return self.x_dataloader(dataset=self.datasets.test, shuffle=False)
 
 
 class DevicePrefetcher:

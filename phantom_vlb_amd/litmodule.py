@@ -212,6 +212,14 @@ class VLBLitModuleConfig:
     # [num_target] file per subject.  Finite, >= 0; a 0/1 file is a mask (targets with weight 0 are neither trained on nor
     # scored, and may be NaN in the data).  None: every target counts alike, as the reference
     target_weights: str | None = None
+    # the evaluation pass (test_step / Trainer.test): per-target r, R^2 and mse over a held-out split.
+    # score_block: contiguous clips per bootstrap block (a clip's block is its rank in its head's clips // score_block, the rule
+    # of ridge_cv_block); score_bootstrap: resamples of those blocks for the standard error and the one-sided p-value of r
+    # (0: none, else >= 2), drawn from score_bootstrap_seed; score_save_predictions: the .npz also holds every prediction
+    score_block: int = 128
+    score_bootstrap: int = 0
+    score_bootstrap_seed: int = 0
+    score_save_predictions: bool = False
 
     def __post_init__(self):
         self.dtype = torch.bfloat16      # reference :155
@@ -238,6 +246,15 @@ class VLBLitModuleConfig:
             raise ValueError(f"ridge_cv_folds={self.ridge_cv_folds!r}: an integer >= 2 is needed")
         if isinstance(self.ridge_cv_block, bool) or not isinstance(self.ridge_cv_block, int) or self.ridge_cv_block < 1:
             raise ValueError(f"ridge_cv_block={self.ridge_cv_block!r}: an integer >= 1 is needed")
+        if isinstance(self.score_block, bool) or not isinstance(self.score_block, int) or self.score_block < 1:
+            raise ValueError(f"score_block={self.score_block!r}: an integer >= 1 is needed")
+        if isinstance(self.score_bootstrap, bool) or not isinstance(self.score_bootstrap, int) or self.score_bootstrap < 0 \
+                or self.score_bootstrap == 1:
+            raise ValueError(f"score_bootstrap={self.score_bootstrap!r}: 0 (no bootstrap) or an integer >= 2 is needed")
+        if isinstance(self.score_bootstrap_seed, bool) or not isinstance(self.score_bootstrap_seed, int) or self.score_bootstrap_seed < 0:
+            raise ValueError(f"score_bootstrap_seed={self.score_bootstrap_seed!r}: an integer >= 0 is needed")
+        if not isinstance(self.score_save_predictions, bool):
+            raise ValueError(f"score_save_predictions={self.score_save_predictions!r}: true or false is needed")
         if self.ridge_lambda_grid is not None:
             if self.ridge_fit != "closed_form":
                 raise ValueError("ridge_lambda_grid is the closed-form fit's choice of l2_lambda: set ridge_fit='closed_form' "
@@ -745,12 +762,13 @@ class VLBLitModule(_Base):
         save_file(self.merged_state_dict(), path)
         return path
 
-    def _common_step(self, batch, train: bool):
+    def _common_step(self, batch, train: bool, use_cache: bool = True):
+        """``use_cache=False`` (the evaluation pass): the feature cache is not consulted, the clip runs the backbone"""
         cfg, g = self.config, self.geometry
         dev = self.device
         self._cached_step = False
         subject = check_batch_subjects(batch, getattr(cfg, "subjects", None), len(batch["timeseries"]))
-        cache = self.feature_caches.get("train" if train else "val") if cfg.cache_features and "index" in batch else None
+        cache = self.feature_caches.get("train" if train else "val") if cfg.cache_features and use_cache and "index" in batch else None
         if cache is not None and cache.lookup(batch["index"]):
             # every clip's features are cached: no backbone, no weight mask; the same head kernels on the same fp32 inputs
             y = batch["timeseries"].to(dev, torch.float32).to(torch.bfloat16).float().contiguous()
@@ -1073,6 +1091,71 @@ class VLBLitModule(_Base):
         if "subject" in batch:            # per-subject validation correlations (LogValAccuracyCallback)
             out["subject"] = torch.as_tensor(batch["subject"]).detach().cpu().to(torch.int64)
         return out
+
+    # ------------------------------------------------------------------ evaluation pass
+    def on_test_epoch_start(self):
+        """Lightning hook: a fresh ``TargetScores`` (target weights' mask as the keep mask); with ``ema_decay`` and ``ema_eval``
+        the whole pass runs inside ``averaged_weights()``, as a validation epoch does."""
+        from .evaluate import TargetScores
+        cfg = self.config
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise ValueError(f"the evaluation pass with WORLD_SIZE={os.environ['WORLD_SIZE']}: scoring is single-process only "
+                             "(clips must arrive in dataset order); run one process")
+        self.test_scores = TargetScores(cfg.num_target, getattr(cfg, "subjects", None), self.target_weight_mask(),
+                                        getattr(cfg, "score_block", 128), self.device,
+                                        save_predictions=bool(getattr(cfg, "score_save_predictions", False)))
+        self.test_scores_result = None
+        self._test_loss, self._test_batches = None, 0
+        if self.__dict__.get("_ema_test_ctx") is None and self._ema_buffer() is not None and getattr(cfg, "ema_eval", False):
+            self._ema_test_ctx = self.averaged_weights()
+            self._ema_test_ctx.__enter__()
+
+    def test_step(self, batch):
+        """``validation_step`` on a clip of the evaluation split: the same eval-mode forward (the feature cache is not
+        consulted), ``test/brain_loss``, and the clip's predictions and targets into ``self.test_scores``."""
+        if self.__dict__.get("test_scores") is None:
+            self.on_test_epoch_start()
+        if "timeseries" not in batch:
+            raise ValueError("test_step: the batch has no \"timeseries\": scoring needs targets (pure prediction is out of scope)")
+        was = self.training
+        self.train(False)
+        pred, y, terms = self._common_step(batch, train=False, use_cache=False)
+        self.backbone.launch_deferred_video_tokens()
+        self.train(was)
+        loss = terms[2].clone()
+        self.log("test/brain_loss", loss)
+        out = {"loss": loss, "brain_preds": pred.clone(), "brain_vals": y}
+        if "subject" in batch:
+            out["subject"] = torch.as_tensor(batch["subject"]).detach().cpu().to(torch.int64)
+        self.test_scores.add(out["brain_preds"], y, out.get("subject"), batch.get("index"))
+        self._test_loss = loss.double() if self._test_loss is None else self._test_loss + loss.double()
+        self._test_batches += 1
+        return out
+
+    def on_test_epoch_end(self):
+        """Leaves the EMA context, finishes the scores (``self.test_scores_result``) and logs ``test/brain_loss`` (the mean of the
+        batches'), ``test_corr_avg``, ``test_r2_avg`` and ``test/brain_mse`` - with ``subjects`` also ``<key>/<subject>`` for every
+        subject that had clips, the plain key being the mean over those (as ``val_corr_avg``)."""
+        ctx, self._ema_test_ctx = self.__dict__.get("_ema_test_ctx"), None
+        if ctx is not None:
+            ctx.__exit__(None, None, None)
+        cfg = self.config
+        scores = self.__dict__.get("test_scores")
+        if scores is None:
+            return
+        res = scores.finish(getattr(cfg, "score_bootstrap", 0), getattr(cfg, "score_bootstrap_seed", 0))
+        self.test_scores_result = res
+        if self._test_batches:
+            self.log("test/brain_loss", float(self._test_loss) / self._test_batches)
+        keys = ("test_corr_avg", "test_r2_avg", "test/brain_mse")
+        had = [g for g in range(scores.H) if scores.counts[g] > 0]
+        if scores.subjects is not None:
+            for g in had:
+                for k, a in zip(keys, res["avg"][g]):
+                    self.log(f"{k}/{scores.subjects[g]}", float(a))
+        if had:
+            for i, k in enumerate(keys):
+                self.log(k, float(sum(res["avg"][g][i] for g in had) / len(had)))
 
     # ------------------------------------------------------------------ hooks Lightning's fit loop calls (reference train.py:41-56)
     def configure_gradient_clipping(self, optimizer, gradient_clip_val=None, gradient_clip_algorithm=None):

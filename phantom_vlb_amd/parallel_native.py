@@ -8,6 +8,7 @@ travels through its store / a broadcast) and what the default transport uses; th
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 import torch.distributed as dist
@@ -31,6 +32,7 @@ class DirectComm:
             c.group, c.world, c.rank = None, world, r
             c._h = ctypes.c_void_p(handles[r])
             c._stage, c._loop_stage = None, stage             # the staging buffer lives as long as any communicator
+            c._pid = os.getpid()
             c.stream = torch.cuda.Stream(device=device)
             out.append(c)
         return out
@@ -47,16 +49,21 @@ class DirectComm:
             dist.broadcast_object_list(ids, src=0, group=group)
             buf = (ctypes.c_ubyte * 128).from_buffer_copy(ids[0])
         self._h = ctypes.c_void_p()
+        self._pid = os.getpid()
         check(lib.vlb_comm_init(self.rank, self.world, buf, ctypes.byref(self._h)), "vlb_comm_init")
         self._stage = None
         # collectives run on a side stream (event hand-off with the compute stream), like torch's NCCL stream
         self.stream = stream if stream is not None else torch.cuda.Stream()
 
     def __del__(self):
+        # Only the process that made the communicator destroys it.  A forked child (multiprocessing's Manager server, a
+        # fork-context worker) inherits the parent's objects, garbage included; when its collector finalises such a copy the
+        # handle points at RCCL / HIP state whose threads and device context do not exist there, and destroying it crashes
+        # the child.  The parent's own object still destroys the communicator once.
         h = getattr(self, "_h", None)
-        if h:
+        if h and getattr(self, "_pid", None) == os.getpid():
             lib.vlb_comm_destroy(h)
-            self._h = None
+        self._h = None
 
     def _enter(self):
         self.stream.wait_stream(torch.cuda.current_stream())

@@ -305,6 +305,51 @@ class Trainer:
         self._log(metrics)
         return metrics
 
+    def test(self, model, datamodule=None, dataloaders=None, ckpt_path=None):
+        """The evaluation pass: ``on_test_epoch_start`` / ``test_step`` / ``on_test_epoch_end`` over
+        ``dataloaders`` (default ``datamodule.test_dataloader()``; clips must arrive in dataset order), after loading
+        ``ckpt_path`` through ``load_trainable_checkpoint``.  -> ``[metrics]`` (the ``test*`` values the module logged), which also
+        go to the loggers; the per-target result stays in ``model.test_scores_result``.  One process only.  Trainables,
+        optimiser state and dropout counters are not touched (beyond what loading ``ckpt_path`` sets)."""
+        if self.world > 1:
+            raise ValueError(f"Trainer.test with WORLD_SIZE={self.world}: the evaluation pass is single-process only (clips are "
+                             "scored in dataset order; data-parallel evaluation is not supported); run one process")
+        self.model = model
+        model.trainer = self
+        model.configure_model()
+        if ckpt_path:
+            if getattr(model, "optimizer", None) is None and getattr(model.config, "ema_decay", None) is not None:
+                model.configure_optimizers()         # the averaged weights live in the optimiser: ema_eval reads them from there
+            load_trainable_checkpoint(model, ckpt_path)
+        loader = dataloaders if dataloaders is not None else datamodule.test_dataloader()
+        dataset = getattr(loader, "dataset", None)
+        was = getattr(dataset, "features_only", False)
+        if was:
+            dataset.features_only = False            # the feature cache is not consulted: every clip runs the backbone
+        if torch.cuda.is_available() and not hasattr(loader, "iter_selected"):
+            from .datamodule import DevicePrefetcher
+            loader = DevicePrefetcher(loader, model.device, ("language", "padvals", "subject", "index"),
+                                      on_staged=getattr(model, "prefetch_vision", None),
+                                      on_discard=getattr(model, "discard_prefetched_vision", None))
+        try:
+            model.on_test_epoch_start()
+            self._cb("on_test_epoch_start", model)
+            for bi, batch in _iter_selected(loader, None, None):
+                out = model.test_step(batch)
+                self._cb("on_test_batch_end", model, out, batch, bi)
+            model.on_test_epoch_end()
+            self._cb("on_test_epoch_end", model)
+        finally:
+            if was:
+                dataset.features_only = True
+            ctx = model.__dict__.get("_ema_test_ctx")
+            if ctx is not None:                      # an exception inside the pass: back on the last iterate
+                model._ema_test_ctx = None
+                ctx.__exit__(None, None, None)
+        metrics = {k: float(v) for k, v in getattr(model, "logged", {}).items() if k.startswith(("test/", "test_"))}
+        self._log(metrics)
+        return [metrics]
+
     def fit(self, model, datamodule=None, ckpt_path=None):
         # frozen-backbone feature cache (feature_cache.py): one process only - with sharded frozen weights a rank that skipped
         # its forward would leave the others waiting in their per-layer all-gathers

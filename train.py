@@ -8,6 +8,9 @@ Lightning objects (VLBLitModule / VLBDataModule / LogValAccuracyCallback subclas
 package is importable, so the reference's own unchanged train.py can drive them too): ONE device, exercised only against
 tests/fake_lightning.py so far.  Comet logging is optional: without ``comet_ml`` or
 credentials only the CSV logger is attached.
+
+Root keys beyond the reference's: ``export_merged=<file>`` (merged LoRA weights) and the evaluation pass ``evaluate=test|val``,
+``evaluate_out=<file.npz>``, ``ckpt_path=<file>``, ``fit=false`` (``check_evaluate_keys``).
 """
 from __future__ import annotations
 
@@ -30,7 +33,37 @@ def export_merged(litmodule, path: str) -> str:
     return out
 
 
+def check_evaluate_keys(config: dict) -> tuple:
+    """Root keys of the evaluation pass -> (split or None, fit, ckpt_path): ``evaluate=test|val`` scores that
+    split after the fit (``evaluate_out=<file.npz>``, default ``<output_dir>/scores_<split>.npz``); ``ckpt_path=<file>`` is
+    handed to ``fit``, or with ``fit=false`` - which skips the fit and needs it - to ``test``."""
+    split, fit, ckpt = config.get("evaluate"), config.get("fit", True), config.get("ckpt_path")
+    if split is not None and split not in ("test", "val"):
+        raise ValueError(f"evaluate={split!r}: expected test or val")
+    if not isinstance(fit, bool):
+        raise ValueError(f"fit={fit!r}: true or false is needed")
+    if not fit and not ckpt:
+        raise ValueError("fit=false skips the fit and evaluates a saved run: it needs ckpt_path=<file>")
+    if not fit and split is None:
+        raise ValueError("fit=false without evaluate=test|val leaves nothing to do")
+    if config.get("evaluate_out") and split is None:
+        raise ValueError(f"evaluate_out={config['evaluate_out']!r} needs evaluate=test|val")
+    if split == "test" and not config["datamodule"]["config"].get("test_lazyload_path"):
+        raise ValueError("evaluate=test needs datamodule.config.test_lazyload_path (the held-out split)")
+    return split, fit, (str(ckpt) if ckpt else None)
+
+
+def evaluate(trainer, litmodule, datamodule, split: str, out_path: str, ckpt_path=None) -> str:
+    """Score ``split`` through ``Trainer.test`` (both splits go through the same ``TargetScores``) and write the ``.npz``."""
+    loader = datamodule.test_dataloader() if split == "test" else datamodule.x_dataloader(datamodule.datasets.val, shuffle=False)
+    metrics = trainer.test(litmodule, dataloaders=loader, ckpt_path=ckpt_path)[0]
+    out = litmodule.test_scores.write(out_path)
+    print(f"[train] {split} scores written to {out}: " + ", ".join(f"{k}={v:.6g}" for k, v in sorted(metrics.items())))
+    return out
+
+
 def train(config: dict) -> None:
+    split, do_fit, ckpt_path = check_evaluate_keys(config)            # before anything is built
     if config.get("export_merged") and not config["litmodule"]["config"].get("use_lora"):       # before the fit, not after it
         raise ValueError(f"export_merged={config['export_merged']!r} needs a LoRA run (litmodule.config.use_lora=true)")
     import torch
@@ -67,8 +100,14 @@ def train(config: dict) -> None:
     datamodule = instantiate(config["datamodule"])
     print("[train] datasets:", datamodule.datasets.dset_names)
     litmodule = instantiate(config["litmodule"])
-    trainer.fit(model=litmodule, datamodule=datamodule)
-    trainer.save_checkpoint(config["output_dir"])          # reference train.py:58 -> <output_dir>/final.ckpt
+    if getattr(datamodule.datasets, "test_names", None):
+        print("[train] test split:", datamodule.datasets.test_names)
+    if do_fit:
+        trainer.fit(model=litmodule, datamodule=datamodule, **({"ckpt_path": ckpt_path} if ckpt_path else {}))
+        trainer.save_checkpoint(config["output_dir"])          # reference train.py:58 -> <output_dir>/final.ckpt
+    if split is not None:
+        out_path = config.get("evaluate_out") or os.path.join(config["output_dir"], f"scores_{split}.npz")
+        evaluate(trainer, litmodule, datamodule, split, out_path, None if do_fit else ckpt_path)
     if config.get("export_merged"):
         export_merged(litmodule, config["export_merged"])
 
